@@ -2,9 +2,10 @@
 """bench.py — SeTok encode_images throughput on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--workload cfg2|cfg3|cfg4|cfg4-forward|cfg5]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Started WITHOUT a launcher (`WORLD_SIZE` unset) and with --gpus N > 1, the script re-executes itself under
+Started WITHOUT a launcher (`WORLD_SIZE` unset) and with --gpus N > 1, the script starts itself as a child process under
 `torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (the reference's own parallelism is data
 parallelism under a launcher: scripts/train_setok.sh:38-39, scripts/zero2.json:16-22); it never prints `n_gpus: 1` for a run
 that asked for more, and exits with an error if fewer than N GPUs are visible.
@@ -15,11 +16,13 @@ clustering -> per-cluster encoder + mean -> inter-cluster encoder -> out Linear 
 Images shard embarrassingly: every rank encodes its own batch, there is no collective on the data
 path (weak scaling); the only collectives are the barrier and the MAX over ranks of the wall time.
 
-Rank 0 prints ONE JSON line with the driver's fields plus `roofline` (dominant kernel = the bf16
-MFMA GEMM; achieved = algorithmic FLOPs of the GEMM launches / their HIP-event durations measured
-inside the timed region on the launch stream) and `cpu_baseline` (the CPU oracle — a port of the
-reference's forward, validated against the reference in the build container — timed on this box's
-host cores on a bounded sample of the same workload).
+A plain run sets up, warms up, times the --steps steps (no probes on the launches), writes the outputs of the last
+timed step when --dump-outputs DIR is given, and prints ONE JSON line from rank 0: metric, value, unit,
+higher_is_better, dtype, ms_per_step and the workload's config.  Everything else is measured only under --full:
+`roofline` (dominant kernel = the bf16 MFMA GEMM; achieved = algorithmic FLOPs of the GEMM launches / their HIP-event
+durations measured inside the timed region on the launch stream, every --probe-every-th step), the live PMC passes,
+clock / power under load, the select_layer = -2 steps, and `cpu_baseline` (the CPU oracle — a port of the reference's
+forward, validated against the reference — timed on the host cores on a bounded sample of the same workload).
 """
 from __future__ import annotations
 
@@ -167,8 +170,9 @@ def gpu_telemetry(step, device_index, n_steps=6):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: become N ranks.  Re-executes this script under torch.distributed.run (one process per
-    GPU, rendezvous on 127.0.0.1 at a free port); the re-executed ranks see WORLD_SIZE and take the normal path."""
+    """`python bench.py --gpus N` without a launcher: become N ranks.  Runs this script again under torch.distributed.run in a child process
+    (one process per GPU, rendezvous on 127.0.0.1 at a free port) and exits with its status; the ranks see WORLD_SIZE and take the normal path."""
+    import subprocess
     import socket
     if not args.launch_check and not args.share_gpu:
         n_vis = torch.cuda.device_count()
@@ -181,7 +185,11 @@ def self_launch(args):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     log("no launcher in the environment: " + " ".join(cmd))
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    if rc < 0:                                              # killed by a signal: report it as a shell does (128 + signal: 134 abort, 139 segfault)
+        log(f"torch.distributed.run ended on signal {-rc}")
+        rc = 128 - rc
+    sys.exit(rc)
 
 
 def launch_check(rank, world, local):
@@ -241,7 +249,7 @@ def live_traffic(select_layer, log):
             out = os.path.join(tmp, counter)
             t0 = time.perf_counter()
             r = subprocess.run(["rocprofv3", "--kernel-trace", "--pmc", counter, "-d", out, "-o", "p", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                                "--steps", "2", "--warmup", "1", "--timed-only", "--select-layer", str(select_layer)],
+                                "--steps", "2", "--warmup", "1", "--full", "--timed-only", "--select-layer", str(select_layer)],
                                cwd="/tmp", env=env, capture_output=True, text=True, timeout=150)
             found = [os.path.join(dp, f) for dp, _, fs in os.walk(out) for f in fs if f.endswith(".db")]
             if r.returncode != 0 or not found:
@@ -263,6 +271,40 @@ def live_traffic(select_layer, log):
 
 def gemm_class(p):
     return p["kernel"].split(":", 1)[1] if ":" in p["kernel"] else "all"
+
+
+DUMP_BYTES = {"tokens": 32 << 20, "logits": 24 << 20}     # --dump-outputs: per-array caps (64 MiB in all at most, counts and scalars included)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, out, step):
+    """What the timed path returned in its last step, as float32 / float64 .npy files under `path`: the packed tokens (`tokens`, with the
+    per-image `counts`), and where the workload has them the reconstruction loss (cfg3), the logits and the LM loss (cfg5).  An array above
+    its cap in DUMP_BYTES is replaced by a fixed, seeded sample of its rows (kept in order); `<name>_rows` then holds the row indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    written = []
+    arrays = {"tokens": out.packed, "counts": torch.tensor(out.counts, dtype=torch.float64)}
+    if hasattr(step, "recon_loss"):
+        arrays["reconstruction_loss"] = step.recon_loss.reshape(1)
+    if hasattr(step, "logits"):
+        arrays["logits"] = step.logits.reshape(-1, step.logits.shape[-1])
+        arrays["lm_loss"] = step.loss.reshape(1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        cap = DUMP_BYTES.get(name)
+        if cap is not None and t.numel() * 4 > cap:
+            n_rows = max(1, cap // (t[0].numel() * 4))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(DUMP_SEED))[:n_rows].sort().values
+            np.save(os.path.join(path, name + "_rows.npy"), rows.double().numpy())
+            written.append(name + "_rows")
+            t = t[rows.to(t.device)]
+        elif os.path.exists(os.path.join(path, name + "_rows.npy")):
+            os.remove(os.path.join(path, name + "_rows.npy"))          # (a sample's indices left by an earlier run into the same folder)
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        written.append(name)
+    log(f"outputs of the last timed step written to {path}: {', '.join(written)}")
 
 
 def main():
@@ -296,12 +338,20 @@ def main():
     ap.add_argument("--launch-check", action="store_true", help="CPU-only check of the self-launcher and the rank bookkeeping (gloo)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2",
                     help="cfg2 is the BASELINE.json metric; the others are additional measurements (no cpu_baseline leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, 64 MiB at most: larger outputs as a fixed, "
+                         "seeded sample of their rows); the inputs depend on the arguments only, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: HIP-event probes on the GEMM launches and the roofline built from them, "
+                         "the live PMC passes, clock / power under load, the select_layer = -2 steps and the CPU baseline (a plain run does none of these)")
     args = ap.parse_args()
     img, b_default, with_decoder, workload_desc = WORKLOADS[args.workload]
     if args.batch is None:
         args.batch = b_default
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)                                   # does not return
 
@@ -407,19 +457,23 @@ def main():
         log(f"warmup step {i} done")
     startup_s = time.perf_counter() - T_START                       # process start -> model built, context warm, warm-up steps done: what a rank spends before the barrier
     barrier()
-    ops.profile_start()                          # HIP events around every GEMM launch, on the launch stream ...
-    pe = max(1, args.probe_every)                # ... of every pe-th timed step: the probe has a cost of its own (see --probe-every)
+    full = args.full
+    pe = max(1, args.probe_every) if full else 0  # --full: HIP events around every GEMM launch, on the launch stream, of every pe-th timed step
+    if full:                                     # (the probe has a cost of its own, see --probe-every); a plain run is not probed
+        ops.profile_start()
     probed_steps = 0
     t0 = time.perf_counter()
     for i in range(args.steps):
         if pe > 1:
             ops.profile_pause(i % pe != 0)
-        probed_steps += 1 if i % pe == 0 else 0
+        probed_steps += 1 if pe and i % pe == 0 else 0
         out = step()
     barrier()
     dt_local = time.perf_counter() - t0
-    prof = ops.profile_stop()
+    prof = ops.profile_stop() if full else []
     log(f"timed {args.steps} steps in {dt_local:.3f} s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, step)               # before anything below runs the step again
     from setok_amd.parallel import max_over_ranks
     dt = max_over_ranks(dt_local, device=dev)            # wall time of the slowest rank
 
@@ -435,7 +489,7 @@ def main():
 
     # the select_layer = -2 number (the reference classes' default, 23 layers) beside the headline's -1: a few extra steps, untimed above
     other = None
-    if rank == 0 and args.workload == "cfg2" and world == 1 and args.select_layer == -1 and not args.timed_only:
+    if full and rank == 0 and args.workload == "cfg2" and world == 1 and args.select_layer == -1 and not args.timed_only:
         tower = tok.image_feature_encoder
         tower.select_layer = -2
         setok_amd.encode_images(tok, proj, images); torch.cuda.synchronize()
@@ -451,10 +505,10 @@ def main():
 
     # clock / power under load: rank 0 re-runs the step while polling rocm-smi — only where the step has no collective (a training step's
     # all-reduce would wait for ranks that are not stepping)
-    telemetry = gpu_telemetry(step, local) if rank == 0 and not args.timed_only and (world == 1 or trainer is None) else None
+    telemetry = gpu_telemetry(step, local) if full and rank == 0 and not args.timed_only and (world == 1 or trainer is None) else None
     applies = args.workload == "cfg2" and args.dtype == "bf16" and B == 256 and args.select_layer == -1
     traffic, traffic_note = None, None
-    if rank == 0 and world == 1 and applies and not args.timed_only and not args.no_cpu_baseline and not args.no_live_traffic:
+    if full and rank == 0 and world == 1 and applies and not args.timed_only and not args.no_cpu_baseline and not args.no_live_traffic:
         traffic, why = live_traffic(args.select_layer, log)           # the default run: measured here, on this box
         if traffic is None:
             log(f"live PMC passes unavailable ({why}); falling back to the committed passes")
@@ -463,32 +517,17 @@ def main():
             live_note = None
     else:
         live_note = "not collected in this invocation (multi-rank, --timed-only, --no-cpu-baseline or --no-live-traffic)"
-    if traffic is None:
+    if full and traffic is None:
         traffic, traffic_note = load_traffic(applies)
         if traffic is not None:
             traffic["file"] = f"{traffic['file']} (the builder's committed passes; live passes: {live_note})" 
     if rank == 0:
-        gname = {"bf16": "gemm_bf16", "f16": "gemm_f16", "f32": "gemm_f32"}[args.dtype]
-        peak = PEAK_F32_TFLOPS if args.dtype == "f32" else PEAK_BF16_TFLOPS                    # (fp16 and bf16 MFMA: the same dense peak)
-        gemm = [p for p in prof if p["kernel"].split(":")[0] == gname]
-        g_ms = sum(p["ms"] for p in gemm)
-        g_fl = sum(p["flops"] for p in gemm)
-        achieved = g_fl / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
-        classes = {}
-        for p_ in gemm:
-            c = classes.setdefault(gemm_class(p_), dict(launches=0, ms=0.0, flops=0.0, bytes=0.0))
-            c["launches"] += 1; c["ms"] += p_["ms"]; c["flops"] += p_["flops"]; c["bytes"] += p_.get("bytes", 0.0)
-        per_class = {k: {"launches_per_step": v["launches"] // max(probed_steps, 1), "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1),
-                         "avg_launch_ms": round(v["ms"] / v["launches"], 4),
-                         "algorithmic_mb_per_launch": round(v["bytes"] / v["launches"] / 1e6, 1)} for k, v in sorted(classes.items())}
-        alg_bytes = sum(p_.get("bytes", 0.0) for p_ in gemm) / max(len(gemm), 1)
         res = {
             "metric": "images/s SeTok encode (ViT-L/14, 224^2, dyn-k)" if args.workload == "cfg2" else f"images/s SeTok {args.workload}",
             "value": round(world * B * args.steps / dt, 2),
             "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "probe_every": pe,                              # measurement mode of value / ms_per_step: 1 = rounds 1-4's (every step probed), 4 = default since round 5
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": workload_desc, "batch_per_gpu": B, "global_batch": world * B,
@@ -497,52 +536,68 @@ def main():
                                     if trainer is not None else f"dp{world} (images sharded, no data-path collective)") + ("" if args.backend == "nccl" and not args.share_gpu else
                                                                                                    f" [VALIDATION RUN: backend {args.backend}, ranks share one GPU: not a scaling number]"),
                        "per_rank": per_rank, "slowest_rank": max(per_rank, key=lambda r: r["ms_per_step"])["rank"]},
-            "roofline": {"bound": "mfma", "kernel": "gemm_pp_kernel<*> / gemm_persist_kernel<*> / gemm_tail_kernel<*> (every 16-bit MFMA GEMM launch of the step)" if args.dtype != "f32"
-                         else "gemm_f32_kernel (exact-f32 MFMA GEMM, parity mode)",
-                         "achieved": round(achieved, 1), "peak": peak,
-                         "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                         "traffic": traffic["gemm"]["traffic_bytes_per_launch"] if traffic else None,
-                         "algorithmic_bytes_per_launch": round(alg_bytes),
-                         "launches_per_step": len(gemm) // max(probed_steps, 1),
-                         "probe": f"HIP events on every GEMM launch of {probed_steps} of the {args.steps} timed steps (every {pe}-th; --probe-every)",
-                         "avg_launch_ms": round(g_ms / max(len(gemm), 1), 4),
-                         "avg_launch_gflop": round(g_fl / max(len(gemm), 1) / 1e9, 2),
-                         "gemm_share_of_step": round(g_ms / max(probed_steps, 1) / (dt / args.steps * 1e3), 3),
-                         "per_class": per_class},
         }
-        if traffic:
-            res["roofline"]["traffic_source"] = traffic["file"]
-            res["roofline"]["traffic_per_class"] = traffic["gemm"].get("per_class")
-        else:
-            res["roofline"]["traffic_note"] = traffic_note
-        clus = [p for p in prof if p["kernel"] == "cluster_dpc_knn"]
-        if clus:
-            c_ms = sum(p["ms"] for p in clus) / len(clus)
-            c_bytes = sum(p["flops"] for p in clus) / len(clus)                              # the "flops" slot holds algorithmic BYTES here
-            c_gbs = c_bytes / (c_ms * 1e-3) / 1e9
-            gram_tf = 2.0 * B * (img // PATCH) ** 4 * 1024 / (c_ms * 1e-3) / 1e12           # the Gram's 2 N^2 C per image over the whole call
-            res["roofline_clustering"] = {"bound": "hbm", "kernel": "setok_cluster_dpc_knn (Gram -> kNN density -> delta/score -> centres -> assignment)",
-                                          "achieved": round(c_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(c_gbs / PEAK_HBM_GBS, 4),
-                                          "algorithmic_bytes_per_call": round(c_bytes),
-                                          "traffic": traffic["clustering"]["traffic_bytes_per_launch"] if traffic else None,
-                                          "gram_tflops_over_the_call": round(gram_tf, 1),
-                                          "ms_per_call": round(c_ms, 4), "share_of_step": round(c_ms * (len(clus) / max(probed_steps, 1)) / (dt / args.steps * 1e3), 4)}
-        if args.dtype != "f32":
-            res["roofline"]["mfma_only_random_operands_tflops"] = MFMA_ONLY_RANDOM_TFLOPS
-            res["roofline"]["frac_of_mfma_only_random"] = round(achieved / MFMA_ONLY_RANDOM_TFLOPS, 4)
-        if telemetry:
-            res["roofline"].update(telemetry)
-            if telemetry.get("sclk_mhz_under_load"):
-                pk = peak * telemetry["sclk_mhz_under_load"] / 2400.0
-                res["roofline"]["peak_at_measured_clock"] = round(pk, 1)
-                res["roofline"]["frac_at_measured_clock"] = round(achieved / pk, 4)
-        if other:
-            res["config"]["also_select_layer_minus2"] = other
+        if full:                                     # everything besides the headline (see --full)
+            gname = {"bf16": "gemm_bf16", "f16": "gemm_f16", "f32": "gemm_f32"}[args.dtype]
+            peak = PEAK_F32_TFLOPS if args.dtype == "f32" else PEAK_BF16_TFLOPS                    # (fp16 and bf16 MFMA: the same dense peak)
+            gemm = [p for p in prof if p["kernel"].split(":")[0] == gname]
+            g_ms = sum(p["ms"] for p in gemm)
+            g_fl = sum(p["flops"] for p in gemm)
+            achieved = g_fl / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
+            classes = {}
+            for p_ in gemm:
+                c = classes.setdefault(gemm_class(p_), dict(launches=0, ms=0.0, flops=0.0, bytes=0.0))
+                c["launches"] += 1; c["ms"] += p_["ms"]; c["flops"] += p_["flops"]; c["bytes"] += p_.get("bytes", 0.0)
+            per_class = {k: {"launches_per_step": v["launches"] // max(probed_steps, 1), "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1),
+                             "avg_launch_ms": round(v["ms"] / v["launches"], 4),
+                             "algorithmic_mb_per_launch": round(v["bytes"] / v["launches"] / 1e6, 1)} for k, v in sorted(classes.items())}
+            alg_bytes = sum(p_.get("bytes", 0.0) for p_ in gemm) / max(len(gemm), 1)
+            res["probe_every"] = pe                     # measurement mode of value / ms_per_step: 1 = rounds 1-4's (every step probed), 4 = default since round 5
+            res["roofline"] = {"bound": "mfma", "kernel": "gemm_pp_kernel<*> / gemm_persist_kernel<*> / gemm_tail_kernel<*> (every 16-bit MFMA GEMM launch of the step)" if args.dtype != "f32"
+                             else "gemm_f32_kernel (exact-f32 MFMA GEMM, parity mode)",
+                             "achieved": round(achieved, 1), "peak": peak,
+                             "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                             "traffic": traffic["gemm"]["traffic_bytes_per_launch"] if traffic else None,
+                             "algorithmic_bytes_per_launch": round(alg_bytes),
+                             "launches_per_step": len(gemm) // max(probed_steps, 1),
+                             "probe": f"HIP events on every GEMM launch of {probed_steps} of the {args.steps} timed steps (every {pe}-th; --probe-every)",
+                             "avg_launch_ms": round(g_ms / max(len(gemm), 1), 4),
+                             "avg_launch_gflop": round(g_fl / max(len(gemm), 1) / 1e9, 2),
+                             "gemm_share_of_step": round(g_ms / max(probed_steps, 1) / (dt / args.steps * 1e3), 3),
+                             "per_class": per_class}
+            if traffic:
+                res["roofline"]["traffic_source"] = traffic["file"]
+                res["roofline"]["traffic_per_class"] = traffic["gemm"].get("per_class")
+            else:
+                res["roofline"]["traffic_note"] = traffic_note
+            clus = [p for p in prof if p["kernel"] == "cluster_dpc_knn"]
+            if clus:
+                c_ms = sum(p["ms"] for p in clus) / len(clus)
+                c_bytes = sum(p["flops"] for p in clus) / len(clus)                              # the "flops" slot holds algorithmic BYTES here
+                c_gbs = c_bytes / (c_ms * 1e-3) / 1e9
+                gram_tf = 2.0 * B * (img // PATCH) ** 4 * 1024 / (c_ms * 1e-3) / 1e12           # the Gram's 2 N^2 C per image over the whole call
+                res["roofline_clustering"] = {"bound": "hbm", "kernel": "setok_cluster_dpc_knn (Gram -> kNN density -> delta/score -> centres -> assignment)",
+                                              "achieved": round(c_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(c_gbs / PEAK_HBM_GBS, 4),
+                                              "algorithmic_bytes_per_call": round(c_bytes),
+                                              "traffic": traffic["clustering"]["traffic_bytes_per_launch"] if traffic else None,
+                                              "gram_tflops_over_the_call": round(gram_tf, 1),
+                                              "ms_per_call": round(c_ms, 4), "share_of_step": round(c_ms * (len(clus) / max(probed_steps, 1)) / (dt / args.steps * 1e3), 4)}
+            if args.dtype != "f32":
+                res["roofline"]["mfma_only_random_operands_tflops"] = MFMA_ONLY_RANDOM_TFLOPS
+                res["roofline"]["frac_of_mfma_only_random"] = round(achieved / MFMA_ONLY_RANDOM_TFLOPS, 4)
+            if telemetry:
+                res["roofline"].update(telemetry)
+                if telemetry.get("sclk_mhz_under_load"):
+                    pk = peak * telemetry["sclk_mhz_under_load"] / 2400.0
+                    res["roofline"]["peak_at_measured_clock"] = round(pk, 1)
+                    res["roofline"]["frac_at_measured_clock"] = round(achieved / pk, 4)
+            if other:
+                res["config"]["also_select_layer_minus2"] = other
         if det is not None:
             res["config"]["reconstruction_mse"] = round(float(step.recon_loss), 6)      # the step's terminal scalar (random-init decoder vs a random gold image)
         if llm is not None:
             res["config"]["lm_loss"] = round(float(step.loss), 6)
-        if not args.no_cpu_baseline and not args.timed_only and world == 1 and args.workload == "cfg2":
+        if full and not args.no_cpu_baseline and not args.timed_only and world == 1 and args.workload == "cfg2":
             res["cpu_baseline"] = cpu_baseline(tok, proj, select_layer=args.select_layer)
         else:
             res["cpu_baseline"] = None

@@ -13,7 +13,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu)")
-    config.addinivalue_line("markers", "reference: needs /root/reference (build container only)")
     config.addinivalue_line("markers", "grad: runs with torch autograd enabled (everything else runs under torch.no_grad())")
 
 

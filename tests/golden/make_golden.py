@@ -15,6 +15,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.dirname(HERE))
+import golden_io                 # noqa: E402
 import rac_harness as R          # noqa: E402
 import setok_oracle as O         # noqa: E402
 
@@ -26,9 +28,8 @@ def npy(t):
 
 
 def save(name, **arrs):
-    path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **arrs)
-    print(f"wrote {name}.npz  {os.path.getsize(path) / 1024:.1f} KiB")
+    for path in golden_io.save(os.path.join(HERE, name + ".npz"), **arrs):      # in parts of at most 1 MiB where the whole would be larger
+        print(f"wrote {os.path.basename(path)}  {os.path.getsize(path) / 1024:.1f} KiB")
 
 
 def load_weights_into(tok, sd):
@@ -290,7 +291,7 @@ def gen_head_grads():
     """§8(f) row 4: parameter gradients of the reference's head modules by the reference's OWN autograd
     (oracle/rac_harness.py::rac_head_grads) for L = sum_i <tokens_i, upstream_i> on the two dynamic-k images of head_small.npz
     (whose weights and features it reuses).  Stored: the upstream gradients and every parameter gradient."""
-    z = np.load(os.path.join(HERE, "head_small.npz"))
+    z = golden_io.load(os.path.join(HERE, "head_small.npz"))
     sd = {k[2:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("w:")}
     tok = small_tok()
     res = tok.load_state_dict(sd, strict=False)
@@ -336,7 +337,7 @@ def gen_bf16_reference(dt=torch.bfloat16, name="bf16_reference"):
     rel = lambda a, b: float((a.double() - b.double()).abs().max() / b.double().abs().max())
     arrs = {}
     for cfg, src in (("cfg2", "vitl_224"), ("cfg4", "vitl_336")):
-        feats = torch.from_numpy(np.load(os.path.join(HERE, src + ".npz"))["feats"])
+        feats = torch.from_numpy(golden_io.load(os.path.join(HERE, src + ".npz"))["feats"])
         for i in range(feats.shape[0]):
             r = R.rac_head_single(tok, feats[i].to(dt), return_stages=True)
             x, lab = r["x"].float(), r["idx_cluster"]
@@ -382,7 +383,7 @@ def gen_bf16_tower(dt=torch.bfloat16, name="bf16_tower"):
     vc, hc = O.VitConfig(), O.HeadConfig(threshold=0.125)
     tsd, hsd = O.init_tower_weights(vc, seed=0), O.init_head_weights(hc, seed=1)
     d = R.make_clip_dir(vc.hidden_size, vc.num_hidden_layers, vc.num_attention_heads, vc.intermediate_size, vc.image_size, vc.patch_size, seed=0)
-    z = np.load(os.path.join(HERE, "vitl_224.npz"))
+    z = golden_io.load(os.path.join(HERE, "vitl_224.npz"))
     feats32 = torch.from_numpy(z["feats"])
     images = torch.randn(2, 3, 224, 224, generator=torch.Generator().manual_seed(3))
     for sel in (-2, -1):
@@ -415,7 +416,7 @@ def gen_bf16_tower(dt=torch.bfloat16, name="bf16_tower"):
                   f"1 - centre Jaccard {dj:.3f}; tokens with another centre {dp:.3f}")
     # ---- small dims, the whole path (the tower of e2e_small's recipe), 4 images --------------------------------------------------------
     tok = small_tok(sel=-2)
-    sdz = np.load(os.path.join(HERE, "e2e_small.npz"))
+    sdz = golden_io.load(os.path.join(HERE, "e2e_small.npz"))
     sd = {k[2:]: torch.from_numpy(sdz[k]) for k in sdz.files if k.startswith("w:")}
     if sd:
         load_weights_into(tok, sd)
@@ -582,8 +583,113 @@ def gen_lm_loss():
     save("lm_loss", **arrs)
 
 
+def gen_reference_live():
+    """What tests/test_oracle_vs_reference.py compares the oracle with: the reference's own modules run on the inputs those tests build
+    (seeded, regenerated there bit-exactly), plus the small tokenizer's weights and state-dict layout.  A position-encoding table too large
+    to store is held as the SHA-256 of its float32 bytes (the test is bit-exact)."""
+    import copy
+    import hashlib
+    import importlib.util
+    tok = R.build_reference_tokenizer(R.make_clip_dir(64, 3, 4, 128, 112, 14, seed=0), hidden_dim=64, token_feat_dim=96,
+                                      dim_feedforward=128, min_cluster_num=8, threshold=0.5)
+    out = {}
+    raw = tok.state_dict()
+    norm = O.normalise_tower_keys(dict(raw))
+    for k, v in norm.items():
+        out["w:" + k] = npy(v)
+    out["ref_keys"] = np.array(list(raw.keys()))
+    for k, v in raw.items():
+        out["shape:" + k] = np.array(v.shape, np.int64)
+        assert k.startswith("image_feature_encoder.") or torch.equal(norm[k], v)      # the head's keys and values are "w:" + key
+    # head on identical features (seeds 0-3; the threshold is taken from the reference's own scores)
+    for seed in (0, 1, 2, 3):
+        g = torch.Generator().manual_seed(seed)
+        feats = torch.randn(64, 64, generator=g)
+        noise = torch.rand(64, generator=g)
+        s0 = R.rac_head_single(tok, feats, threshold=1e9, noise=noise, return_stages=True)["score"].reshape(-1)
+        thr = float(s0.sort(descending=True).values[10:12].mean())
+        out[f"head:{seed}:thr"] = np.array(thr, np.float64)
+        for j, kw in enumerate((dict(), dict(threshold=thr), dict(k=5, threshold=thr))):
+            ref = R.rac_head_single(tok, feats, noise=noise, return_stages=True, **kw)
+            for name in ("x", "index_down", "idx_cluster", "score", "tokens"):
+                out[f"head:{seed}:{j}:{name}"] = npy(ref[name])
+    # the tower (HF CLIP) at three layer selections
+    g = torch.Generator().manual_seed(3)
+    images = torch.randn(2, 3, 112, 112, generator=g)
+    for sel in (-2, -1, 1):
+        tok.image_feature_encoder.select_layer = sel
+        out[f"tower:{sel}"] = npy(tok.image_feature_encoder(images))
+    tok.image_feature_encoder.select_layer = -2
+    # PositionalEncoding2D
+    _, mod = R.load_reference()
+    for h, w, c in ((16, 16, 1024), (24, 24, 1024), (14, 14, 768), (3, 5, 10)):
+        pe = mod.PositionalEncoding2D(c)(torch.zeros(1, h, w, c)).reshape(h * w, c).contiguous()
+        out[f"pe_sha256:{h}x{w}x{c}"] = np.frombuffer(hashlib.sha256(npy(pe).astype(np.float32).tobytes()).digest(), np.uint8)
+        if h * w * c <= 4096:
+            out[f"pe:{h}x{w}x{c}"] = npy(pe)
+    # the two defects of the reference's forward (D1: a batch of images, D2: a 2-D input to inter_encoder): what they raise
+    for name, call in (("D1", lambda: tok(torch.randn(2, 3, 112, 112))), ("D2", lambda: tok.inter_encoder(torch.randn(5, 64)))):
+        try:
+            call()
+            out["defect:" + name] = np.array("")
+        except Exception as e:
+            out["defect:" + name] = np.array(type(e).__name__)
+    # Q-Former
+    dc = O.DetokConfig(token_feat_dim=48, hidden_dim=32, patch_size=14, image_size=42, decoder_embed_dim=32, decoder_nheads=2,
+                       decoder_depth=1, num_hidden_layers=3, cross_attention_freq=2, mapper_hidden=32, mapper_heads=4,
+                       mapper_intermediate=64)
+    sd = O.init_detok_weights(dc, seed=11)
+    emb, enc = R.build_reference_qformer(hidden=32, heads=4, intermediate=64, layers=3, cross_freq=2, encoder_width=32,
+                                         num_queries=dc.num_queries)
+    torch.manual_seed(0)
+    x = torch.randn(3, 6, 32)
+    mask = torch.ones(3, 6); mask[0, 2:] = 0; mask[2, 5:] = 0
+    q = sd["mask_tokens"].expand(3, -1, -1)
+    out["qformer:mask"] = npy(R.rac_qformer(emb, enc, sd, q, x, mask))
+    out["qformer:nomask"] = npy(R.rac_qformer(emb, enc, sd, q, x, None))
+    # prepare_inputs_labels_for_multimodal: 4 keyword sets x 4 input variants; an output that is None is absent
+    ids, am, labels, feats, W = O.splice_inputs(21, 6, 14, 50, 12)
+    pos = torch.arange(14).expand(6, 14).clone()
+    for i, kw in enumerate([dict(), dict(padding_side="left"), dict(max_length=11), dict(max_length=5, padding_side="left")]):
+        for v, (p_, a_, l_) in enumerate(((pos, am, labels), (None, None, None), (None, am.bool(), labels), (pos, am, None))):
+            ref = R.rac_prepare_inputs(ids, p_, a_, l_, feats, W, **kw)
+            out[f"splice:{i}:{v}:n"] = np.array(len(ref), np.int64)
+            for j, r in enumerate(ref):
+                if r is not None:
+                    out[f"splice:{i}:{v}:{j}"] = npy(r)
+    # the language-model loss statements
+    for i, (seed, B, T, V, padding) in enumerate(((0, 2, 9, 37, "none"), (5, 4, 17, 101, "right"), (6, 3, 13, 64, "left"))):
+        logits, labels_, am_ = O.lm_loss_inputs(seed, B, T, V, padding)
+        out[f"lm_loss:{i}"] = npy(R.rac_lm_loss(logits, labels_, am_))
+    # WeightedMSELoss (loss/mse.py)
+    spec = importlib.util.spec_from_file_location("rac_mse", os.path.join(R.REF_ROOT, "src", "model", "loss", "mse.py"))
+    mse = importlib.util.module_from_spec(spec); spec.loader.exec_module(mse)
+    g = torch.Generator().manual_seed(1)
+    a, b = torch.randn(4, 3, 28, 42, generator=g), torch.randn(4, 3, 28, 42, generator=g)
+    out["pixel_mse"] = npy(mse.WeightedMSELoss()(a, b))
+    # stage 2: the reference's projector + splice under autograd
+    Bm = R.load_reference_projector_builder()
+    seed, B, T, V, Dt, Dh = 21, 4, 11, 30, 48, 32
+    ids, am, labels, feats, W = O.splice_inputs(seed, B, T, V, Dh)
+    g = torch.Generator().manual_seed(seed)
+    toks = [torch.randn(f.shape[0], Dt, generator=g) for f in feats]
+    w_down = torch.randn(V, Dh, generator=g) * 0.3
+    torch.manual_seed(seed)
+    proj = Bm.build_vision_projector("mlp2x_gelu", mm_hidden_size=Dt, hidden_size=Dh)
+    for n, p in proj.named_parameters():
+        out["stage2:param:" + n] = npy(p)
+    pos = torch.arange(T).expand(B, T).clone()
+    loss, embeds, new_labels, pg, tg, _ = R.rac_stage2_grads(copy.deepcopy(proj), toks, ids, pos, am, labels, W, w_down)
+    out["stage2:loss"], out["stage2:embeds"], out["stage2:new_labels"] = npy(loss), npy(embeds), npy(new_labels)
+    for n, t in pg.items():
+        out["stage2:grad:" + n] = npy(t)
+    for i, t in enumerate(tg):
+        out[f"stage2:tokens_grad:{i}"] = npy(t)
+    save("reference_live", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["head_small", "cluster_full", "e2e_small", "vitl", "detok", "splice", "head_grads", "llama", "lm_loss", "stage2"]
+    which = sys.argv[1:] or ["head_small", "cluster_full", "e2e_small", "vitl", "detok", "splice", "head_grads", "llama", "lm_loss", "stage2", "reference_live"]
     if "stage2" in which:
         gen_stage2()
     if "bf16_reference" in which:
@@ -616,3 +722,5 @@ if __name__ == "__main__":
         gen_tower_features_vitl336()
     if "llama_7bdims" in which:
         gen_llama_7bdims()
+    if "reference_live" in which:
+        gen_reference_live()

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 import setok_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,7 @@ def _rel(got, ref):
 
 
 def _case(golden_dir, name):
-    z = np.load(os.path.join(golden_dir, "detok.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "detok.npz"))
     kw = {str(k): v for k, v in zip(z[name + ":cfg_keys"], z[name + ":cfg_vals"])}
     kw = {k: (float(v) if k == "mlp_ratio" else int(v)) for k, v in kw.items()}
     dc = O.DetokConfig(**kw)

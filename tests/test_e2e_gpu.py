@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 import parity
 import setok_oracle as O
 
@@ -43,7 +44,7 @@ def _small_tok(sd, sel=-2, dtype=torch.float32):
 
 @pytest.mark.parametrize("case", ["fallback", "dynamic", "planted", "masked", "k_explicit", "n16_direct"])
 def test_head_small_golden(golden_dir, case):
-    z = np.load(os.path.join(golden_dir, "head_small.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "head_small.npz"))
     sd = {k[2:]: _t(z[k]) for k in z.files if k.startswith("w:")}
     tok = _small_tok(sd)
     feats = _t(z[f"{case}:feats"])
@@ -66,7 +67,7 @@ def test_head_small_golden(golden_dir, case):
 
 @pytest.mark.parametrize("tag", ["sel-2_fallback", "sel-2_dynamic", "sel-1_fallback", "sel-1_dynamic"])
 def test_e2e_small_golden(golden_dir, tag):
-    z = np.load(os.path.join(golden_dir, "e2e_small.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "e2e_small.npz"))
     sd = {k[2:]: _t(z[k]) for k in z.files if k.startswith("w:")}
     sel = int(tag.split("_")[0][3:])
     tok = _small_tok(sd, sel=sel)
@@ -98,7 +99,7 @@ def _vitl_tok(dtype=torch.float32, threshold=0.125, with_tower=True):
 
 def test_vitl_head_from_reference_features(golden_dir):
     """cfg2 dims: the head on the reference's own fp32 tower features."""
-    z = np.load(os.path.join(golden_dir, "vitl_224.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "vitl_224.npz"))
     tok = _vitl_tok(with_tower=False)
     feats = _t(z["feats"])
     hidden = torch.cat([torch.zeros(2, 1, 1024), feats], 1).reshape(-1, 1024).to(DEV)
@@ -121,7 +122,7 @@ def test_vitl_head_from_reference_features(golden_dir):
 
 def test_vitl_tower_fp32_parity(golden_dir):
     """a1 at full ViT-L/14-224 dims in fp32 (exact-f32 MFMA) against the reference's HF tower."""
-    z = np.load(os.path.join(golden_dir, "vitl_224.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "vitl_224.npz"))
     tok = _vitl_tok()
     g = torch.Generator().manual_seed(int(z["spec"][2]))
     images = torch.randn(2, 3, 224, 224, generator=g)
@@ -273,7 +274,7 @@ def test_full_size_batch_invariance_and_properties(dt):
 def test_dataset_side_encode_batch_equals_per_sample(golden_dir):
     """pairDataset.py:419-447: `gen_image = vision_tokenizer(image)`, `num_tokens = gen_image.shape[0]` per sample; the batched form
     returns the same tensors bit-exactly."""
-    z = np.load(os.path.join(golden_dir, "e2e_small.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "e2e_small.npz"))
     sd = {k[2:]: _t(z[k]) for k in z.files if k.startswith("w:")}
     tok = _small_tok(sd)
     g = torch.Generator().manual_seed(5)

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_io
 import setok_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -173,7 +174,7 @@ def test_the_reference_loaders_sequence_in_fp16(golden_dir):
     float16 images (the image processor's output cast by the caller, src/model/setok/clip_encoder.py:55,59).  Round 5 raised TypeError at the
     first kernel.  The features come back in float16, the one setok_encode call equals the op-by-op host path bit for bit, an image's result
     does not depend on its batch, and the tokens sit within 1.5 x the reference's OWN fp16 run of the fp32 reference (tests/golden/fp16_tower.npz)."""
-    zt = np.load(os.path.join(golden_dir, "fp16_tower.npz"))
+    zt = golden_io.load(os.path.join(golden_dir, "fp16_tower.npz"))
     sd = {k[len("small:w:"):]: torch.from_numpy(zt[k]) for k in zt.files if k.startswith("small:w:")}
     tok = _small_tok(torch.float32, sd)
     if hasattr(tok, "load_model"):

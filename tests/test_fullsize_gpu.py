@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 import parity
 import setok_oracle as O
 
@@ -115,8 +116,8 @@ def test_bf16_mode_is_no_worse_than_the_references_own_bf16_run(golden_dir, cfg,
     fp32 clustering of the same features, which is what the GPU computes: 37 / 46 against 36 / 47 at cfg2), with the bf16-rounded weights.
     The measured errors are printed (-s) and recorded in DESIGN.md §2."""
     dt = LOW[low]
-    z = np.load(os.path.join(golden_dir, low + "_reference.npz"))
-    feats = _t(np.load(os.path.join(golden_dir, src + ".npz"))["feats"])
+    z = golden_io.load(os.path.join(golden_dir, low + "_reference.npz"))
+    feats = _t(golden_io.load(os.path.join(golden_dir, src + ".npz"))["feats"])
     hc = O.HeadConfig(threshold=0.125)
     sd_head = {k: v.to(dt).float() for k, v in O.init_head_weights(hc, seed=1).items()}
     tok = _vitl_tok(img=14 * grid, dtype=dt, with_tower=False)
@@ -190,10 +191,10 @@ def test_cfg2_bf16_from_pixels_drifts_no_further_than_the_references_own_bf16_ru
         floors: counts within 20 %, Jaccard >= 0.5, same-centre >= 0.4).
     sel = -2: the reference classes' default layer; sel = -1: what the launch scripts pass (bench.py's headline)."""
     dt = LOW[low]
-    zb = np.load(os.path.join(golden_dir, "bf16_tower.npz"))                     # (holds the reference's fp32 run at select_layer = -1 for both modes)
-    zt = zb if low == "bf16" else np.load(os.path.join(golden_dir, "fp16_tower.npz"))
+    zb = golden_io.load(os.path.join(golden_dir, "bf16_tower.npz"))                     # (holds the reference's fp32 run at select_layer = -1 for both modes)
+    zt = zb if low == "bf16" else golden_io.load(os.path.join(golden_dir, "fp16_tower.npz"))
     if sel == -2:
-        z = np.load(os.path.join(golden_dir, "vitl_224.npz"))
+        z = golden_io.load(os.path.join(golden_dir, "vitl_224.npz"))
         feats32 = _t(z["feats"])
         ref32 = [(_t(z[f"{i}:index_down"]).long(), _t(z[f"{i}:idx_cluster"]).long()) for i in range(2)]
     else:
@@ -234,7 +235,7 @@ def test_small_dims_bf16_tower_from_pixels_against_the_references_bf16_tower(gol
     """The same yardstick at small dims with the weights in the fixture (the whole tower, 4 images): GPU bf16 (fp16) features no further from the
     reference's fp32 features than 1.5 x the reference's own bf16 (fp16) tower."""
     dt = LOW[low]
-    zt = np.load(os.path.join(golden_dir, low + "_tower.npz"))
+    zt = golden_io.load(os.path.join(golden_dir, low + "_tower.npz"))
     sd = {k[len("small:w:"):]: _t(zt[k]) for k in zt.files if k.startswith("small:w:")}
     vc = dict(hidden_size=64, intermediate_size=128, num_hidden_layers=3, num_attention_heads=4, image_size=112, patch_size=14)
     tok = SetokTokenizer(vision_tower=vc, mm_vision_select_layer=-2, hidden_dim=64, token_feat_dim=96, min_cluster_num=8, threshold=0.5, nheads=2,
@@ -256,7 +257,7 @@ def test_small_dims_bf16_tower_from_pixels_against_the_references_bf16_tower(gol
 # ======================================================================================================================================
 def test_cfg4_vitl336_head_fp32_from_reference_features(golden_dir):
     """The head at cfg4 dims on the reference's own fp32 tower features: integers bit-exact, tensors within 1e-4."""
-    z = np.load(os.path.join(golden_dir, "vitl_336.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "vitl_336.npz"))
     tok = _vitl_tok(img=336, with_tower=False)
     feats = _t(z["feats"])
     assert tuple(feats.shape) == (2, 576, 1024)
@@ -280,7 +281,7 @@ def test_cfg4_vitl336_head_fp32_from_reference_features(golden_dir):
 def test_cfg4_vitl336_tower_fp32_and_whole_path_from_pixels(golden_dir):
     """a1 at ViT-L/14-336 in fp32 (exact-f32 MFMA GEMMs, the 19-tile attention path) against the reference's HF tower, then the whole
     path from pixels: every decision the margin analysis calls certain equals the reference's."""
-    z = np.load(os.path.join(golden_dir, "vitl_336.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "vitl_336.npz"))
     tok = _vitl_tok(img=336)
     g = torch.Generator().manual_seed(int(z["spec"][2]))
     images = torch.randn(2, 3, 336, 336, generator=g)
@@ -361,7 +362,7 @@ def test_cfg3_decoder_full_dims_batch_256():
 def test_cfg5_vicuna7b_dims_two_layers_fp32_vs_hf(golden_dir):
     """hidden 4096 / 32 heads x 128 / SwiGLU 11008 / vocab 32000, two decoder layers, fp32: hidden states and logits against HuggingFace
     LlamaForCausalLM's golden outputs (generated by tests/golden/make_golden.py; the 0.67 G weights regenerate from the seed)."""
-    z = np.load(os.path.join(golden_dir, "llama_7bdims.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "llama_7bdims.npz"))
     kw = {str(k): int(v) for k, v in zip(z["cfg_keys"], z["cfg_vals"])}
     seed, B, T, left = (int(v) for v in z["spec"])
     lc = O.LlamaConfigLite(**kw)

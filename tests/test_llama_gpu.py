@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_io
 import setok_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -157,7 +158,7 @@ def test_attention_causal_and_rope_grouped_query(dt, tol, H, Hkv, Dh, T):
 
 
 def _case(golden_dir, name):
-    z = np.load(os.path.join(golden_dir, "llama.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "llama.npz"))
     kw = {str(k): int(v) for k, v in zip(z[name + ":cfg_keys"], z[name + ":cfg_vals"])}
     lc = O.LlamaConfigLite(**kw)
     seed, B, T, left = [int(v) for v in z[name + ":spec"]]
@@ -218,7 +219,7 @@ def test_setokim_forward_splices_then_prefills():
 def test_lm_loss_matches_oracle_and_golden(golden_dir, dt, tol):
     """setok_lm_loss against the oracle (setokim_llama.py:145-160) and, in fp32, the reference's own value; the logits are bf16-representable, so
     both dtypes read the same numbers.  Also: a strided logits view, no valid position -> NaN, and the count."""
-    z = np.load(os.path.join(golden_dir, "lm_loss.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "lm_loss.npz"))
     for c in sorted({k.split(":")[0] for k in z.files}):
         seed, B, T, V = (int(v) for v in z[c + ":spec"])
         logits, labels, am = O.lm_loss_inputs(seed, B, T, V, str(z[c + ":padding"]))

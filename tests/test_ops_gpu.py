@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_io
 import setok_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -284,7 +285,7 @@ def _cluster_gpu(x, k, thr, mcn, noise=None, token_mask=None):
 
 
 def test_cluster_head_small_golden(golden_dir):
-    z = np.load(os.path.join(golden_dir, "head_small.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "head_small.npz"))
     for case in ("fallback", "dynamic", "planted", "masked", "k_explicit"):
         x = torch.from_numpy(z[f"{case}:x"])
         k = int(z[f"{case}:k"]); thr = float(z[f"{case}:threshold"])
@@ -303,7 +304,7 @@ def test_cluster_head_small_golden(golden_dir):
 
 
 def test_cluster_full_dims_golden(golden_dir):
-    z = np.load(os.path.join(golden_dir, "cluster_full.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "cluster_full.npz"))
     n_exact = 0
     for name in sorted({k.split(":")[0] for k in z.files}):
         N, C, m, seed, k, mcn, thr = z[name + ":spec"]
@@ -323,7 +324,7 @@ def test_cluster_full_dims_golden(golden_dir):
 
 def test_cluster_vitl_reference_features(golden_dir):
     """Dynamic-k and fallback branches on the reference's own ViT-L tower features (cfg2 dims)."""
-    z = np.load(os.path.join(golden_dir, "vitl_224.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "vitl_224.npz"))
     feats = torch.from_numpy(z["feats"])
     x = feats + O.pos_encoding_2d(16, 16, 1024)[None]
     for thr, pre in ((0.125, ""), (0.5, "fb:")):

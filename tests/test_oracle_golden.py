@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 import setok_oracle as O
 
 torch.set_num_threads(min(8, os.cpu_count() or 1))
@@ -16,7 +17,7 @@ def _t(a):
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz"))
+    return golden_io.load(os.path.join(golden_dir, name + ".npz"))
 
 
 HEAD_CASES = ["fallback", "dynamic", "planted", "masked", "k_explicit", "n16_direct"]
@@ -292,7 +293,7 @@ def test_llama_prefill_matches_hf(golden_dir, name):
 
 def test_lm_loss_matches_reference(golden_dir):
     """setokim_llama.py:145-160 — the oracle's restatement against the loss the reference's own statements gave (tests/golden/lm_loss.npz)."""
-    z = np.load(os.path.join(golden_dir, "lm_loss.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "lm_loss.npz"))
     cases = sorted({k.split(":")[0] for k in z.files})
     assert len(cases) == 3
     for c in cases:

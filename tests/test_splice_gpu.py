@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 import setok_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _t(a):
 
 
 def _case(golden_dir, name):
-    z = np.load(os.path.join(golden_dir, "splice.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "splice.npz"))
     seed, B, T, V, D, maxlen, left = [int(v) for v in z[name + ":spec"]]
     ids, am, labels, feats, W = O.splice_inputs(seed, B, T, V, D, pad=not name.startswith("nopad"))
     kw = dict(max_length=None if maxlen < 0 else maxlen, padding_side="left" if left else "right")

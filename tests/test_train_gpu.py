@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_io
 import setok_oracle as O
 
 pytestmark = [pytest.mark.gpu, pytest.mark.grad]        # torch-autograd references + the hand-written backward: gradients stay enabled
@@ -148,8 +149,8 @@ def _small_tok(sd, dtype=torch.float32):
 
 
 def _grad_case(golden_dir):
-    z = np.load(os.path.join(golden_dir, "head_small.npz"))
-    gz = np.load(os.path.join(golden_dir, "head_grads.npz"))
+    z = golden_io.load(os.path.join(golden_dir, "head_small.npz"))
+    gz = golden_io.load(os.path.join(golden_dir, "head_grads.npz"))
     sd = {k[2:]: _t(z[k]) for k in z.files if k.startswith("w:")}
     feats = [_t(z["dynamic:feats"]), _t(z["planted:feats"])]
     hidden = torch.cat([torch.cat([torch.zeros(1, 64), f], 0) for f in feats], 0)          # class-token rows that 'patch' drops

@@ -6,9 +6,9 @@ mkdir -p $out
 cd $GRAFT_REPO_ROOT
 bash tools/profile_round.sh $tag > $out/profile_round.log 2>&1
 bash tools/profile_util.sh $tag > $out/profile_util.log 2>&1
-python bench.py > $out/bench_final.json 2> $out/bench_final.err
+python bench.py --full > $out/bench_final.json 2> $out/bench_final.err
 for w in cfg3 cfg4-forward cfg4 cfg5; do
-  python bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err
+  python bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err
 done
 cd /tmp && export TMPDIR=/tmp
 for w in cfg3 cfg4 cfg5; do

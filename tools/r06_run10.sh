@@ -10,7 +10,7 @@ for i in 1 2 3; do
 done > $out/ab_attn_lone_row.log 2>&1
 ab() {
   for tag in "$@"; do
-    SETOK_HIP_LIB=$(lib $tag) timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --probe-every 1 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$tag', d['ms_per_step'], r['achieved'], r['frac'])"
+    SETOK_HIP_LIB=$(lib $tag) timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --probe-every 1 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$tag', d['ms_per_step'], r['achieved'], r['frac'])"
   done
 }
 ab base lr0 base lr0 base lr0 >> $out/ab_attn_lone_row.log 2>&1
