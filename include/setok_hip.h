@@ -360,6 +360,24 @@ int setok_gelu_bwd_dropout(void* stream, int dtype, const void* pre, const void*
 int setok_attention_bwd(void* stream, int dtype, const void* qkv, const int32_t* seg_offsets, int n_segs, int seg_len,
                         const void* out, const void* dout, void* dqkv, int rows, int H, int Dh, float scale, float* ws);
 
+/* Backward of setok_cross_attention (and of self-attention in the same operand layout) for the reconstruction decoder: n_segs groups of q_len query
+ * rows; segment s attends to key / value rows [kv_offsets[s], kv_offsets[s+1]) (at most max_kv of them), or, with kv_offsets == NULL, to the
+ * uniform rows [s * max_kv, (s+1) * max_kv) (self-attention: max_kv = q_len and q, k, v the three column windows of one qkv buffer).
+ * q, out, dout, dq: (n_segs * q_len, >= H*Dh) rows of strides ldq, ldo, lddo, lddq; k, v: rows of stride ldkv; dk, dv: rows of stride lddkv
+ * (the [dk | dv] halves of one buffer, or the dk / dv windows of a dqkv buffer).  Operands and strides 16-byte aligned, Dh % 8 == 0.
+ * The log-sum-exp and do.o of every row are recomputed (nothing is saved by the forward).  Deterministic: no atomics, fixed summation order,
+ * a segment's gradients do not depend on the other segments.  ws: fp32[2 * n_segs * q_len * H]. */
+int setok_mha_bwd(void* stream, int dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                  const int32_t* kv_offsets, int n_segs, int q_len, int max_kv, const void* out, int64_t ldo, const void* dout,
+                  int64_t lddo, void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv, int H, int Dh, float scale, float* ws);
+
+/* Backward of setok_pixel_loss(setok_unpatchify(patches)) in one pass: dpatches (B*gh*gw, ld) receives d loss / d patch rows in the layout
+ * the pixel head's GEMM produced (columns >= 3 p^2, the GEMM's pad, are zero), scaled by upstream[0] (fp32, device: the loss's incoming
+ * gradient).  kind 0 (mse): 2 (pred - gold) / n;  kind 1 (l1): sign(pred - gold) / n with sign(0) = 0;  n = B * 3 * gh*p * gw*p.
+ * kind 2: the backward of setok_unpatchify alone — `pred` is d loss / d image and `gold` is not read. */
+int setok_pixel_loss_bwd(void* stream, int dtype, const void* pred, const void* gold, int kind, const float* upstream, void* dpatches,
+                         int64_t ld, int B, int gh, int gw, int p);
+
 /* Backward of setok_segment_mean (tokenizer.py:151): drows[r, :] = dseg[s, :] / n_s for every member row r of segment s. */
 int setok_segment_mean_bwd(void* stream, int dtype, const void* dseg, const int32_t* seg_offsets, const int32_t* n_segs_dev,
                            int max_segs, void* drows, int C);

@@ -81,6 +81,8 @@ SIGNATURES = {
     "setok_gelu_bwd": [_vp, _i, _vp, _vp, _vp, _i64],
     "setok_gelu_bwd_dropout": [_vp, _i, _vp, _vp, _vp, _i64, _f, C.c_uint64, C.c_uint64],
     "setok_attention_bwd": [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "setok_mha_bwd": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _f, _vp],
+    "setok_pixel_loss_bwd": [_vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _i, _i],
     "setok_segment_mean_bwd": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i],
     "setok_adamw": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f],
     "setok_rmsnorm": [_vp, _i, _vp, _vp, _vp, _i, _i, _f],

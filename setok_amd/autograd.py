@@ -11,6 +11,8 @@ inside the transposes for db, setok_gelu_bwd, setok_layernorm_bwd, setok_splice_
     ProjectorFn   VisionProjector / LinearProjector              d loss / d projector parameters, d loss / d tokens
     SpliceRowsFn  splice_multimodal (the embedding + image rows)    d loss / d projected image tokens (d embed_tokens.weight on request)
     HeadFn        SetokTokenizer.encode_features                    d loss / d head parameters (inner_encoder, inter_encoder, out)
+    DetokFn       SetokDeTokenizer.forward / decode_image /         d loss / d decoder parameters, d loss / d tokens (detok_train.py)
+                  reconstruction_loss
 
 Everything else on the path is inference-only and says so (round 4): the forward always runs — reference-style inference callers
 do not wrap their calls in no_grad and freshly built modules have trainable parameters — and, when torch would have recorded a graph, the
@@ -55,23 +57,25 @@ class _NoBackwardFn(torch.autograd.Function):
     """Identity whose backward raises: the grad_fn of an inference-only module's output when autograd would have expected a graph."""
 
     @staticmethod
-    def forward(ctx, out, what, *deps):
-        ctx.what = what
+    def forward(ctx, out, what, msg, *deps):
+        ctx.what, ctx.msg = what, msg
         return out.view_as(out)
 
     @staticmethod
     def backward(ctx, *grads):
+        if ctx.msg:
+            raise NotImplementedError(ctx.msg)
         raise NotImplementedError(
             f"{ctx.what} ran on the HIP library without an autograd graph (it has no backward pass there): backward() through its output "
             f"would silently train nothing.  Freeze the module (`requires_grad_(False)`), call it under `torch.no_grad()`, or detach its output.")
 
 
-def no_backward(what: str, value, deps: Iterable[Any]):
+def no_backward(what: str, value, deps: Iterable[Any], msg: Optional[str] = None):
     """Inference-only modules whose REFERENCE counterpart is differentiable (Block, SetokDeTokenizer, the LLM prefill): the forward runs as
     inference whatever the grad mode — a freshly built nn.Module has `requires_grad=True` parameters and reference-style inference callers do
     not wrap their calls — and, where torch would have recorded a graph (gradients enabled + an input / parameter requiring one),
     every floating-point tensor of the result carries a grad_fn that RAISES in backward.  Nothing trains silently, nothing that only wants the
-    values crashes."""
+    values crashes.  `msg`: the backward's error message, when the generic one does not say why."""
     if not torch.is_grad_enabled():
         return value
     live = [t for t in deps if isinstance(t, torch.Tensor) and t.requires_grad]
@@ -80,7 +84,7 @@ def no_backward(what: str, value, deps: Iterable[Any]):
 
     def wrap(v):
         if isinstance(v, torch.Tensor):
-            return _NoBackwardFn.apply(v, what, *live) if v.is_floating_point() else v
+            return _NoBackwardFn.apply(v, what, msg, *live) if v.is_floating_point() else v
         if isinstance(v, tuple):
             return tuple(wrap(u) for u in v)
         if isinstance(v, list):
@@ -275,3 +279,28 @@ def head_apply(tok, hidden_rows: torch.Tensor, B: int, k=None, threshold=None, n
     aux: dict = {}
     packed = HeadFn.apply(tok, hidden_rows, B, k, threshold, noise, token_mask, seed, aux, tuple(n for n, _ in named), *[p for _, p in named])
     return packed, aux["counts"], aux["idx"], aux["score"]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the reconstruction decoder (detokenizer.py; the reference trains it with the tokenizer in one graph, model.py:86-92)
+# ----------------------------------------------------------------------------------------------------------------------------
+class DetokFn(torch.autograd.Function):
+    """SetokDeTokenizer's forward ("feats"), decode_image ("image") or reconstruction_loss ("loss") on packed tokens, keeping what
+    detok_train.detok_backward needs.  `names`: the reference names of `params`, in order."""
+
+    @staticmethod
+    def forward(ctx, det, mode: str, counts, kind: str, packed: torch.Tensor, gold: Optional[torch.Tensor], names: Tuple[str, ...],
+                *params: torch.Tensor):
+        saved: Dict[str, Any] = {}
+        out = det._compute(packed.detach(), counts, mode, gold, kind, saved=saved)
+        ctx.det, ctx.saved, ctx.names, ctx.params = det, saved, names, params
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        from .detok_train import detok_backward
+        need = {n: bool(r) for n, r in zip(ctx.names, ctx.needs_input_grad[7:])}
+        dtokens, grads = detok_backward(ctx.det, ctx.saved, g, need_tokens=ctx.needs_input_grad[4], need=need)
+        ctx.saved = None
+        out = tuple(_grad_as(grads.get(n), p) if need[n] else None for n, p in zip(ctx.names, ctx.params))
+        return (None, None, None, None, dtokens, None, None) + out

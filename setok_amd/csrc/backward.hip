@@ -431,10 +431,6 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 int setok_attention_bwd_seg_bf16(hipStream_t s, const bf16* qkv, const int32_t* seg_offsets, int n_segs, const bf16* out, const bf16* dout,
                                  bf16* dqkv, float* lse_ws, float* d_ws, int H, int Dh, float scale);       // attn_seg_bwd.hip
 
-#define DISPATCH_T(NAME, CALL_BF16, CALL_F32)                                  \
-    if (dtype == SETOK_BF16) { CALL_BF16; }                                    \
-    else if (dtype == SETOK_F32) { CALL_F32; }                                 \
-    else return setok_fail(SETOK_EINVAL, NAME ": bad dtype %d", dtype);
 
 extern "C" int setok_transpose(void* stream, int dtype, const void* x, int64_t ldx, int rows, int cols, void* out, int64_t ldo, int chunk,
                                float* colsum_partial) {

@@ -49,6 +49,12 @@ int setok_fail(int code, const char* fmt, ...);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// one entry point, two element types: the 16-bit type of the build (SETOK_BF16) or fp32
+#define DISPATCH_T(NAME, CALL_BF16, CALL_F32)                                  \
+    if (dtype == SETOK_BF16) { CALL_BF16; }                                    \
+    else if (dtype == SETOK_F32) { CALL_F32; }                                 \
+    else return setok_fail(SETOK_EINVAL, NAME ": bad dtype %d", dtype);
+
 // ---- optional launch profiler (capi.hip): HIP events on the launch stream around the GEMM and clustering entry points ------------------
 // Off by default (one relaxed load per call).  bench.py switches it on around its timed region: `roofline.achieved` is the algorithmic
 // work of these launches / their event durations, measured where the launches really happen — inside the library, whichever host calls it.

@@ -205,6 +205,9 @@ class SetokDeTokenizer(PackCacheMixin, nn.Module):
         self.hidden_dim = hidden_dim
         self.decoder_embed_dim = decoder_embed_dim
         self.decoder_nheads = decoder_nheads
+        # the forward is eval-mode arithmetic (no dropout); with non-zero rates a training-mode module refuses the backward pass (detok_train)
+        self.proj_drop_p = float(proj_drop or 0.0)
+        self.attn_drop_p = float(attn_drop or 0.0)
 
         cfg = _resolve_mapper_config(feature_mapper_path_or_name)
         cfg.update(encoder_width=hidden_dim, add_cross_attention=True, cross_attention_freq=cross_attention_freq,
@@ -305,9 +308,11 @@ class SetokDeTokenizer(PackCacheMixin, nn.Module):
 
     # -- stages --------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def _qformer(self, pk, enc: torch.Tensor, kv_offsets: torch.Tensor, B: int, max_kv: int) -> torch.Tensor:
+    def _qformer(self, pk, enc: torch.Tensor, kv_offsets: torch.Tensor, B: int, max_kv: int, saved: Optional[list] = None) -> torch.Tensor:
         """BertModel.forward (module.py:852-1014) as detokenizer.py:105-109 calls it, on packed rows.
-        enc: (sum L_i, hidden) mapped tokens; returns (B * Q, hidden)."""
+        enc: (sum L_i, hidden) mapped tokens; returns (B * Q, hidden).  `saved`: a list that receives, stage by stage, what the backward pass
+        (detok_train.py) needs; the LayerNorms then write fresh tensors instead of overwriting their inputs (the same kernels, the same bits)."""
+        keep = saved is not None
         cfg = self.mapper.cfg
         Hh = cfg["num_attention_heads"]
         hs = cfg["hidden_size"]
@@ -316,36 +321,50 @@ class SetokDeTokenizer(PackCacheMixin, nn.Module):
         Q = self.num_mask_token
         h = ops.layernorm(pk["queries"], *pk["emb_ln"][:2], pk["emb_ln"][2])      # module.py:203; (Q, hs), shared by every image
         nb = 1                                                                      # images the rows of `h` currently stand for
-        for d in pk["layers"]:
+        for li, d in enumerate(pk["layers"]):
             # self-attention among the Q queries (module.py:511-519), BertSelfOutput (:383-387)
             qkv = ops.linear(h, *d["qkv"])
             o = ops.attention(qkv, Hh, Dh, scale, seg_len=Q)
             y = ops.linear(o, *d["so"], residual=h)
-            h = ops.layernorm(y, *d["sln"][:2], d["sln"][2], out=y)
+            if keep:
+                saved.append(("self", li, nb, h, qkv, o, y))
+            h = ops.layernorm(y, *d["sln"][:2], d["sln"][2], out=None if keep else y)
             if "cq" in d:                                                          # module.py:532-546
                 if nb != B:                                                        # first image-dependent step: broadcast the shared rows
                     h = h.unsqueeze(0).expand(B, Q, hs).reshape(B * Q, hs).contiguous()
                     nb = B
+                    if keep:
+                        saved.append(("bcast",))
                 q = ops.linear(h, *d["cq"])
                 kv = ops.linear(enc, *d["ckv"])                                    # (sum L_i, 2 * hs) = [key | value]
                 o = ops.cross_attention(q, kv[:, :hs], kv[:, hs:], Hh, Dh, scale, Q, kv_offsets, B, max_kv)
                 y = ops.linear(o, *d["co"], residual=h)
-                h = ops.layernorm(y, *d["cln"][:2], d["cln"][2], out=y)
+                if keep:
+                    saved.append(("cross", li, h, q, kv, o, y))
+                h = ops.layernorm(y, *d["cln"][:2], d["cln"][2], out=None if keep else y)
             # query feed-forward (module.py:579-582): dense + erf-GELU, dense, LayerNorm(. + input)
             u = ops.linear(h, *d["fi"], act=ops.ACT_GELU_ERF)
             y = ops.linear(u, *d["fo"], residual=h)
-            h = ops.layernorm(y, *d["fln"][:2], d["fln"][2], out=y)
+            if keep:
+                saved.append(("ffn", li, h, u, y))
+            h = ops.layernorm(y, *d["fln"][:2], d["fln"][2], out=None if keep else y)
         if nb != B:                                                                 # no cross-attention layer at all
             h = h.unsqueeze(0).expand(B, Q, hs).reshape(B * Q, hs).contiguous()
+            if keep:
+                saved.append(("bcast",))
         return h
 
     @torch.no_grad()
-    def _pixel_decoder(self, pk, h: torch.Tensor, B: int) -> torch.Tensor:
-        """detokenizer.py:117-120 on rows (B * Q, D): timm Block = x + proj(attn(norm1 x)); x + fc2(gelu(fc1(norm2 x)))."""
+    def _pixel_decoder(self, pk, h: torch.Tensor, B: int, saved: Optional[list] = None) -> torch.Tensor:
+        """detokenizer.py:117-120 on rows (B * Q, D): timm Block = x + proj(attn(norm1 x)); x + fc2(gelu(fc1(norm2 x))).
+        `saved` (see _qformer): per block (input rows, qkv, attention output, rows after the attention residual, GELU output), then the
+        decoder_norm input; the residual sums then go to fresh tensors instead of overwriting `h`."""
         Q, D, Hh = self.num_mask_token, self.decoder_embed_dim, self.decoder_nheads
         Dh = D // Hh
+        keep = saved is not None
         y = st = None
-        for b in pk["blocks"]:
+        for bi, b in enumerate(pk["blocks"]):
+            h_in = h
             if "qkv_ln" in b:
                 st = ops.row_stats(h, b["n1"][2], out=st)
                 qkv = ops.linear_ln(h, b["qkv_ln"], st)
@@ -353,33 +372,36 @@ class SetokDeTokenizer(PackCacheMixin, nn.Module):
                 y = ops.layernorm(h, *b["n1"][:2], b["n1"][2], out=y)
                 qkv = ops.linear(y, *b["qkv"])
             o = ops.attention(qkv, Hh, Dh, Dh ** -0.5, seg_len=Q)
-            ops.linear(o, *b["proj"], residual=h, out=h)
+            h = ops.linear(o, *b["proj"], residual=h, out=None if keep else h)
             if "fc1_ln" in b:
                 st = ops.row_stats(h, b["n2"][2], out=st)
                 u = ops.linear_ln(h, b["fc1_ln"], st, act=ops.ACT_GELU_ERF)
             else:
                 y = ops.layernorm(h, *b["n2"][:2], b["n2"][2], out=y)
                 u = ops.linear(y, *b["fc1"], act=ops.ACT_GELU_ERF)
-            ops.linear(u, *b["fc2"], residual=h, out=h)
+            if keep:
+                saved.append(("block", bi, h_in, qkv, o, h, u))
+            h = ops.linear(u, *b["fc2"], residual=h, out=None if keep else h)
+        if keep:
+            saved.append(("final", h))
         return ops.layernorm(h, *pk["dec_ln"][:2], pk["dec_ln"][2], out=y)
 
     def forward(self, x, attention_masks: Optional[torch.Tensor] = None, return_stages: bool = False):
-        """Inference arithmetic (no autograd graph).  With gradients enabled and a parameter or the tokens requiring one, the result carries a
-        grad_fn whose backward raises (autograd.no_backward): SeTok.forward-style callers that only read the reconstruction run, a
-        `loss.backward()` through the decoder says that it has no backward pass here."""
-        from . import autograd
-        deps = [getattr(x, "packed", x) if not isinstance(x, (list, tuple)) else None, *(x if isinstance(x, (list, tuple)) else ()), *self.parameters()]
-        with torch.no_grad():
-            out = self._forward(x, attention_masks, return_stages)
-        return autograd.no_backward("SetokDeTokenizer.forward", out, deps)
+        """x: RaggedTokens (the tokenizer's output), a list of (L_i, D) tensors, or padded (B, L, D) with `attention_masks` (B, L)
+        (1 = token, 0 = padding; None = all tokens).  Returns (B, Q, decoder_embed_dim).
 
-    def _forward(self, x, attention_masks: Optional[torch.Tensor] = None, return_stages: bool = False):
-        """x: RaggedTokens (the tokenizer's output), a list of (L_i, D) tensors, or padded (B, L, D) with
-        `attention_masks` (B, L) (1 = token, 0 = padding; None = all tokens).  Returns (B, Q, decoder_embed_dim)."""
+        With gradients enabled and the tokens or a parameter requiring one, the result carries the decoder's backward pass (detok_train.py,
+        autograd.DetokFn); the values are the no_grad call's, bit for bit.  The arithmetic is eval mode (no dropout): a module in training mode
+        with a non-zero proj_drop / attn_drop gives a result whose backward raises.  `return_stages=True` is inference-only."""
+        return self._run(x, attention_masks, "feats", return_stages=return_stages)
+
+    def _tokens(self, x, attention_masks):
+        """(packed rows, counts) of any accepted token form — torch plumbing, so a gradient flows back through the gather to the caller's tensor
+        (padding positions get exact zeros)."""
         if isinstance(x, (list, tuple)):
             x = RaggedTokens(torch.cat(list(x), 0), [t.shape[0] for t in x])
         if isinstance(x, RaggedTokens):
-            packed, counts = x.packed, x.counts
+            packed, counts = x.packed, list(x.counts)
         else:
             if x.dim() != 3:
                 raise ValueError("expected padded tokens of shape (B, L, token_feat_dim)")
@@ -396,48 +418,90 @@ class SetokDeTokenizer(PackCacheMixin, nn.Module):
             raise ValueError(f"token feature dim {packed.shape[-1]} != token_feat_dim {self.token_feat_dim}")
         if B == 0 or min(counts) < 1:
             raise ValueError("every image needs at least one token (an all-masked row has no defined softmax on this path)")
+        return packed.to(self.dtype).contiguous(), counts
+
+    def _run(self, x, attention_masks, mode: str, gold: Optional[torch.Tensor] = None, kind: str = "mse", return_stages: bool = False):
+        """mode "feats" (forward), "image" (decode_image) or "loss" (reconstruction_loss)."""
+        from . import autograd
+        packed, counts = self._tokens(x, attention_masks)
+        names, params = zip(*self.named_parameters())
+        if mode == "feats":                                                        # to_pixels takes no part
+            names, params = zip(*[(n, p) for n, p in zip(names, params) if not n.startswith("to_pixels.")])
+        if not autograd.grad_needed(packed, *params):
+            with torch.no_grad():
+                return self._compute(packed, counts, mode, gold, kind, return_stages)
+        if return_stages or (self.training and (self.proj_drop_p > 0.0 or self.attn_drop_p > 0.0)):
+            with torch.no_grad():
+                out = self._compute(packed, counts, mode, gold, kind, return_stages)
+            msg = None
+            if not return_stages:
+                msg = (f"SetokDeTokenizer: training-mode dropout in the decoder (proj_drop={self.proj_drop_p}, attn_drop={self.attn_drop_p}) is not "
+                       f"built: the HIP path computes the eval-mode arithmetic and has no backward pass for the dropout masks.  Call `.eval()` "
+                       f"on the decoder, or build it with proj_drop=0 and attn_drop=0, to get gradients.")
+            entry = dict(feats="forward", image="decode_image", loss="reconstruction_loss")[mode]
+            return autograd.no_backward(f"SetokDeTokenizer.{entry}", out, [packed, *params], msg=msg)
+        return autograd.DetokFn.apply(self, mode, counts, kind, packed, gold, tuple(names), *params)
+
+    def _compute(self, packed: torch.Tensor, counts, mode: str, gold: Optional[torch.Tensor], kind: str, return_stages: bool = False,
+                 saved: Optional[dict] = None):
+        """The arithmetic of the three entry points on packed tokens.  `saved` (a dict): filled with what detok_train.detok_backward needs."""
+        B = len(counts)
         pk = self._pack()
-        packed = packed.to(self.dtype).contiguous()
         offs = torch.zeros(B + 1, dtype=torch.int32)
         offs[1:] = torch.tensor(counts, dtype=torch.int32).cumsum(0)
         kv_offsets = offs.to(packed.device, non_blocking=True)
+        st_q = st_p = None
+        if saved is not None:
+            st_q, st_p = [], []
+            saved.update(pk=pk, packed=packed, counts=list(counts), kv_offsets=kv_offsets, qformer=st_q, blocks=st_p, mode=mode, kind=kind)
 
         enc = ops.linear(packed, *pk["fc_in"])                                     # detokenizer.py:104
-        mapped = self._qformer(pk, enc, kv_offsets, B, max(counts))                # :105-109
+        mapped = self._qformer(pk, enc, kv_offsets, B, max(counts), saved=st_q)    # :105-109
         dec = ops.linear(mapped, *pk["dec_in"])                                    # :111
         Q, D = self.num_mask_token, self.decoder_embed_dim
         pos = self.position_embedding.table(self.height, self.weight, dec.dtype, dec.device, crop=D)   # :112-114, module.py:145
         dec_in = ops.select_add_pos(dec, pos, B, Q, 0)                             # :115
         stages = dict(enc=enc, mapped=mapped.reshape(B, Q, -1), dec_in=dec_in.reshape(B, Q, D).clone()) if return_stages else None
-        out = self._pixel_decoder(pk, dec_in, B).reshape(B, Q, D)                  # :117-120
+        if saved is not None:
+            saved.update(enc=enc, mapped=mapped)
+        out = self._pixel_decoder(pk, dec_in, B, saved=st_p).reshape(B, Q, D)     # :117-120
         if return_stages:
             stages["out"] = out
             return stages
-        return out
+        if mode == "feats":
+            return out
+        # the pixel head (SURVEY.md §8f row 2): `to_pixels` per query, 'n (h w) (p q c) -> n c (h p) (w q)' (ops.unpatchify)
+        patches = ops.linear(out.reshape(B * Q, D), *pk["pix"])
+        img = ops.unpatchify(patches, B, self.height, self.weight, self.patch_size)
+        if saved is not None:
+            saved.update(feats=out.reshape(B * Q, D), img=img, gold=gold)
+        if mode == "image":
+            return img
+        return ops.pixel_loss(img, gold, kind)
 
     # -- the pixel head (SURVEY.md §8f row 2: "define the missing return / pixel head explicitly") ------------------------------------------
     def decode_image(self, x, attention_masks: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens -> reconstructed image (B, 3, height * patch_size, weight * patch_size): forward(), then `to_pixels` per query and the
-        'n (h w) (p q c) -> n c (h p) (w q)' rearrangement (ops.unpatchify)."""
+        'n (h w) (p q c) -> n c (h p) (w q)' rearrangement (ops.unpatchify).  Differentiable as forward() is."""
         if self.to_pixels is None:
             raise RuntimeError("this SetokDeTokenizer was built without pixel_head=True: there is no `to_pixels` layer (the reference defines none)")
-        from . import autograd
-        feats = self.forward(x, attention_masks)                                    # (B, Q, D)
-        with torch.no_grad():
-            B, Q, D = feats.shape
-            pk = self._pack()
-            patches = ops.linear(feats.detach().reshape(B * Q, D), *pk["pix"])
-            img = ops.unpatchify(patches, B, self.height, self.weight, self.patch_size)
-        return autograd.no_backward("SetokDeTokenizer.decode_image", img, [feats, *self.to_pixels.parameters()])
+        return self._run(x, attention_masks, "image")
 
     def reconstruction_loss(self, x, gold_image: torch.Tensor, attention_masks: Optional[torch.Tensor] = None, kind: str = "mse") -> torch.Tensor:
         """The pixel term of the reference's reconstruction objective between decode_image(x) and `gold_image` (B, 3, H, W) as a 0-d fp32 tensor:
         "mse" = WeightedMSELoss without a mask (src/model/loss/mse.py:9-19), "l1" = the |input - reconstruction| mean of the GAN loss
-        (src/model/loss/discriminator.py:161,170).  LPIPS and the adversarial term are out of scope."""
-        img = self.decode_image(x, attention_masks)
-        if tuple(gold_image.shape) != tuple(img.shape):
-            raise ValueError(f"gold_image has shape {tuple(gold_image.shape)}, the decoder reconstructs {tuple(img.shape)}")
-        from . import autograd
-        with torch.no_grad():
-            loss = ops.pixel_loss(img.detach(), gold_image.to(device=img.device, dtype=img.dtype).contiguous(), kind)
-        return autograd.no_backward("SetokDeTokenizer.reconstruction_loss", loss, [img])
+        (src/model/loss/discriminator.py:161,170).  LPIPS and the adversarial term are out of scope.  Differentiable as forward() is, with the
+        loss's backward and the patch rearrangement in one kernel (ops.pixel_loss_bwd); `gold_image` itself gets no gradient."""
+        if self.to_pixels is None:
+            raise RuntimeError("this SetokDeTokenizer was built without pixel_head=True: there is no `to_pixels` layer (the reference defines none)")
+        if kind not in ("mse", "l1"):
+            raise ValueError(f"kind must be 'mse' or 'l1', got {kind!r}")
+        if torch.is_grad_enabled() and gold_image.requires_grad:
+            raise ValueError("reconstruction_loss: gold_image requires a gradient, but the target of the pixel loss gets none on this path; "
+                             "pass gold_image.detach()")
+        B = len(x) if isinstance(x, (list, tuple)) else (len(x.counts) if isinstance(x, RaggedTokens) else x.shape[0])
+        want = (B, 3, self.height * self.patch_size, self.weight * self.patch_size)
+        if tuple(gold_image.shape) != want:
+            raise ValueError(f"gold_image has shape {tuple(gold_image.shape)}, the decoder reconstructs {want}")
+        gold = gold_image.detach().to(device=self.device, dtype=self.dtype).contiguous()
+        return self._run(x, attention_masks, "loss", gold=gold, kind=kind)

@@ -484,6 +484,53 @@ def attention_bwd(qkv: Tensor, out: Tensor, dout: Tensor, H: int, Dh: int, scale
     return dqkv
 
 
+def mha_bwd(q: Tensor, k: Tensor, v: Tensor, out: Tensor, dout: Tensor, H: int, Dh: int, scale: float, q_len: int,
+            kv_offsets: Optional[Tensor], n_segs: int, max_kv: int, dq: Optional[Tensor] = None, dk: Optional[Tensor] = None,
+            dv: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Backward of cross_attention (self-attention: kv_offsets None, max_kv = q_len, q / k / v the column windows of one qkv buffer).
+    All operands are 2-D row views with unit column stride; dq, dk, dv may be given as views (the windows of one dqkv buffer, or the
+    [dk | dv] halves of one buffer), else fresh (rows, H*Dh) tensors are returned.  k / v and dk / dv share their row strides."""
+    C = H * Dh
+    for t in (q, k, v, out, dout):
+        assert t.dim() == 2 and t.shape[1] == C and t.stride(1) == 1 and t.is_cuda and t.dtype == q.dtype
+    assert k.stride(0) == v.stride(0) and q.shape[0] == n_segs * q_len and out.shape[0] == dout.shape[0] == q.shape[0] and k.shape[0] == v.shape[0]
+    if kv_offsets is not None:
+        assert kv_offsets.dtype == torch.int32 and kv_offsets.numel() >= n_segs + 1
+        if n_segs:                                                # every key row must get its dk / dv (one host read of the longest segment)
+            longest = int((kv_offsets[1:n_segs + 1] - kv_offsets[:n_segs]).max())
+            assert longest <= max_kv, f"a key / value segment has {longest} rows, more than max_kv = {max_kv}"
+    else:
+        assert k.shape[0] == n_segs * max_kv
+    if dq is None:
+        dq = torch.empty((q.shape[0], C), dtype=q.dtype, device=q.device)
+    if dk is None or dv is None:
+        dkv = torch.empty((k.shape[0], 2 * C), dtype=q.dtype, device=q.device)
+        dk, dv = dkv[:, :C], dkv[:, C:]
+    for t, like in ((dq, q), (dk, k), (dv, v)):
+        assert t.shape == like.shape and t.stride(1) == 1 and t.dtype == q.dtype
+    assert dk.stride(0) == dv.stride(0)
+    ws = _ws(q.device, 2 * q.shape[0] * H)
+    _lib.call("setok_mha_bwd", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0), _p(kv_offsets), n_segs,
+              q_len, max_kv, out.data_ptr(), out.stride(0), dout.data_ptr(), dout.stride(0), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dv.data_ptr(),
+              dk.stride(0), H, Dh, scale, _p(ws))
+    return dq, dk, dv
+
+
+def pixel_loss_bwd(pred: Tensor, gold: Optional[Tensor], kind: str, upstream: Tensor, n_pad: int, gh: int, gw: int, p: int) -> Tensor:
+    """d loss / d patch rows (B*gh*gw, n_pad) for loss = pixel_loss(unpatchify(patches), gold, kind), times the 0-d fp32 device tensor
+    `upstream`; pad columns are zero.  kind "unpatchify": the backward of unpatchify alone (`pred` is d loss / d image, `gold` unused)."""
+    code = {"mse": 0, "l1": 1, "unpatchify": 2}[kind]
+    B = pred.shape[0]
+    assert pred.dim() == 4 and tuple(pred.shape[1:]) == (3, gh * p, gw * p) and pred.is_contiguous()
+    if code != 2:
+        assert gold is not None and gold.shape == pred.shape and gold.dtype == pred.dtype and gold.is_contiguous()
+    up = upstream.detach().reshape(1).to(device=pred.device, dtype=torch.float32).contiguous()
+    out = torch.empty((B * gh * gw, n_pad), dtype=pred.dtype, device=pred.device)
+    _lib.call("setok_pixel_loss_bwd", _stream(), _code(pred.dtype), _p(pred), _p(gold) if code != 2 else None, code, _p(up), _p(out), n_pad,
+              B, gh, gw, p)
+    return out
+
+
 def segment_mean_bwd(dseg: Tensor, seg_offsets: Tensor, n_segs_dev: Tensor, n_segs: int, rows: int) -> Tensor:
     Cc = dseg.shape[-1]
     out = torch.empty((rows, Cc), dtype=dseg.dtype, device=dseg.device)
