@@ -10,149 +10,23 @@
 // The forward kernels are not changed, so nothing is saved from them: the log-sum-exp and delta_i = do_i . o_i are recomputed here.
 //   s_ij = scale q_i.k_j,  p_ij = exp(s_ij - lse_i),  ds_ij = p_ij (do_i.v_j - delta_i)
 //   dq_i = scale sum_j ds_ij k_j,  dk_j = scale sum_i ds_ij q_i,  dv_j = sum_i p_ij do_i
-// Kernel A: one wave per (query row, head): lse_i, delta_i (kept for kernel B in `ws`) and dq_i.
-// Kernel B: one wave per (key row, head): dk_j, dv_j by a loop over its segment's query rows in row order.
+// Head dims 48 and 64 in the 16-bit type run the MFMA kernels below.  Every other shape, fp32, and SETOK_ATTN_BWD_GENERIC=1 run the generic
+// wave-per-(row, head) pair that setok_attention_bwd uses too (norm_attn.hip, setok_attention_bwd_generic).  In both forms a query kernel
+// computes lse_i, delta_i (kept in `ws`) and dq_i, then a key kernel dk_j and dv_j by a loop over its segment's query rows in row order.
 // No atomics; every sum runs in a fixed order, so two runs give the same bits, and a segment's result does not depend on its neighbours.
 #include "common.h"
 
+int setok_attention_bwd_generic(const char* what, hipStream_t s, int dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                                const void* o, int64_t ldo, const void* dout, int64_t lddo, void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv,
+                                const int32_t* seg_offsets, int n_segs, int seg_len, int q_len, int rows, int H, int Dh, float scale,
+                                float* lse, float* dsum, int skip_long);                                     // norm_attn.hip
+
 namespace {
 
-constexpr int MB_MAXC = 2;                      // head dim up to 64 lanes * VEC * 2
-
+// the key rows [k0, k1) of group s (the rule of norm_attn.hip's attn_rows)
 __device__ inline void kv_range(const int32_t* kv_offsets, int s, int max_kv, int& k0, int& k1) {
     if (kv_offsets) { k0 = kv_offsets[s]; k1 = kv_offsets[s + 1]; if (k1 - k0 > max_kv) k1 = k0 + max_kv; }
     else { k0 = s * max_kv; k1 = k0 + max_kv; }
-}
-
-template <typename T>
-__device__ inline float wave_dot(const T* base, const float (&a)[MB_MAXC][Elem<T>::VEC], int lane, int nc, int Dh) {
-    constexpr int V = Elem<T>::VEC;
-    float acc = 0.f, buf[V];
-#pragma unroll
-    for (int c = 0; c < MB_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-        if (c < nc && d < Dh) {
-            ld_vec<T>(base + d, buf);
-#pragma unroll
-            for (int i = 0; i < V; ++i) acc = fmaf(a[c][i], buf[i], acc);
-        }
-    }
-    return wave_sum(acc);
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void mha_bwd_q_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, const T* __restrict__ v,
-                                                       int64_t ldkv, const int32_t* __restrict__ kv_offsets, int q_len, int max_kv,
-                                                       const T* __restrict__ o, int64_t ldo, const T* __restrict__ dout, int64_t lddo,
-                                                       T* __restrict__ dq, int64_t lddq, float* __restrict__ lse, float* __restrict__ dsum,
-                                                       int H, int Dh, float scale) {
-    constexpr int V = Elem<T>::VEC;
-    const int row = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
-    int k0, k1;
-    kv_range(kv_offsets, row / q_len, max_kv, k0, k1);
-    const int nc = (Dh + 64 * V - 1) / (64 * V);
-    const int64_t hc = (int64_t)h * Dh;
-    float qr[MB_MAXC][V], dq_[MB_MAXC][V], dO[MB_MAXC][V], buf[V];
-    float D = 0.f;
-#pragma unroll
-    for (int c = 0; c < MB_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-#pragma unroll
-        for (int i = 0; i < V; ++i) { qr[c][i] = 0.f; dq_[c][i] = 0.f; dO[c][i] = 0.f; }
-        if (c < nc && d < Dh) {
-            ld_vec<T>(q + (int64_t)row * ldq + hc + d, qr[c]);
-            ld_vec<T>(dout + (int64_t)row * lddo + hc + d, dO[c]);
-            ld_vec<T>(o + (int64_t)row * ldo + hc + d, buf);
-#pragma unroll
-            for (int i = 0; i < V; ++i) D += dO[c][i] * buf[i];
-        }
-    }
-    D = wave_sum(D);
-    float m = -INFINITY, l = 0.f;
-    for (int j = k0; j < k1; ++j) {
-        const float s = wave_dot<T>(k + (int64_t)j * ldkv + hc, qr, lane, nc, Dh) * scale;
-        const float mn = fmaxf(m, s);
-        l = l * expf(m - mn) + expf(s - mn);
-        m = mn;
-    }
-    const float L = m + logf(l);
-    for (int j = k0; j < k1; ++j) {
-        const T* kp = k + (int64_t)j * ldkv + hc;
-        const float p = expf(wave_dot<T>(kp, qr, lane, nc, Dh) * scale - L);
-        const float ds = p * (wave_dot<T>(v + (int64_t)j * ldkv + hc, dO, lane, nc, Dh) - D) * scale;
-#pragma unroll
-        for (int c = 0; c < MB_MAXC; ++c) {
-            const int d = (c * 64 + lane) * V;
-            if (c < nc && d < Dh) {
-                ld_vec<T>(kp + d, buf);
-#pragma unroll
-                for (int i = 0; i < V; ++i) dq_[c][i] = fmaf(ds, buf[i], dq_[c][i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < MB_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-        if (c < nc && d < Dh) st_vec<T>(dq + (int64_t)row * lddq + hc + d, dq_[c]);
-    }
-    if (lane == 0) { lse[(int64_t)row * H + h] = L; dsum[(int64_t)row * H + h] = D; }
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void mha_bwd_kv_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, const T* __restrict__ v,
-                                                        int64_t ldkv, const int32_t* __restrict__ kv_offsets, int q_len, int max_kv,
-                                                        const T* __restrict__ dout, int64_t lddo, T* __restrict__ dk, T* __restrict__ dv,
-                                                        int64_t lddkv, const float* __restrict__ lse, const float* __restrict__ dsum,
-                                                        int H, int Dh, float scale) {
-    constexpr int V = Elem<T>::VEC;
-    const int seg = blockIdx.x / max_kv, h = blockIdx.y, lane = threadIdx.x;
-    int k0, k1;
-    kv_range(kv_offsets, seg, max_kv, k0, k1);
-    const int j = k0 + (int)(blockIdx.x % max_kv);
-    if (j >= k1) return;
-    const int nc = (Dh + 64 * V - 1) / (64 * V);
-    const int64_t hc = (int64_t)h * Dh;
-    float kr[MB_MAXC][V], vr[MB_MAXC][V], dk_[MB_MAXC][V], dv_[MB_MAXC][V], qb[MB_MAXC][V], ob[MB_MAXC][V];
-#pragma unroll
-    for (int c = 0; c < MB_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-#pragma unroll
-        for (int i = 0; i < V; ++i) { kr[c][i] = 0.f; vr[c][i] = 0.f; dk_[c][i] = 0.f; dv_[c][i] = 0.f; qb[c][i] = 0.f; ob[c][i] = 0.f; }
-        if (c < nc && d < Dh) {
-            ld_vec<T>(k + (int64_t)j * ldkv + hc + d, kr[c]);
-            ld_vec<T>(v + (int64_t)j * ldkv + hc + d, vr[c]);
-        }
-    }
-    const int i0 = seg * q_len;
-    for (int i = i0; i < i0 + q_len; ++i) {
-        float a = 0.f, b = 0.f;
-#pragma unroll
-        for (int c = 0; c < MB_MAXC; ++c) {
-            const int d = (c * 64 + lane) * V;
-            if (c < nc && d < Dh) {
-                ld_vec<T>(q + (int64_t)i * ldq + hc + d, qb[c]);
-                ld_vec<T>(dout + (int64_t)i * lddo + hc + d, ob[c]);
-#pragma unroll
-                for (int e = 0; e < V; ++e) { a = fmaf(qb[c][e], kr[c][e], a); b = fmaf(ob[c][e], vr[c][e], b); }
-            }
-        }
-        const float s = wave_sum(a) * scale, dp = wave_sum(b);
-        const float p = expf(s - lse[(int64_t)i * H + h]);
-        const float ds = p * (dp - dsum[(int64_t)i * H + h]) * scale;
-#pragma unroll
-        for (int c = 0; c < MB_MAXC; ++c) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) { dk_[c][e] = fmaf(ds, qb[c][e], dk_[c][e]); dv_[c][e] = fmaf(p, ob[c][e], dv_[c][e]); }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < MB_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-        if (c < nc && d < Dh) {
-            st_vec<T>(dk + (int64_t)j * lddkv + hc + d, dk_[c]);
-            st_vec<T>(dv + (int64_t)j * lddkv + hc + d, dv_[c]);
-        }
-    }
 }
 
 // ---- d(pixel loss) / d(patch rows): the backward of setok_pixel_loss and setok_unpatchify in one pass ---------------------------------------
@@ -416,7 +290,7 @@ extern "C" int setok_mha_bwd(void* stream, int dtype, const void* q, int64_t ldq
                              int64_t lddo, void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv, int H, int Dh, float scale, float* ws) {
     SETOK_CHECK_ARG(q && k && v && out && dout && dq && dk && dv && ws, "setok_mha_bwd: null operand");
     const int V = dtype == SETOK_BF16 ? 8 : 4;
-    SETOK_CHECK_ARG(n_segs >= 0 && q_len > 0 && max_kv > 0 && H > 0 && Dh > 0 && Dh % 8 == 0 && Dh <= 64 * V * MB_MAXC,
+    SETOK_CHECK_ARG(n_segs >= 0 && q_len > 0 && max_kv > 0 && H > 0 && Dh > 0 && Dh % 8 == 0 && Dh <= 64 * V * AT_MAXC,
                     "setok_mha_bwd: bad shape n_segs=%d q_len=%d max_kv=%d H=%d Dh=%d", n_segs, q_len, max_kv, H, Dh);
     const int64_t C = (int64_t)H * Dh;
     SETOK_CHECK_ARG(ldq >= C && ldkv >= C && ldo >= C && lddo >= C && lddq >= C && lddkv >= C, "setok_mha_bwd: a row stride is below H*Dh");
@@ -438,18 +312,8 @@ extern "C" int setok_mha_bwd(void* stream, int dtype, const void* q, int64_t ldq
         SETOK_CHECK_LAUNCH("setok_mha_bwd");
         return SETOK_OK;
     }
-    const dim3 gq(rows, H), gkv(n_segs * max_kv, H);
-    DISPATCH_T("setok_mha_bwd",
-        (mha_bwd_q_kernel<bf16><<<gq, 64, 0, s>>>((const bf16*)q, ldq, (const bf16*)k, (const bf16*)v, ldkv, kv_offsets, q_len, max_kv,
-                                                  (const bf16*)out, ldo, (const bf16*)dout, lddo, (bf16*)dq, lddq, lse, dsum, H, Dh, scale),
-         mha_bwd_kv_kernel<bf16><<<gkv, 64, 0, s>>>((const bf16*)q, ldq, (const bf16*)k, (const bf16*)v, ldkv, kv_offsets, q_len, max_kv,
-                                                    (const bf16*)dout, lddo, (bf16*)dk, (bf16*)dv, lddkv, lse, dsum, H, Dh, scale)),
-        (mha_bwd_q_kernel<float><<<gq, 64, 0, s>>>((const float*)q, ldq, (const float*)k, (const float*)v, ldkv, kv_offsets, q_len, max_kv,
-                                                   (const float*)out, ldo, (const float*)dout, lddo, (float*)dq, lddq, lse, dsum, H, Dh, scale),
-         mha_bwd_kv_kernel<float><<<gkv, 64, 0, s>>>((const float*)q, ldq, (const float*)k, (const float*)v, ldkv, kv_offsets, q_len, max_kv,
-                                                     (const float*)dout, lddo, (float*)dk, (float*)dv, lddkv, lse, dsum, H, Dh, scale)));
-    SETOK_CHECK_LAUNCH("setok_mha_bwd");
-    return SETOK_OK;
+    return setok_attention_bwd_generic("setok_mha_bwd", s, dtype, q, ldq, k, v, ldkv, out, ldo, dout, lddo, dq, lddq, dk, dv, lddkv, kv_offsets,
+                                       n_segs, max_kv, q_len, rows, H, Dh, scale, lse, dsum, 0);
 }
 
 extern "C" int setok_pixel_loss_bwd(void* stream, int dtype, const void* pred, const void* gold, int kind, const float* upstream, void* dpatches,

@@ -246,152 +246,6 @@ __global__ void gelu_bwd_dropout_kernel(const T* __restrict__ pre, const T* dy, 
     }
 }
 
-// ---- varlen attention backward, generic (any head dim up to 64 * VEC * 2) ------------------------------------------------------------
-// Forward: s_ij = scale q_i.k_j, p_ij = softmax_j, o_i = sum_j p_ij v_j.  With D_i = do_i.o_i:
-//   ds_ij = p_ij (do_i.v_j - D_i),  dq_i = scale sum_j ds_ij k_j,  dk_j = scale sum_i ds_ij q_i,  dv_j = sum_i p_ij do_i.
-// Kernel A: one wave per (query row i, head): log-sum-exp and D_i (kept for kernel B) and dq_i.
-// Kernel B: one wave per (key row j, head): dk_j, dv_j by a loop over the segment's queries.  No atomics.
-constexpr int AT_MAXC = 2;
-template <typename T>
-__device__ inline void seg_of(const int32_t* seg_offsets, int n_segs, int seg_len, int rows, int row, int& s0, int& s1) {
-    if (seg_offsets) {
-        int lo = 0, hi = n_segs;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_offsets[mid] <= row) lo = mid; else hi = mid; }
-        s0 = seg_offsets[lo]; s1 = seg_offsets[lo + 1];
-    } else { s0 = (row / seg_len) * seg_len; s1 = min(s0 + seg_len, rows); }
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void attn_bwd_q_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ seg_offsets, int n_segs, int seg_len,
-                                                        const T* __restrict__ o, const T* __restrict__ dout, T* __restrict__ dqkv,
-                                                        float* __restrict__ lse, float* __restrict__ dsum, int rows, int H, int Dh, float scale,
-                                                        int skip_long) {
-    constexpr int V = Elem<T>::VEC;
-    const int row = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
-    int s0, s1;
-    seg_of<T>(seg_offsets, n_segs, seg_len, rows, row, s0, s1);
-    if (row < s0 || row >= s1) return;
-    if (skip_long && s1 - s0 > 32) return;                              // the segment-owning MFMA kernels' share (attn_seg_bwd.hip)
-    const int64_t C = (int64_t)H * Dh, ld = 3 * C;
-    const int nc = (Dh + 64 * V - 1) / (64 * V);
-    float q[AT_MAXC][V], dq[AT_MAXC][V], dO[AT_MAXC][V], buf[V];
-    float D = 0.f;
-#pragma unroll
-    for (int c = 0; c < AT_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-#pragma unroll
-        for (int i = 0; i < V; ++i) { q[c][i] = 0.f; dq[c][i] = 0.f; dO[c][i] = 0.f; }
-        if (c < nc && d < Dh) {
-            ld_vec<T>(qkv + (int64_t)row * ld + h * Dh + d, q[c]);
-            ld_vec<T>(dout + (int64_t)row * C + h * Dh + d, dO[c]);
-            ld_vec<T>(o + (int64_t)row * C + h * Dh + d, buf);
-#pragma unroll
-            for (int i = 0; i < V; ++i) D += dO[c][i] * buf[i];
-        }
-    }
-    D = wave_sum(D);
-    auto dot_k = [&](const T* base, const float (&a)[AT_MAXC][V]) {
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < AT_MAXC; ++c) {
-            const int d = (c * 64 + lane) * V;
-            if (c < nc && d < Dh) {
-                ld_vec<T>(base + d, buf);
-#pragma unroll
-                for (int i = 0; i < V; ++i) acc = fmaf(a[c][i], buf[i], acc);
-            }
-        }
-        return wave_sum(acc);
-    };
-    float m = -INFINITY, l = 0.f;
-    for (int j = s0; j < s1; ++j) {
-        const float s = dot_k(qkv + (int64_t)j * ld + C + h * Dh, q) * scale;
-        const float mn = fmaxf(m, s);
-        l = l * expf(m - mn) + expf(s - mn);
-        m = mn;
-    }
-    const float L = m + logf(l);
-    for (int j = s0; j < s1; ++j) {
-        const T* kp = qkv + (int64_t)j * ld + C + h * Dh;
-        const float s = dot_k(kp, q) * scale;
-        const float p = expf(s - L);
-        const float dp = dot_k(qkv + (int64_t)j * ld + 2 * C + h * Dh, dO);
-        const float ds = p * (dp - D) * scale;
-#pragma unroll
-        for (int c = 0; c < AT_MAXC; ++c) {
-            const int d = (c * 64 + lane) * V;
-            if (c < nc && d < Dh) {
-                ld_vec<T>(kp + d, buf);
-#pragma unroll
-                for (int i = 0; i < V; ++i) dq[c][i] = fmaf(ds, buf[i], dq[c][i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < AT_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-        if (c < nc && d < Dh) st_vec<T>(dqkv + (int64_t)row * ld + h * Dh + d, dq[c]);
-    }
-    if (lane == 0) { lse[(int64_t)row * H + h] = L; dsum[(int64_t)row * H + h] = D; }
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void attn_bwd_kv_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ seg_offsets, int n_segs, int seg_len,
-                                                         const T* __restrict__ dout, T* __restrict__ dqkv, const float* __restrict__ lse,
-                                                         const float* __restrict__ dsum, int rows, int H, int Dh, float scale, int skip_long) {
-    constexpr int V = Elem<T>::VEC;
-    const int row = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
-    int s0, s1;
-    seg_of<T>(seg_offsets, n_segs, seg_len, rows, row, s0, s1);
-    if (row < s0 || row >= s1) return;
-    if (skip_long && s1 - s0 > 32) return;
-    const int64_t C = (int64_t)H * Dh, ld = 3 * C;
-    const int nc = (Dh + 64 * V - 1) / (64 * V);
-    float k[AT_MAXC][V], v[AT_MAXC][V], dk[AT_MAXC][V], dv[AT_MAXC][V], qb[AT_MAXC][V], ob[AT_MAXC][V];
-#pragma unroll
-    for (int c = 0; c < AT_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-#pragma unroll
-        for (int i = 0; i < V; ++i) { k[c][i] = 0.f; v[c][i] = 0.f; dk[c][i] = 0.f; dv[c][i] = 0.f; }
-        if (c < nc && d < Dh) {
-            ld_vec<T>(qkv + (int64_t)row * ld + C + h * Dh + d, k[c]);
-            ld_vec<T>(qkv + (int64_t)row * ld + 2 * C + h * Dh + d, v[c]);
-        }
-    }
-    for (int i = s0; i < s1; ++i) {
-        float a = 0.f, b = 0.f;
-#pragma unroll
-        for (int c = 0; c < AT_MAXC; ++c) {
-            const int d = (c * 64 + lane) * V;
-            if (c < nc && d < Dh) {
-                ld_vec<T>(qkv + (int64_t)i * ld + h * Dh + d, qb[c]);
-                ld_vec<T>(dout + (int64_t)i * C + h * Dh + d, ob[c]);
-#pragma unroll
-                for (int e = 0; e < V; ++e) { a = fmaf(qb[c][e], k[c][e], a); b = fmaf(ob[c][e], v[c][e], b); }
-            }
-        }
-        const float s = wave_sum(a) * scale, dp = wave_sum(b);
-        const float p = expf(s - lse[(int64_t)i * H + h]);
-        const float ds = p * (dp - dsum[(int64_t)i * H + h]) * scale;
-#pragma unroll
-        for (int c = 0; c < AT_MAXC; ++c) {
-            const int d = (c * 64 + lane) * V;
-            if (c < nc && d < Dh) {
-#pragma unroll
-                for (int e = 0; e < V; ++e) { dk[c][e] = fmaf(ds, qb[c][e], dk[c][e]); dv[c][e] = fmaf(p, ob[c][e], dv[c][e]); }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < AT_MAXC; ++c) {
-        const int d = (c * 64 + lane) * V;
-        if (c < nc && d < Dh) {
-            st_vec<T>(dqkv + (int64_t)row * ld + C + h * Dh + d, dk[c]);
-            st_vec<T>(dqkv + (int64_t)row * ld + 2 * C + h * Dh + d, dv[c]);
-        }
-    }
-}
-
 // ---- d(mean over a segment): every member row gets d_seg / n -------------------------------------------------------------------------
 template <typename T>
 __global__ void segment_mean_bwd_kernel(const T* __restrict__ dseg, const int32_t* __restrict__ off, const int32_t* __restrict__ n_segs,
@@ -430,6 +284,10 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 
 int setok_attention_bwd_seg_bf16(hipStream_t s, const bf16* qkv, const int32_t* seg_offsets, int n_segs, const bf16* out, const bf16* dout,
                                  bf16* dqkv, float* lse_ws, float* d_ws, int H, int Dh, float scale);       // attn_seg_bwd.hip
+int setok_attention_bwd_generic(const char* what, hipStream_t s, int dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                                const void* o, int64_t ldo, const void* dout, int64_t lddo, void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv,
+                                const int32_t* seg_offsets, int n_segs, int seg_len, int q_len, int rows, int H, int Dh, float scale,
+                                float* lse, float* dsum, int skip_long);                                     // norm_attn.hip
 
 
 extern "C" int setok_transpose(void* stream, int dtype, const void* x, int64_t ldx, int rows, int cols, void* out, int64_t ldo, int chunk,
@@ -528,14 +386,12 @@ extern "C" int setok_attention_bwd(void* stream, int dtype, const void* qkv, con
                                                     H, Dh, scale);
         if (rc == SETOK_OK) skip_long = 1; else if (rc != SETOK_EUNSUPPORTED) return rc;
     }
-    dim3 grid(rows, H);
-    DISPATCH_T("setok_attention_bwd",
-               (attn_bwd_q_kernel<bf16><<<grid, 64, 0, s>>>((const bf16*)qkv, seg_offsets, n_segs, seg_len, (const bf16*)out, (const bf16*)dout, (bf16*)dqkv, lse, dsum, rows, H, Dh, scale, skip_long),
-                attn_bwd_kv_kernel<bf16><<<grid, 64, 0, s>>>((const bf16*)qkv, seg_offsets, n_segs, seg_len, (const bf16*)dout, (bf16*)dqkv, lse, dsum, rows, H, Dh, scale, skip_long)),
-               (attn_bwd_q_kernel<float><<<grid, 64, 0, s>>>((const float*)qkv, seg_offsets, n_segs, seg_len, (const float*)out, (const float*)dout, (float*)dqkv, lse, dsum, rows, H, Dh, scale, 0),
-                attn_bwd_kv_kernel<float><<<grid, 64, 0, s>>>((const float*)qkv, seg_offsets, n_segs, seg_len, (const float*)dout, (float*)dqkv, lse, dsum, rows, H, Dh, scale, 0)));
-    SETOK_CHECK_LAUNCH("setok_attention_bwd");
-    return SETOK_OK;
+    const int64_t C = (int64_t)H * Dh;
+    const int64_t w = C * (dtype == SETOK_F32 ? 4 : 2);                         // bytes of one of the q | k | v windows of a qkv row
+    const char* p = (const char*)qkv;
+    char* d = (char*)dqkv;
+    return setok_attention_bwd_generic("setok_attention_bwd", s, dtype, p, 3 * C, p + w, p + 2 * w, 3 * C, out, C, dout, C, d, 3 * C, d + w, d + 2 * w,
+                                       3 * C, seg_offsets, n_segs, seg_len, 0, rows, H, Dh, scale, lse, dsum, skip_long);
 }
 
 extern "C" int setok_segment_mean_bwd(void* stream, int dtype, const void* dseg, const int32_t* seg_offsets, const int32_t* n_segs_dev, int max_segs,

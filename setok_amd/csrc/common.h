@@ -133,6 +133,9 @@ template <> struct Elem<bf16> {
     __device__ static inline void st(bf16* p, float v) { *p = (bf16)v; }
 };
 
+// The generic attention backward (norm_attn.hip) keeps a lane's share of a head row in AT_MAXC 16-byte pieces: head dim <= 64 * VEC * AT_MAXC.
+constexpr int AT_MAXC = 2;
+
 // 16-byte vector load/store of VEC elements as floats
 template <typename T> __device__ inline void ld_vec(const T* p, float* out);
 template <> __device__ inline void ld_vec<float>(const float* p, float* out) {

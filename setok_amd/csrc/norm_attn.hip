@@ -275,10 +275,41 @@ extern "C" int setok_ln_fold(void* stream, const void* W, const float* gamma, co
 }
 
 // --------------------------------------------------------------------------------------------
-// Generic varlen attention: one wave per (query row, head).  Exact-softmax (max-subtracted, fp32).
+// Generic varlen attention, forward and backward: one wave per (row, head).  Exact-softmax (max-subtracted, fp32).
 // This is the any-shape / parity-mode path (fp32, head dim 512 of the cluster encoders, ragged
-// segments); the bf16 ViT shape has its own MFMA kernel in attn_vit.hip.
+// segments, the decoder's head dims without an MFMA backward); the bf16 ViT shape has its own MFMA
+// kernel in attn_vit.hip.
 // --------------------------------------------------------------------------------------------
+// Which rows meet, for the forward and both backward kernels alike:
+//   q_len == 0: self-attention over `rows` rows in segments, ragged (seg_offsets[0 .. n_segs]) or uniform (seg_len rows each, the last one cut
+//               at `rows`).  Work item x is row x; its segment holds its keys and, for a key row, its queries.
+//   q_len > 0:  n_segs groups of q_len query rows; group s attends to the key rows [seg_offsets[s], seg_offsets[s + 1]), cut to seg_len (host
+//               contract: seg_len bounds every segment), or [s seg_len, (s + 1) seg_len).  Work item x is query row x, or (key_side) key
+//               x % seg_len of group x / seg_len, whose queries are the group's rows.
+// Returns the row of work item x and the rows [r0, r1) on the other side, or -1 when x is no row: past the last ragged segment, or past the
+// keys of its group.
+__device__ inline int attn_rows(const int32_t* seg_offsets, int n_segs, int seg_len, int q_len, int rows, int x, bool key_side, int& r0, int& r1) {
+    if (q_len == 0) {
+        if (seg_offsets) {
+            int lo = 0, hi = n_segs;                                // find s with off[s] <= x < off[s+1]
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_offsets[mid] <= x) lo = mid; else hi = mid; }
+            r0 = seg_offsets[lo]; r1 = seg_offsets[lo + 1];
+            if (x >= r1 || x < r0) return -1;
+        } else {
+            r0 = (x / seg_len) * seg_len; r1 = min(r0 + seg_len, rows);
+        }
+        return x;
+    }
+    const int s = x / (key_side ? seg_len : q_len);
+    int k0, k1;
+    if (seg_offsets) { k0 = seg_offsets[s]; k1 = seg_offsets[s + 1]; if (k1 - k0 > seg_len) k1 = k0 + seg_len; }
+    else { k0 = s * seg_len; k1 = k0 + seg_len; }
+    if (!key_side) { r0 = k0; r1 = k1; return x; }
+    r0 = s * q_len; r1 = r0 + q_len;
+    const int j = k0 + x % seg_len;
+    return j < k1 ? j : -1;
+}
+
 template <typename T>
 __global__ __launch_bounds__(64) void attn_generic_kernel(const T* __restrict__ qbase, int64_t ldq, const T* __restrict__ kbase,
                                                           const T* __restrict__ vbase, int64_t ld,
@@ -289,21 +320,10 @@ __global__ __launch_bounds__(64) void attn_generic_kernel(const T* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* qs = sm;                 // Dh
     float* ps = sm + Dh;            // seg_len (upper bound on the segment length)
-    const int row = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+    const int h = blockIdx.y, lane = threadIdx.x;
     int s0, s1;
-    if (q_len > 0) {                                                // cross-attention: query row -> its segment's key rows
-        const int seg = row / q_len;
-        if (seg_offsets) { s0 = seg_offsets[seg]; s1 = seg_offsets[seg + 1]; }
-        else { s0 = seg * seg_len; s1 = s0 + seg_len; }
-        if (s1 - s0 > seg_len) s1 = s0 + seg_len;                   // host contract: seg_len bounds every segment
-    } else if (seg_offsets) {
-        int lo = 0, hi = n_segs;                                    // find s with off[s] <= row < off[s+1]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_offsets[mid] <= row) lo = mid; else hi = mid; }
-        s0 = seg_offsets[lo]; s1 = seg_offsets[lo + 1];
-        if (row >= s1 || row < s0) return;                          // row beyond the last segment
-    } else {
-        s0 = (row / seg_len) * seg_len; s1 = min(s0 + seg_len, rows);
-    }
+    const int row = attn_rows(seg_offsets, n_segs, seg_len, q_len, rows, blockIdx.x, false, s0, s1);
+    if (row < 0) return;
     const int n = s1 - s0;
     const T* qp = qbase + (int64_t)row * ldq + h * Dh;
     const T* kh = kbase + h * Dh;
@@ -393,6 +413,163 @@ __global__ __launch_bounds__(64) void attn_generic_kernel(const T* __restrict__ 
         for (int i = 0; i < V; ++i) o[i] *= inv;
         st_vec<T>(orow + d, o);
     }
+}
+
+// Backward (head dim up to 64 lanes * VEC * AT_MAXC).  With s_ij = scale q_i.k_j, p_ij = softmax_j, o_i = sum_j p_ij v_j, D_i = do_i.o_i:
+//   ds_ij = p_ij (do_i.v_j - D_i),  dq_i = scale sum_j ds_ij k_j,  dk_j = scale sum_i ds_ij q_i,  dv_j = sum_i p_ij do_i.
+// Nothing is saved from the forward: the query kernel recomputes lse_i (online) and D_i and keeps them in lse / dsum for the key kernel.
+// No atomics; every sum runs in a fixed order, so two runs give the same bits, and a segment's result does not depend on its neighbours.
+template <typename T>
+__device__ inline float wave_dot(const T* base, const float (&a)[AT_MAXC][Elem<T>::VEC], int lane, int nc, int Dh) {
+    constexpr int V = Elem<T>::VEC;
+    float acc = 0.f, buf[V];
+#pragma unroll
+    for (int c = 0; c < AT_MAXC; ++c) {
+        const int d = (c * 64 + lane) * V;
+        if (c < nc && d < Dh) {
+            ld_vec<T>(base + d, buf);
+#pragma unroll
+            for (int i = 0; i < V; ++i) acc = fmaf(a[c][i], buf[i], acc);
+        }
+    }
+    return wave_sum(acc);
+}
+
+// one wave per (query row, head): lse_i, D_i and dq_i.  skip_long: segments of more than 32 rows are left to the MFMA kernels (attn_seg_bwd.hip).
+template <typename T>
+__global__ __launch_bounds__(64) void attn_bwd_q_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, const T* __restrict__ v,
+                                                        int64_t ldkv, const T* __restrict__ o, int64_t ldo, const T* __restrict__ dout, int64_t lddo,
+                                                        T* __restrict__ dq, int64_t lddq, const int32_t* __restrict__ seg_offsets, int n_segs,
+                                                        int seg_len, int q_len, int rows, int H, int Dh, float scale, float* __restrict__ lse,
+                                                        float* __restrict__ dsum, int skip_long) {
+    constexpr int V = Elem<T>::VEC;
+    const int h = blockIdx.y, lane = threadIdx.x;
+    int k0, k1;
+    const int row = attn_rows(seg_offsets, n_segs, seg_len, q_len, rows, blockIdx.x, false, k0, k1);
+    if (row < 0 || (skip_long && k1 - k0 > 32)) return;
+    const int nc = (Dh + 64 * V - 1) / (64 * V);
+    const int64_t hc = (int64_t)h * Dh;
+    float qr[AT_MAXC][V], dqr[AT_MAXC][V], dO[AT_MAXC][V], buf[V];
+    float D = 0.f;
+#pragma unroll
+    for (int c = 0; c < AT_MAXC; ++c) {
+        const int d = (c * 64 + lane) * V;
+#pragma unroll
+        for (int i = 0; i < V; ++i) { qr[c][i] = 0.f; dqr[c][i] = 0.f; dO[c][i] = 0.f; }
+        if (c < nc && d < Dh) {
+            ld_vec<T>(q + (int64_t)row * ldq + hc + d, qr[c]);
+            ld_vec<T>(dout + (int64_t)row * lddo + hc + d, dO[c]);
+            ld_vec<T>(o + (int64_t)row * ldo + hc + d, buf);
+#pragma unroll
+            for (int i = 0; i < V; ++i) D += dO[c][i] * buf[i];
+        }
+    }
+    D = wave_sum(D);
+    float m = -INFINITY, l = 0.f;
+    for (int j = k0; j < k1; ++j) {
+        const float s = wave_dot<T>(k + (int64_t)j * ldkv + hc, qr, lane, nc, Dh) * scale;
+        const float mn = fmaxf(m, s);
+        l = l * expf(m - mn) + expf(s - mn);
+        m = mn;
+    }
+    const float L = m + logf(l);
+    for (int j = k0; j < k1; ++j) {
+        const T* kp = k + (int64_t)j * ldkv + hc;
+        const float p = expf(wave_dot<T>(kp, qr, lane, nc, Dh) * scale - L);
+        const float ds = p * (wave_dot<T>(v + (int64_t)j * ldkv + hc, dO, lane, nc, Dh) - D) * scale;
+#pragma unroll
+        for (int c = 0; c < AT_MAXC; ++c) {
+            const int d = (c * 64 + lane) * V;
+            if (c < nc && d < Dh) {
+                ld_vec<T>(kp + d, buf);
+#pragma unroll
+                for (int i = 0; i < V; ++i) dqr[c][i] = fmaf(ds, buf[i], dqr[c][i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < AT_MAXC; ++c) {
+        const int d = (c * 64 + lane) * V;
+        if (c < nc && d < Dh) st_vec<T>(dq + (int64_t)row * lddq + hc + d, dqr[c]);
+    }
+    if (lane == 0) { lse[(int64_t)row * H + h] = L; dsum[(int64_t)row * H + h] = D; }
+}
+
+// one wave per (key row, head): dk_j, dv_j by a loop over its queries in row order
+template <typename T>
+__global__ __launch_bounds__(64) void attn_bwd_kv_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, const T* __restrict__ v,
+                                                         int64_t ldkv, const T* __restrict__ dout, int64_t lddo, T* __restrict__ dk, T* __restrict__ dv,
+                                                         int64_t lddkv, const int32_t* __restrict__ seg_offsets, int n_segs, int seg_len, int q_len,
+                                                         int rows, int H, int Dh, float scale, const float* __restrict__ lse,
+                                                         const float* __restrict__ dsum, int skip_long) {
+    constexpr int V = Elem<T>::VEC;
+    const int h = blockIdx.y, lane = threadIdx.x;
+    int i0, i1;
+    const int j = attn_rows(seg_offsets, n_segs, seg_len, q_len, rows, blockIdx.x, true, i0, i1);
+    if (j < 0 || (skip_long && i1 - i0 > 32)) return;
+    const int nc = (Dh + 64 * V - 1) / (64 * V);
+    const int64_t hc = (int64_t)h * Dh;
+    float kr[AT_MAXC][V], vr[AT_MAXC][V], dkr[AT_MAXC][V], dvr[AT_MAXC][V], qb[AT_MAXC][V], ob[AT_MAXC][V];
+#pragma unroll
+    for (int c = 0; c < AT_MAXC; ++c) {
+        const int d = (c * 64 + lane) * V;
+#pragma unroll
+        for (int i = 0; i < V; ++i) { kr[c][i] = 0.f; vr[c][i] = 0.f; dkr[c][i] = 0.f; dvr[c][i] = 0.f; qb[c][i] = 0.f; ob[c][i] = 0.f; }
+        if (c < nc && d < Dh) {
+            ld_vec<T>(k + (int64_t)j * ldkv + hc + d, kr[c]);
+            ld_vec<T>(v + (int64_t)j * ldkv + hc + d, vr[c]);
+        }
+    }
+    for (int i = i0; i < i1; ++i) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int c = 0; c < AT_MAXC; ++c) {
+            const int d = (c * 64 + lane) * V;
+            if (c < nc && d < Dh) {
+                ld_vec<T>(q + (int64_t)i * ldq + hc + d, qb[c]);
+                ld_vec<T>(dout + (int64_t)i * lddo + hc + d, ob[c]);
+#pragma unroll
+                for (int e = 0; e < V; ++e) { a = fmaf(qb[c][e], kr[c][e], a); b = fmaf(ob[c][e], vr[c][e], b); }
+            }
+        }
+        const float s = wave_sum(a) * scale, dp = wave_sum(b);
+        const float p = expf(s - lse[(int64_t)i * H + h]);
+        const float ds = p * (dp - dsum[(int64_t)i * H + h]) * scale;
+#pragma unroll
+        for (int c = 0; c < AT_MAXC; ++c) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) { dkr[c][e] = fmaf(ds, qb[c][e], dkr[c][e]); dvr[c][e] = fmaf(p, ob[c][e], dvr[c][e]); }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < AT_MAXC; ++c) {
+        const int d = (c * 64 + lane) * V;
+        if (c < nc && d < Dh) {
+            st_vec<T>(dk + (int64_t)j * lddkv + hc + d, dkr[c]);
+            st_vec<T>(dv + (int64_t)j * lddkv + hc + d, dvr[c]);
+        }
+    }
+}
+
+// The generic branch of setok_attention_bwd (q_len = 0; packed qkv as three column windows of stride 3 H Dh) and of setok_mha_bwd (q_len > 0).
+// The caller has checked the arguments; `what` names it in the errors.  lse / dsum: one float per (query row, head) each.
+int setok_attention_bwd_generic(const char* what, hipStream_t s, int dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                                const void* o, int64_t ldo, const void* dout, int64_t lddo, void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv,
+                                const int32_t* seg_offsets, int n_segs, int seg_len, int q_len, int rows, int H, int Dh, float scale,
+                                float* lse, float* dsum, int skip_long) {
+    const dim3 gq(rows, H), gkv(q_len > 0 ? n_segs * seg_len : rows, H);
+    auto launch = [&](auto elem) {
+        using T = decltype(elem);
+        attn_bwd_q_kernel<T><<<gq, 64, 0, s>>>((const T*)q, ldq, (const T*)k, (const T*)v, ldkv, (const T*)o, ldo, (const T*)dout, lddo, (T*)dq, lddq,
+                                               seg_offsets, n_segs, seg_len, q_len, rows, H, Dh, scale, lse, dsum, skip_long);
+        attn_bwd_kv_kernel<T><<<gkv, 64, 0, s>>>((const T*)q, ldq, (const T*)k, (const T*)v, ldkv, (const T*)dout, lddo, (T*)dk, (T*)dv, lddkv,
+                                                 seg_offsets, n_segs, seg_len, q_len, rows, H, Dh, scale, lse, dsum, skip_long);
+    };
+    if (dtype == SETOK_BF16) launch(bf16{});
+    else if (dtype == SETOK_F32) launch(float{});
+    else return setok_fail(SETOK_EINVAL, "%s: bad dtype %d", what, dtype);
+    SETOK_CHECK_LAUNCH(what);
+    return SETOK_OK;
 }
 
 int setok_attention_vit_bf16(hipStream_t s, const bf16* qkv, bf16* out, int n_imgs, int T, int H, int Dh, float scale);  // attn_vit.hip
