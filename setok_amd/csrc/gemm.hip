@@ -9,7 +9,7 @@
 //    staging, LDS double-buffered, one barrier per K tile.  LDS rows are 128 B with a 16-B-slot XOR
 //    swizzle (slot ^= row & 7) so a ds_read_b128 lane group is <= 2-way conflicted
 //    (cdna_hip_programming.md T2).
-//  * the big bf16 Linear layers (>= 48 output tiles of 256x256) go to the persistent direct-to-LDS kernel
+//  * the big bf16 Linear layers (>= 90 output tiles of 256x256) go to the persistent direct-to-LDS kernel
 //    in gemm_persist.hip, every smaller bf16 -> bf16 problem with N % 64 == 0 to that file's 64x64 eight-stage
 //    LDS-DMA kernel (a handful of images is latency-bound: 257 x 3072 x 1024 takes 9 us there against 36 us
 //    here; one-image encode 9.0 -> 3.8 ms); the kernel below serves fp32 outputs (Gram matrix), batches and
@@ -19,7 +19,6 @@
 //  * fp32 kernel  (parity mode): 64x64x16 block tile, 4 waves, v_mfma_f32_32x32x2_f32 — bit-for-bit a
 //    k-ordered fmaf chain, so results do not depend on tile geometry.
 #include "common.h"
-#include <stdlib.h>
 
 struct GemmArgs {
     const void* A; const void* W; const float* bias; const void* res; void* C;
@@ -235,7 +234,24 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
 }
 
 // --------------------------------------------------------------------------------------------
-static bool g_force_small_tiles = false;   // test hook: SETOK_GEMM_SMALL_TILES=1 keeps every bf16 GEMM on the 128x128 kernel
+// bf16 problems from this many output tiles of 256 x 256 on go to the persistent kernel.  Measured crossover against the small-tile kernel: 60 and 80
+// tiles are faster there, 96 on the persistent one (round 4: 48 -> 90, the pair-wise small-tile kernel moved it: profiles/r04_mintiles.log).
+constexpr int PERSIST_MIN_TILES = 90;
+
+enum class Bf16Kernel { Persist, Small, PersistF32Batched, Tile128 };
+
+// The kernel a bf16-input problem goes to.  setok_linear_dev and setok_linear_ln both dispatch through this one function: that is what keeps a row's
+// bits independent of the batch it is computed in (see the top of this file).
+static Bf16Kernel bf16_kernel(const GemmArgs& g, int out_dtype, int batch) {
+    const int tiles256 = cdiv(g.M, 256) * cdiv(g.N, 256);
+    if (out_dtype == SETOK_BF16 && batch == 1 && g.N % 64 == 0 && g.ldc % 8 == 0)
+        return g.K >= 192 && tiles256 >= PERSIST_MIN_TILES ? Bf16Kernel::Persist : Bf16Kernel::Small;
+    // fp32-out batched problems without bias / activation / residual and with enough tiles (weight-gradient partial products)
+    if (!g.m_dev && out_dtype == SETOK_F32 && !g.bias && !g.res && g.act == SETOK_ACT_NONE && g.N % 64 == 0 && g.K >= 192 && g.ldc % 4 == 0 &&
+        g.sA % 8 == 0 && g.sW % 8 == 0 && g.sC % 4 == 0 && tiles256 * batch >= 96)
+        return Bf16Kernel::PersistF32Batched;
+    return Bf16Kernel::Tile128;
+}
 
 // setok_linear with an optional DEVICE-side row count `m_dev` (one int32, <= M): the launch is sized for M rows, tiles beyond *m_dev exit at once
 // and no row beyond it is read or written — how setok_encode runs its ragged stages (the rows of all images' cluster tokens) without the host
@@ -252,15 +268,9 @@ int setok_linear_dev(void* stream, int dtype, int out_dtype, const void* A, int6
     GemmArgs g{A, W, bias, residual, C, lda, ldc, strideA, strideW, strideC, M, N, K, act, m_dev};
     hipStream_t s = (hipStream_t)stream;
     const double es_in = dtype == SETOK_BF16 ? 2.0 : 4.0, es_out = out_dtype == SETOK_BF16 ? 2.0 : 4.0;
-    {
-        static const bool env_small = [] { const char* e = getenv("SETOK_GEMM_SMALL_TILES"); return e && e[0] == '1'; }();
-        g_force_small_tiles = env_small;
-    }
-    static const int persist_min = [] { const char* e = getenv("SETOK_GEMM_PERSIST_MINTILES"); return e ? atoi(e) : 90; }();   // test hook; round 4: 48 -> 90 (the pair-wise small-tile kernel moved the crossover: profiles/r04_mintiles.log)
-    static const int small_max = [] { const char* e = getenv("SETOK_GEMM_SMALL64_MAXTILES"); return e ? atoi(e) : 0x7fffffff; }();
-    // the launches of gemm_persist.hip (every bf16 -> bf16 problem with aligned rows, unless a test hook says otherwise) carry the profiler's timestamps themselves
-    const bool lds_dma_path = dtype == SETOK_BF16 && out_dtype == SETOK_BF16 && batch == 1 && K % BK == 0 && lda % 8 == 0 && N % 64 == 0 && ldc % 8 == 0 && !g_force_small_tiles &&
-                              ((K >= 192 && cdiv(M, 256) * cdiv(N, 256) >= persist_min) || cdiv(M, BM) * cdiv(N, BN) <= small_max);
+    const Bf16Kernel kern = bf16_kernel(g, out_dtype, batch);
+    // the launches of gemm_persist.hip's bf16 -> bf16 kernels carry the profiler's timestamps themselves
+    const bool lds_dma_path = dtype == SETOK_BF16 && (kern == Bf16Kernel::Persist || kern == Bf16Kernel::Small);
     SetokProfScope prof(s, dtype == SETOK_BF16 ? SETOK_PROF_GEMM_BF16 : SETOK_PROF_GEMM_F32, act | (residual ? 4 : 0), 2.0 * M * N * K * batch,
                         batch * (((double)M * K + (double)N * K) * es_in + (double)M * N * es_out * (residual ? 2 : 1)),   // A, W (+ residual) read once, C written once
                         lds_dma_path);
@@ -268,18 +278,15 @@ int setok_linear_dev(void* stream, int dtype, int out_dtype, const void* A, int6
     if (dtype == SETOK_BF16) {
         SETOK_CHECK_ARG(K % BK == 0, "setok_linear(bf16): K=%d must be a multiple of %d", K, BK);
         SETOK_CHECK_ARG(lda % 8 == 0, "setok_linear(bf16): lda must be a multiple of 8");
-        // big problems (>= 90 tiles of 256x256; measured crossover against the 64x64 kernel: 60 and 80 tiles are faster there, 96 here): persistent direct-to-LDS kernel (gemm_persist.hip)
-        if (out_dtype == SETOK_BF16 && batch == 1 && N % 64 == 0 && K >= 192 && ldc % 8 == 0 && cdiv(M, 256) * cdiv(N, 256) >= persist_min && !g_force_small_tiles)
-            return setok_gemm_persist_bf16(s, (const bf16*)A, lda, (const bf16*)W, bias, (const bf16*)residual, (bf16*)C, ldc, M, N, K, act, nullptr, nullptr, m_dev);
-        // fp32-out batched problems without bias / activation / residual and with enough tiles (weight-gradient partial products)
-        if (!m_dev && out_dtype == SETOK_F32 && !bias && !residual && act == SETOK_ACT_NONE && N % 64 == 0 && K >= 192 && ldc % 4 == 0 &&
-            strideA % 8 == 0 && strideW % 8 == 0 && strideC % 4 == 0 && cdiv(M, 256) * cdiv(N, 256) * batch >= 96 && !g_force_small_tiles)
-            return setok_gemm_persist_f32_batched(s, (const bf16*)A, lda, (const bf16*)W, (float*)C, ldc, M, N, K, batch, strideA, strideW, strideC);
-        // every other bf16 -> bf16 problem with N % 64 == 0: 64 x 64 tiles, eight-stage LDS-DMA pipeline (gemm_persist.hip).
-        // SETOK_GEMM_SMALL64_MAXTILES=<n> (test hook) limits it to problems of at most n 128 x 128 tiles.
-        {
-            if (out_dtype == SETOK_BF16 && batch == 1 && N % 64 == 0 && ldc % 8 == 0 && cdiv(M, BM) * cdiv(N, BN) <= small_max && !g_force_small_tiles)
+        switch (kern) {
+            case Bf16Kernel::Persist:
+                return setok_gemm_persist_bf16(s, (const bf16*)A, lda, (const bf16*)W, bias, (const bf16*)residual, (bf16*)C, ldc, M, N, K, act, nullptr, nullptr, m_dev);
+            case Bf16Kernel::Small:
                 return setok_gemm_small_bf16(s, (const bf16*)A, lda, (const bf16*)W, bias, (const bf16*)residual, (bf16*)C, ldc, M, N, K, act, nullptr, nullptr, m_dev);
+            case Bf16Kernel::PersistF32Batched:
+                return setok_gemm_persist_f32_batched(s, (const bf16*)A, lda, (const bf16*)W, (float*)C, ldc, M, N, K, batch, strideA, strideW, strideC);
+            case Bf16Kernel::Tile128:
+                break;
         }
         dim3 grid(cdiv(N, BN), cdiv(M, BM), batch);
         if (out_dtype == SETOK_BF16) gemm_bf16_kernel<bf16, true><<<grid, 256, 0, s>>>(g);
@@ -304,8 +311,8 @@ extern "C" int setok_linear(void* stream, int dtype, int out_dtype, const void* 
     return setok_linear_dev(stream, dtype, out_dtype, A, lda, W, bias, residual, C, ldc, M, N, K, act, batch, strideA, strideW, strideC, nullptr);
 }
 
-// LayerNorm folded into the consuming Linear (bf16 throughput mode; gemm_persist.hip explains the algebra).  Same kernel choice as
-// setok_linear makes for a bf16 -> bf16 problem, so a row's result does not depend on the batch it is computed in.
+// LayerNorm folded into the consuming Linear (bf16 throughput mode; gemm_persist.hip explains the algebra).  The kernel is bf16_kernel's choice for the
+// same bf16 -> bf16 problem, so a row's result does not depend on the batch it is computed in.
 extern "C" int setok_linear_ln(void* stream, const void* A, int64_t lda, const void* w_gamma, const float* col_frag, const float* row_stats,
                                void* C, int64_t ldc, int M, int N, int K, int act) {
     SETOK_CHECK_ARG(A && w_gamma && col_frag && row_stats && C, "setok_linear_ln: null operand");
@@ -316,8 +323,8 @@ extern "C" int setok_linear_ln(void* stream, const void* A, int64_t lda, const v
     if (M == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;
     SetokProfScope prof(s, SETOK_PROF_GEMM_BF16, act | 8, 2.0 * M * N * K, ((double)M * K + (double)N * K) * 2.0 + (double)M * N * 2.0 + (double)M * 32.0, true);
-    static const int persist_min = [] { const char* e = getenv("SETOK_GEMM_PERSIST_MINTILES"); return e ? atoi(e) : 90; }();
-    if (K >= 192 && cdiv(M, 256) * cdiv(N, 256) >= persist_min)
+    const GemmArgs g{A, w_gamma, nullptr, nullptr, C, lda, ldc, 0, 0, 0, M, N, K, act, nullptr};
+    if (bf16_kernel(g, SETOK_BF16, 1) == Bf16Kernel::Persist)       // (the argument checks above leave only Persist or Small)
         return setok_gemm_persist_bf16(s, (const bf16*)A, lda, (const bf16*)w_gamma, nullptr, nullptr, (bf16*)C, ldc, M, N, K, act, row_stats, col_frag, nullptr);
     return setok_gemm_small_bf16(s, (const bf16*)A, lda, (const bf16*)w_gamma, nullptr, nullptr, (bf16*)C, ldc, M, N, K, act, row_stats, col_frag, nullptr);
 }

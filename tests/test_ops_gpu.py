@@ -811,7 +811,7 @@ def _merge_rem_outputs():
 
 
 def test_remainder_rows_inside_the_launch_equal_the_separate_launch(tmp_path):
-    """since round 5 a ping-pong launch finishes the rows behind its last whole 256-row tile itself (PP_MERGE_REM; the first wave row runs the
+    """since round 5 a ping-pong launch finishes the rows behind its last whole 256-row tile itself (the end of gemm_pp_body; the first wave row runs the
     small-tile kernel's tile function while the second has ended — correct only because s_barrier counts the surviving waves).  SETOK_GEMM_MERGE_REM=0 sends
     them to a launch of the small-tile kernel as rounds 3-4 did.  The switch is read once per process, so the other arm runs in a child process: identical
     bits for every activation x residual x folded-LayerNorm combination, at both remainder tile shapes."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """A/B of a Linear with the LayerNorm folded in (setok_linear_ln) against the plain Linear on the two ViT-L shapes that use it, sustained.
-SETOK_GEMM_TIMING=1 prints the per-tile s_memtime breakdown of each launch.  python tools/bench_ln_gemm.py [seconds]"""
+python tools/bench_ln_gemm.py [seconds]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
