@@ -270,10 +270,13 @@ def gather_rows(x: Tensor, perm: Tensor) -> Tensor:
     return out
 
 
-def segment_mean(h: Tensor, seg_offsets: Tensor, n_segs_dev: Tensor, n_segs: int) -> Tensor:
-    """n_segs_dev: 1-element int32 device tensor (e.g. img_offsets[B:]); n_segs: rows to allocate/launch."""
+def segment_mean(h: Tensor, seg_offsets: Tensor, n_segs_dev: Tensor, n_segs: int, out: Optional[Tensor] = None) -> Tensor:
+    """n_segs_dev: 1-element int32 device tensor (e.g. img_offsets[B:]); n_segs: rows to allocate/launch.  Rows of `out` at or beyond
+    n_segs_dev are not written."""
     Cc = h.shape[-1]
-    out = torch.empty((n_segs, Cc), dtype=h.dtype, device=h.device)
+    if out is None:
+        out = torch.empty((n_segs, Cc), dtype=h.dtype, device=h.device)
+    assert out.shape == (n_segs, Cc) and out.dtype == h.dtype
     _lib.call("setok_segment_mean", _stream(), _code(h.dtype), _p(h), _p(seg_offsets), _p(n_segs_dev), n_segs, _p(out), Cc)
     return out
 
