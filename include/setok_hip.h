@@ -434,6 +434,44 @@ int setok_attention_causal_gqa(void* stream, int dtype, const void* qkv, const u
 int setok_lm_loss(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels, const uint8_t* attention_mask, int B, int T,
                   int V, int ignore_index, float* row_ws, float* out);
 
+/* ---- Backward through the FROZEN LLM (stage 2 of the reference's recipe trains mm_in_projector through the language-model loss:
+ * scripts/pretrain_mm_proj.sh, src/train/train_setokim.py:335-339).  Only the dX chain exists: the Linears' dX are setok_linear calls against
+ * transposed weights, these are the backward twins of the entries above; no weight gradient is formed.  All deterministic (no atomics). */
+
+/* Backward of setok_lm_loss: dlogits[b, t, :] = upstream * (softmax(logits[b, t, :].float()) - onehot(labels[b, t + 1])) / n for the positions
+ * the forward counted, exact zeros in every other row (every sequence's last position among them).  loss_out: the forward's `out` on the
+ * device (n = loss_out[1] is read there: no host synchronisation); upstream: one float on the device (NULL = 1).  dlogits: B*T rows of V in
+ * `dtype` with its own row stride ldd; logits / dlogits rows may start at any element boundary (resized vocabularies: 32003).  When the forward
+ * counted no position every row is zero (nothing is divided by n). */
+int setok_lm_loss_bwd(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels, const uint8_t* attention_mask, int B, int T,
+                      int V, int ignore_index, const float* loss_out, const float* upstream, void* dlogits, int64_t ldd);
+
+/* dx of setok_rmsnorm (no weight gradient): statistics recomputed in fp32; g = (dy * weight).to(dtype) is the gradient at the forward's rounding
+ * point, dx = rstd * (g - xhat * mean(g * xhat)) rounded to dtype, + dres (optional: the residual branch's gradient, added in the same pass).
+ * dx may alias dy or dres. */
+int setok_rmsnorm_bwd(void* stream, int dtype, const void* x, const float* weight, const void* dy, const void* dres, void* dx, int rows, int C,
+                      float eps);
+
+/* The transpose of setok_rope_gqa, in place on the dq and dk parts of a [dq | dk | dv] buffer: the same cos / sin tables (fp32, rounded to
+ * dtype), the rotation reversed; dv is left untouched. */
+int setok_rope_bwd_gqa(void* stream, int dtype, void* dqkv, const int64_t* position_ids, int rows, int H, int Hkv, int Dh, float theta);
+
+/* Backward of setok_swiglu_pairs: from the pre-activation pairs (gate_j, up_j) (rows, 2 F) and dout (rows, F) to d (gate_j, up_j) in the same
+ * interleaved layout — what the dX GEMM against the pair-interleaved weight consumes. */
+int setok_swiglu_pairs_bwd(void* stream, int dtype, const void* gate_up_pairs, const void* dout, void* dpairs, int64_t rows, int F);
+
+/* Backward of setok_attention_causal_gqa.  qkv: the forward's input (post-rotary, [q: H | k: Hkv | v: Hkv] heads), out: its output, dout:
+ * d loss / d out; dqkv: the result in the layout of qkv.  The mask is the forward's (query i sees key j iff j <= i and key_mask[j] != 0): a query
+ * that sees no key gets dq = 0, a key no query sees gets dk = dv = 0.  dk / dv of a shared key / value head are the sum over its H / Hkv query
+ * heads in head order.  Nothing is saved by the forward: the log-sum-exp and do.o are recomputed into ws (2*B*T*H floats).  Two runs give the
+ * same bits and a sequence's gradients do not depend on the other sequences of the batch.  Head dim 128 in the 16-bit element type runs an MFMA
+ * pair (SETOK_LLAMA_ATTN_BWD_GENERIC=1 in the environment forces the generic pair), everything else a generic wave-per-row pair. */
+int setok_attention_causal_bwd_gqa(void* stream, int dtype, const void* qkv, const uint8_t* key_mask, const void* out, const void* dout, void* dqkv,
+                                   int B, int T, int H, int Hkv, int Dh, float scale, float* ws);
+/* ... Hkv == H */
+int setok_attention_causal_bwd(void* stream, int dtype, const void* qkv, const uint8_t* key_mask, const void* out, const void* dout, void* dqkv,
+                               int B, int T, int H, int Dh, float scale, float* ws);
+
 #ifdef __cplusplus
 }
 #endif

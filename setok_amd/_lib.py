@@ -94,6 +94,12 @@ SIGNATURES = {
     "setok_attention_causal": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f],
     "setok_attention_causal_gqa": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f],
     "setok_lm_loss": [_vp, _i, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "setok_lm_loss_bwd": [_vp, _i, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64],
+    "setok_rmsnorm_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f],
+    "setok_rope_bwd_gqa": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _f],
+    "setok_swiglu_pairs_bwd": [_vp, _i, _vp, _vp, _vp, _i64, _i],
+    "setok_attention_causal_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "setok_attention_causal_bwd_gqa": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "setok_splice_rows": [_vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _i64, _i, _vp],
     "setok_splice_rows_bwd": [_vp, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i],
 }

@@ -13,7 +13,10 @@ inside the transposes for db, setok_gelu_bwd, setok_layernorm_bwd, setok_splice_
     HeadFn        SetokTokenizer.encode_features                    d loss / d head parameters (inner_encoder, inter_encoder, out)
     DetokFn       SetokDeTokenizer.forward / decode_image /         d loss / d decoder parameters, d loss / d tokens (detok_train.py)
                   reconstruction_loss
+    LlamaFn       LlamaModel.forward with the decoder stack frozen  d loss / d inputs_embeds across the decoder layers (llama_train.py;
+    LlamaLMFn     SetokimLlamaPrefill.forward (logits, LM loss)     the LLM's own weights get no gradient: stage 2 freezes them)
 
+With them `loss.backward()` on SetokimLlamaPrefill's language-model loss reaches the projector: stage 2 end to end.
 Everything else on the path is inference-only and says so (round 4): the forward always runs — reference-style inference callers
 do not wrap their calls in no_grad and freshly built modules have trainable parameters — and, when torch would have recorded a graph, the
 outputs carry a grad_fn whose backward RAISES (`no_backward`), so nothing trains silently.  The CLIP tower, whose reference forward is itself
@@ -304,3 +307,80 @@ class DetokFn(torch.autograd.Function):
         ctx.saved = None
         out = tuple(_grad_as(grads.get(n), p) if need[n] else None for n, p in zip(ctx.names, ctx.params))
         return (None, None, None, None, dtokens, None, None) + out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the frozen LLM (llama.py): stage 2 trains mm_in_projector THROUGH it (train_setokim.py:335-339), so only d / d inputs_embeds exists
+# ----------------------------------------------------------------------------------------------------------------------------
+def _spent(what: str):
+    return RuntimeError(f"{what}: the saved activations were released by the first backward pass (run the forward again; retain_graph is not supported)")
+
+
+class LlamaFn(torch.autograd.Function):
+    """hidden = LlamaModel(inputs_embeds) with every decoder-stack parameter frozen: the prefill's calls, the prefill's bits, with the
+    activations llama_train.llama_backward needs kept."""
+
+    @staticmethod
+    def forward(ctx, model, inputs_embeds: torch.Tensor, attention_mask, position_ids):
+        from .llama_train import llama_forward_train
+        hidden, saved = llama_forward_train(model, inputs_embeds.detach(), attention_mask, position_ids)
+        ctx.model, ctx.saved, ctx.like = model, saved, inputs_embeds
+        return hidden
+
+    @staticmethod
+    def backward(ctx, dhidden: torch.Tensor):
+        from .llama_train import llama_backward
+        if ctx.saved is None:
+            raise _spent("LlamaModel.forward")
+        saved, ctx.saved = ctx.saved, None
+        dx = llama_backward(ctx.model, saved, dhidden) if ctx.needs_input_grad[1] else None
+        like, ctx.like = ctx.like, None
+        return None, _grad_as(dx, like), None, None
+
+
+class LlamaLMFn(torch.autograd.Function):
+    """(logits, loss) = SetokimLlamaPrefill's LLM + lm_head (+ the language-model loss when `labels` is given, else a zero) on inputs_embeds,
+    with the decoder stack and lm_head frozen.  backward: d loss / d logits (setok_lm_loss_bwd) plus any gradient sent to the logits
+    themselves -> lm_head dX -> llama_backward."""
+
+    @staticmethod
+    def forward(ctx, prefill, inputs_embeds: torch.Tensor, attention_mask, position_ids, labels):
+        from .llama_train import llama_forward_train
+        model = prefill.model
+        hidden, saved = llama_forward_train(model, inputs_embeds.detach(), attention_mask, position_ids)
+        B, T, D = hidden.shape
+        w = prefill.lm_head.weight.detach().contiguous()
+        logits = ops.linear(hidden.reshape(B * T, D), w).reshape(B, T, -1)
+        loss_out = ops.lm_loss(logits, labels, attention_mask) if labels is not None else None
+        ctx.prefill, ctx.saved, ctx.like = prefill, saved, inputs_embeds
+        ctx.lm = (logits, labels, attention_mask, loss_out)
+        ctx.set_materialize_grads(False)
+        return logits, (loss_out[0].clone() if loss_out is not None else logits.new_zeros((), dtype=torch.float32))
+
+    @staticmethod
+    def backward(ctx, dlogits: Optional[torch.Tensor], dloss: Optional[torch.Tensor]):
+        from .llama_train import llama_backward
+        if ctx.saved is None:
+            raise _spent("SetokimLlamaPrefill.forward")
+        saved, ctx.saved = ctx.saved, None
+        (logits, labels, attention_mask, loss_out), ctx.lm = ctx.lm, None
+        like, ctx.like = ctx.like, None
+        if not ctx.needs_input_grad[1] or (dlogits is None and (dloss is None or loss_out is None)):
+            return None, None, None, None, None
+        B, T, V = logits.shape
+        w = ctx.prefill.lm_head.weight.detach().contiguous()
+        gran = ops.k_align(logits.dtype)
+        Vp = ops.round_up(V, gran)                                    # the dX GEMM contracts over the vocabulary: zero columns up to its granule
+        dl = (torch.zeros if Vp != V else torch.empty)((B * T, Vp), dtype=logits.dtype, device=logits.device)
+        view = dl[:, :V].view(B, T, V) if Vp == V else dl.view(B, T, Vp)[:, :, :V]
+        if dloss is not None and loss_out is not None:
+            ops.lm_loss_bwd(logits, labels, attention_mask, loss_out, upstream=dloss, out=view)
+            if dlogits is not None:
+                view += dlogits.to(logits.dtype)
+        else:
+            view.copy_(dlogits.to(logits.dtype))
+        del logits
+        dhidden = ops.linear(dl, ops.transpose(w, pad_to=gran))     # lm_head dX
+        del dl
+        dx = llama_backward(ctx.prefill.model, saved, dhidden.reshape(B, T, -1))
+        return None, _grad_as(dx, like), None, None, None

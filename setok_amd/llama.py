@@ -10,7 +10,9 @@
 `model.layers.{i}.{input,post_attention}_layernorm.weight`, `model.norm.weight`, `lm_head.weight`) so a Vicuna / Llama-2 checkpoint loads
 unchanged, and runs the prefill (no KV cache, eager-attention arithmetic) as: RMSNorm -> one fused q|k|v GEMM -> rotary embedding in place
 -> causal + padding-masked MFMA attention -> o_proj GEMM with the residual fused -> RMSNorm -> one fused gate|up GEMM -> SwiGLU ->
-down_proj GEMM with the residual fused.  Inference only.  Grouped-query attention (num_key_value_heads < num_attention_heads: Llama-2-70B,
+down_proj GEMM with the residual fused.  The LLM's own weights get no gradient here (training them is the reference's HF-Trainer side); with the
+decoder stack FROZEN the forward is differentiable with respect to `inputs_embeds` (llama_train.py, autograd.LlamaFn / LlamaLMFn): the
+reference's stage 2, which trains mm_in_projector through the language-model loss.  Grouped-query attention (num_key_value_heads < num_attention_heads: Llama-2-70B,
 Llama-3, Mistral — Vicuna-7B / 13B do not use it) runs on the same kernels: the fused q|k|v rows are [H | Hkv | Hkv] heads wide and query head h
 reads key / value head h // (H // Hkv), HF's `repeat_kv` without the copies.
 """
@@ -95,11 +97,22 @@ class LlamaModel(PackCacheMixin, nn.Module):
 
     def forward(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None):
         """inputs_embeds (B, T, D); attention_mask (B, T), 1 = token (None = all); position_ids (B, T) (None = 0..T-1).
-        Returns the hidden states after the final norm, (B, T, D).  A prefill: inference arithmetic, no autograd graph (where torch would have
-        recorded one the result's backward raises — training the LLM is the reference's HF-Trainer side, SURVEY.md §2 "OUT")."""
+        Returns the hidden states after the final norm, (B, T, D).  Three situations:
+          gradients disabled, or nothing requires one            the prefill, no graph
+          a decoder-stack parameter (layers.*, norm) requires one   the prefill runs and the result's backward raises — training the LLM's own
+                                                                 weights is the reference's HF-Trainer side (SURVEY.md §2 "OUT")
+          the stack is frozen and inputs_embeds requires one     the same values with a grad_fn (autograd.LlamaFn): backward() delivers
+                                                                 d loss / d inputs_embeds"""
+        if torch.is_grad_enabled() and inputs_embeds.requires_grad and not self.stack_requires_grad():
+            return autograd.LlamaFn.apply(self, inputs_embeds, attention_mask, position_ids)
         with torch.no_grad():
             out = self._forward(inputs_embeds, attention_mask, position_ids)
-        return autograd.no_backward("LlamaModel.forward (the prefill has no backward pass on the HIP path)", out, [inputs_embeds, *self.parameters()])
+        return autograd.no_backward("LlamaModel.forward (the prefill has no backward pass for the LLM's own weights on the HIP path; "
+                                    "freeze the LLM to train through it)", out, [inputs_embeds, *self.parameters()])
+
+    def stack_requires_grad(self) -> bool:
+        """Does any parameter of the decoder stack (layers.*, norm — not embed_tokens, whose gradient comes from the splice) require a gradient?"""
+        return any(p.requires_grad for p in self.layers.parameters()) or self.norm.weight.requires_grad
 
     def _forward(self, inputs_embeds, attention_mask=None, position_ids=None):
         B, T, D = inputs_embeds.shape
@@ -193,16 +206,42 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, inputs_embeds=None, labels=None, comp_images=None,
                 last_token_only: bool = False, return_loss: bool = False):
-        with torch.no_grad():
-            out = self._forward(input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images, last_token_only, return_loss)
-        return autograd.no_backward("SetokimLlamaPrefill.forward (inference: encode -> splice -> prefill -> logits)", out, [inputs_embeds, *self.parameters()])
-
-    def _forward(self, input_ids=None, attention_mask=None, position_ids=None, inputs_embeds=None, labels=None, comp_images=None,
-                 last_token_only: bool = False, return_loss: bool = False):
         """Returns (logits, new_labels, attention_mask): logits (B, T', vocab) — or (B, vocab) for every sequence's last token with
         `last_token_only` (what a generation step after the prefill needs) — on the spliced sequence of length T'.  With `return_loss`
         (and labels) a fourth element is the language-model loss of setokim_llama.py:145-160 (shifted cross entropy over the positions whose
-        next token is neither padding nor IGNORE_INDEX), as a 0-d fp32 tensor; the diffusion term of :163-180 is not part of this path."""
+        next token is neither padding nor IGNORE_INDEX), as a 0-d fp32 tensor; the diffusion term of :163-180 is not part of this path.
+
+        Inference unless something upstream of the LLM is being trained THROUGH it: with the decoder stack (model.layers.*, model.norm, lm_head)
+        frozen and `inputs_embeds` requiring a gradient — passed in, or produced by the splice from a trainable projector / tokenizer head /
+        embed_tokens.weight — logits and loss carry a grad_fn (autograd.LlamaLMFn) and `loss.backward()` fills those gradients: the
+        reference's stage 2.  A stack parameter that requires a gradient keeps the inference behaviour: the forward runs, backward raises.
+        `last_token_only` and a `sliding_window` shorter than the sequence are inference-only."""
+        stack_live = self.model.stack_requires_grad() or self.lm_head.weight.requires_grad
+        may_train = torch.is_grad_enabled() and not stack_live
+        what = "SetokimLlamaPrefill.forward (inference: encode -> splice -> prefill -> logits; freeze the LLM to train through it)"
+        given = inputs_embeds
+        with torch.set_grad_enabled(may_train):
+            inputs_embeds, attention_mask, position_ids, new_labels = self._embed(input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images)
+        if may_train and inputs_embeds.requires_grad:
+            if last_token_only:
+                what = "SetokimLlamaPrefill.forward with last_token_only=True (a generation step: inference-only)"
+            else:
+                if return_loss and new_labels is None:
+                    raise ValueError("return_loss needs labels")
+                logits, loss = autograd.LlamaLMFn.apply(self, inputs_embeds, attention_mask, position_ids, new_labels if return_loss else None)
+                return (logits, new_labels, attention_mask, loss) if return_loss else (logits, new_labels, attention_mask)
+        with torch.no_grad():
+            out = self._head(inputs_embeds.detach(), attention_mask, position_ids, new_labels, last_token_only, return_loss)
+        return autograd.no_backward(what, out, [given, inputs_embeds, *self.parameters()])
+
+    def _forward(self, input_ids=None, attention_mask=None, position_ids=None, inputs_embeds=None, labels=None, comp_images=None,
+                 last_token_only: bool = False, return_loss: bool = False):
+        """The inference arithmetic in one call (no graph handling): splice, then the LLM and the vocabulary projection."""
+        inputs_embeds, attention_mask, position_ids, new_labels = self._embed(input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images)
+        return self._head(inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss)
+
+    def _embed(self, input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images):
+        """(inputs_embeds, attention_mask, position_ids, labels) on the spliced sequence (setokim_llama.py:118-128)."""
         new_labels = labels
         self._last_features = None
         if inputs_embeds is None:
@@ -213,17 +252,23 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                 # TARGET_TOKEN_INDEX, an id >= vocab — raises the reference's IndexError (torch's embedding) instead of becoming an address
                 w_e = self.model.embed_tokens.weight.detach().contiguous()
                 status = torch.empty(2, dtype=torch.int32, device=w_e.device)
-                inputs_embeds = ops.splice_rows(input_ids.to(device=w_e.device, dtype=torch.int32).contiguous(), w_e, None, status)
+                src = input_ids.to(device=w_e.device, dtype=torch.int32).contiguous()
+                inputs_embeds = ops.splice_rows(src, w_e, None, status)
                 st = status.cpu()
                 if int(st[0]) != 0:
                     b, t = divmod(int(st[1]), input_ids.shape[1])
                     raise IndexError(f"index out of range in self: input_ids[{b}, {t}] = {int(input_ids[b, t])} is not a row of the "
                                      f"{w_e.shape[0]}-row embedding table (and no images were passed for image placeholders)")
+                if autograd.grad_needed(self.model.embed_tokens.weight):           # a trainable embedding table: the same rows with a grad_fn
+                    inputs_embeds = autograd.SpliceRowsFn.apply(None, self.model.embed_tokens.weight, src)
         sw = config_get(self.config, "sliding_window")
         if sw is not None and int(sw) < inputs_embeds.shape[1]:
             raise NotImplementedError(f"SetokimLlamaPrefill: sliding_window={sw} is shorter than the sequence ({inputs_embeds.shape[1]} positions): "
                                       "windowed attention is not implemented on the HIP path")
-        hidden = self.model(inputs_embeds, attention_mask, position_ids)           # setokim_llama.py:130-140
+        return inputs_embeds, attention_mask, position_ids, new_labels
+
+    def _head(self, inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss):
+        hidden = self.model._forward(inputs_embeds, attention_mask, position_ids)  # setokim_llama.py:130-140
         B, T, D = hidden.shape
         w = self.lm_head.weight.detach().contiguous()
         if last_token_only:

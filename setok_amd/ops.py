@@ -632,3 +632,72 @@ def attention_causal(qkv: Tensor, key_mask: Optional[Tensor], B: int, T: int, H:
     out = torch.empty((B * T, H * Dh), dtype=qkv.dtype, device=qkv.device)
     _lib.call("setok_attention_causal_gqa", _stream(), _code(qkv.dtype), _p(qkv), _p(key_mask), _p(out), B, T, H, Hkv, Dh, scale)
     return out
+
+
+# ---- backward through the frozen LLM (csrc/llama_bwd.hip, csrc/attn_causal_bwd.hip): the dX chain only ----------------------------------------
+def lm_loss_bwd(logits: Tensor, labels: Tensor, attention_mask: Optional[Tensor], loss_out: Tensor, upstream: Optional[Tensor] = None,
+                ignore_index: int = -100, out: Optional[Tensor] = None) -> Tensor:
+    """d loss / d logits for `loss_out = lm_loss(logits, labels, attention_mask)` (its 2-element result: the count is read on the device), times
+    the 0-d / 1-element fp32 device tensor `upstream` (None = 1).  Rows the forward did not count are exact zeros.  `out`: (B, T, V) in the
+    dtype of logits with unit column stride (a view with its own row stride is fine)."""
+    B, T, V = logits.shape
+    lg = logits.reshape(B * T, V)
+    assert lg.stride(1) == 1 and lg.is_cuda and loss_out.dtype == torch.float32 and loss_out.numel() >= 2
+    if out is None:
+        out = torch.empty((B, T, V), dtype=logits.dtype, device=logits.device)
+    do = out.reshape(B * T, V)
+    assert do.dtype == logits.dtype and do.stride(1) == 1 and do.data_ptr() == out.data_ptr()
+    lab = labels.to(device=logits.device, dtype=torch.int64).reshape(B * T).contiguous()
+    am = None if attention_mask is None else (attention_mask.to(logits.device) != 0).to(torch.uint8).reshape(B * T).contiguous()
+    up = None if upstream is None else upstream.detach().reshape(1).to(device=logits.device, dtype=torch.float32).contiguous()
+    _lib.call("setok_lm_loss_bwd", _stream(), _code(logits.dtype), lg.data_ptr(), lg.stride(0), _p(lab), _p(am), B, T, V, ignore_index,
+              _p(loss_out.contiguous()), _p(up), do.data_ptr(), do.stride(0))
+    return out
+
+
+def rmsnorm_bwd(x: Tensor, weight: Tensor, dy: Tensor, eps: float, dres: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """dx of rmsnorm(x, weight, eps) for the upstream dy, plus `dres` (the residual branch's gradient) in the same pass.  `out` may be dy or dres."""
+    rows, Cc = x.shape
+    assert dy.shape == x.shape and dy.dtype == x.dtype and (dres is None or (dres.shape == x.shape and dres.dtype == x.dtype))
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype
+    w = weight if weight.dtype == torch.float32 else weight.float()
+    _lib.call("setok_rmsnorm_bwd", _stream(), _code(x.dtype), _p(x), _p(w.contiguous()), _p(dy), _p(dres), _p(out), rows, Cc, eps)
+    return out
+
+
+def rope_bwd_(dqkv: Tensor, position_ids: Tensor, H: int, Dh: int, theta: float, Hkv: Optional[int] = None) -> Tensor:
+    """The transpose of rope_, in place on the dq and dk parts of dqkv (rows, (H + 2*Hkv)*Dh); dv untouched."""
+    rows = dqkv.shape[0]
+    Hkv = H if Hkv is None else Hkv
+    assert dqkv.shape[1] == (H + 2 * Hkv) * Dh and position_ids.dtype == torch.int64 and position_ids.numel() == rows
+    _lib.call("setok_rope_bwd_gqa", _stream(), _code(dqkv.dtype), _p(dqkv), _p(position_ids.contiguous()), rows, H, Hkv, Dh, theta)
+    return dqkv
+
+
+def swiglu_pairs_bwd(gate_up_pairs: Tensor, dout: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """d (gate_j, up_j) pairs (rows, 2 F) from the pre-activation pairs and d loss / d swiglu_pairs(...) (rows, F).  `out` may be gate_up_pairs."""
+    rows, F2 = gate_up_pairs.shape
+    assert dout.shape == (rows, F2 // 2) and dout.dtype == gate_up_pairs.dtype
+    if out is None:
+        out = torch.empty_like(gate_up_pairs)
+    assert out.shape == gate_up_pairs.shape and out.dtype == gate_up_pairs.dtype
+    _lib.call("setok_swiglu_pairs_bwd", _stream(), _code(gate_up_pairs.dtype), _p(gate_up_pairs), _p(dout), _p(out), rows, F2 // 2)
+    return out
+
+
+def attention_causal_bwd(qkv: Tensor, key_mask: Optional[Tensor], out: Tensor, dout: Tensor, B: int, T: int, H: int, Dh: int, scale: float,
+                         Hkv: Optional[int] = None) -> Tensor:
+    """Backward of attention_causal: dqkv in the layout of qkv ([dq: H heads | dk: Hkv | dv: Hkv]) from the forward's (post-rotary) input, its output
+    and d loss / d out."""
+    Hkv = H if Hkv is None else Hkv
+    assert qkv.shape == (B * T, (H + 2 * Hkv) * Dh) and H % Hkv == 0
+    assert out.shape == (B * T, H * Dh) and dout.shape == out.shape and out.dtype == qkv.dtype and dout.dtype == qkv.dtype
+    if key_mask is not None:
+        assert key_mask.dtype == torch.uint8 and key_mask.numel() == B * T
+    dqkv = torch.empty_like(qkv)
+    ws = _ws(qkv.device, 2 * B * T * H)
+    _lib.call("setok_attention_causal_bwd_gqa", _stream(), _code(qkv.dtype), _p(qkv), _p(key_mask), _p(out), _p(dout), _p(dqkv), B, T, H, Hkv, Dh, scale,
+              _p(ws))
+    return dqkv
