@@ -472,6 +472,38 @@ int setok_attention_causal_bwd_gqa(void* stream, int dtype, const void* qkv, con
 int setok_attention_causal_bwd(void* stream, int dtype, const void* qkv, const uint8_t* key_mask, const void* out, const void* dout, void* dqkv,
                                int B, int T, int H, int Dh, float scale, float* ws);
 
+/* ---- KV-cached greedy decoding (SetokimLlamaForCausalLM.generate, setokim_llama.py:329-396: encode, splice, prefill, then one token per
+ * step against `past_key_values`, :99,133,189).  The step's Linears are setok_linear calls at M = B, its RMSNorm / rotary embedding / SwiGLU the
+ * entries above on B rows; these are the rest.  Pure additions: the ABI version stays 9. */
+
+/* Keys of one chunk of the decode attention: its work is cut over (chunk of this many cache slots, key / value head, sequence).  A constant, so
+ * that how a sequence's keys are partitioned (and every summation order with it) depends on `len` alone. */
+#define SETOK_DECODE_CHUNK 128
+
+/* HF DynamicCache.update (reached from LlamaAttention.forward, modeling_llama.py, with `past_key_values` of setokim_llama.py:133): the post-rotary
+ * k and v columns of B*T rows of a fused [q: H | k: Hkv | v: Hkv] buffer (what setok_rope_gqa leaves behind) are copied to slots
+ * [pos0, pos0 + T) of every sequence of a per-layer cache.  k_cache, v_cache: (B, Hkv, cap, Dh) in `dtype` - the keys of one (sequence,
+ * key / value head) are contiguous rows.  16-byte accesses (operands 16-byte aligned, Dh % 8 == 0); every other slot is left untouched. */
+int setok_kv_append(void* stream, int dtype, const void* qkv, void* k_cache, void* v_cache, int B, int T, int H, int Hkv, int Dh, int cap, int pos0);
+
+/* eager_attention_forward (HF modeling_llama.py: softmax(q k^T * scale + mask) v, fp32 softmax, repeat_kv) for ONE new token per sequence:
+ * query row b of q (B rows of stride ldq elements, H heads of Dh - the q part of the step's fused qkv buffer is read in place) against the cached
+ * keys / values of sequence b.  A key counts iff its slot is < len and key_mask[b * cap + slot] != 0 (key_mask: (B, cap) uint8); a sequence
+ * without such a key gets zeros (setok_attention_causal's convention).  out: (B, H*Dh).
+ * Each K / V byte of a (sequence, key / value head) is read once, for the H / Hkv query heads of its group together.  ws: fp32 workspace of
+ * ws_floats >= B * H * ceil(len / SETOK_DECODE_CHUNK) * (Dh + 2) floats (per-chunk maximum, sum and Dh accumulators, merged in chunk order by a
+ * second launch: no atomics).  A sequence's output bits depend only on its own q, keys, values, mask and `len`: not on B, not on cap, not on the run.
+ * In the 16-bit types the probabilities are rounded to the element type before they multiply V (HF's rounding point).  Dh % 8 == 0; Dh = 128 in the
+ * 16-bit type is the tuned shape; masked slots below len must hold initialised memory (they are read, then discarded). */
+int setok_attention_decode_gqa(void* stream, int dtype, const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                               const uint8_t* key_mask, void* out, int B, int H, int Hkv, int Dh, int cap, int len, float scale, float* ws,
+                               int64_t ws_floats);
+
+/* Greedy selection (`do_sample=False` of HF GenerationMixin, reached from setokim_llama.py:381-396: torch.argmax(next_token_scores, dim=-1)):
+ * out[r] (int64) = the LOWEST index of the maximum of row r of x (rows x V in `dtype`, row stride ld elements, any alignment, V = 32003 included);
+ * a NaN counts as the maximum.  Deterministic. */
+int setok_argmax_rows(void* stream, int dtype, const void* x, int64_t ld, int rows, int V, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,9 @@ SIGNATURES = {
     "setok_attention_causal_bwd_gqa": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "setok_splice_rows": [_vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _i64, _i, _vp],
     "setok_splice_rows_bwd": [_vp, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i],
+    "setok_kv_append": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
+    "setok_attention_decode_gqa": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_argmax_rows": [_vp, _i, _vp, _i64, _i, _i, _vp],
 }
 
 _libs = {}

@@ -15,6 +15,10 @@ decoder stack FROZEN the forward is differentiable with respect to `inputs_embed
 reference's stage 2, which trains mm_in_projector through the language-model loss.  Grouped-query attention (num_key_value_heads < num_attention_heads: Llama-2-70B,
 Llama-3, Mistral — Vicuna-7B / 13B do not use it) runs on the same kernels: the fused q|k|v rows are [H | Hkv | Hkv] heads wide and query head h
 reads key / value head h // (H // Hkv), HF's `repeat_kv` without the copies.
+
+Generation (`SetokimLlamaForCausalLM.generate`, setokim_llama.py:329-396) is greedy decoding with a KV cache: `LlamaModel.prefill` is the same
+prefill that also fills a `generation.KVCache`, `LlamaModel.decode_step` runs one token per sequence against it (csrc/attn_decode.hip), and
+`SetokimLlamaPrefill.generate` is the loop.
 """
 from __future__ import annotations
 
@@ -114,7 +118,9 @@ class LlamaModel(PackCacheMixin, nn.Module):
         """Does any parameter of the decoder stack (layers.*, norm — not embed_tokens, whose gradient comes from the splice) require a gradient?"""
         return any(p.requires_grad for p in self.layers.parameters()) or self.norm.weight.requires_grad
 
-    def _forward(self, inputs_embeds, attention_mask=None, position_ids=None):
+    def _forward(self, inputs_embeds, attention_mask=None, position_ids=None, cache=None):
+        """The prefill.  With `cache` (a generation.KVCache, empty) every layer's post-rotary keys / values are also copied to its slots [0, T):
+        one more launch per layer, nothing else changes."""
         B, T, D = inputs_embeds.shape
         pk = self._pack()
         H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
@@ -125,16 +131,77 @@ class LlamaModel(PackCacheMixin, nn.Module):
         pos = position_ids.to(device=dev, dtype=torch.int64).reshape(B * T).contiguous()
         km = None if attention_mask is None else attention_mask.to(device=dev).bool().to(torch.uint8).reshape(B * T).contiguous()
         y = None
-        for L in pk["layers"]:
+        for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
             qkv = ops.linear(y, L["wqkv"])
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
+            if cache is not None:
+                ops.kv_append(qkv, cache.k[li], cache.v[li], T, H, 0)
             o = ops.attention_causal(qkv, km, B, T, H, dh, dh ** -0.5, Hkv)
             ops.linear(o, L["wo"], residual=x, out=x)
             y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
             g = ops.linear_swiglu(y, L["wgu"])                           # gate|up Linear with SwiGLU in its epilogue (16-bit modes; the unfused pair otherwise: same bits)
             ops.linear(g, L["wd"], residual=x, out=x)
+        if cache is not None:
+            # every sequence's next rotary position: the position of its last attended token + 1 (HF extends `cumsum(attention_mask) - 1` the same way)
+            p2 = pos.reshape(B, T)
+            if km is None:
+                cache.key_mask[:, :T] = 1
+                cache.next_pos.copy_(p2[:, -1] + 1)
+            else:
+                m2 = km.reshape(B, T)
+                cache.key_mask[:, :T] = m2
+                last = (m2.long() * torch.arange(T, device=dev)[None]).max(dim=1).values
+                cache.next_pos.copy_(torch.where(m2.bool().any(dim=1), p2.gather(1, last[:, None])[:, 0] + 1, torch.zeros_like(last)))
+            cache.len = T
         return ops.rmsnorm(x, pk["norm"], self.eps, out=y).reshape(B, T, D)
+
+    @torch.no_grad()
+    def prefill(self, inputs_embeds, attention_mask=None, position_ids=None, cache=None):
+        """`_forward` (the same calls in the same order: the same bits) that also fills `cache` — the first call of HF's generate, which returns
+        `past_key_values` next to the hidden states (setokim_llama.py:133,189).  Returns the final-norm hidden states (B, T, D)."""
+        if cache is None:
+            raise ValueError("LlamaModel.prefill needs a generation.KVCache to fill (forward() is the prefill without one)")
+        B, T, _ = inputs_embeds.shape
+        if cache.len != 0 or cache.B != B or cache.cap < T or len(cache.k) != len(self.layers) or cache.k[0].dtype != self.norm.weight.dtype:
+            raise ValueError(f"LlamaModel.prefill: the cache (B={cache.B}, cap={cache.cap}, len={cache.len}, {len(cache.k)} layers, "
+                             f"{cache.k[0].dtype}) does not fit an empty prefill of B={B}, T={T}")
+        return self._forward(inputs_embeds, attention_mask, position_ids, cache)
+
+    @torch.no_grad()
+    def decode_step(self, inputs_embeds, cache):
+        """One token per sequence against the cache: inputs_embeds (B, D) -> the final-norm hidden states (B, D).  The token is appended at slot
+        `cache.len` of every sequence and rotated to the sequence's own next position (`cache.next_pos`: the position of its last attended token
+        + 1), so left- and right-padded prompts both work — with right padding the masked slots simply stay masked.  HF LlamaDecoderLayer.forward with
+        `past_key_values` on a one-token input; the GEMMs are the prefill's, at M = B."""
+        B, D = inputs_embeds.shape
+        slot = cache.len
+        if slot < 1 or slot >= cache.cap or B != cache.B:
+            raise ValueError(f"LlamaModel.decode_step: cache of B={cache.B} with {slot} of {cache.cap} slots filled cannot take a step of B={B} "
+                             "(prefill first; cap = prompt length + max_new_tokens)")
+        pk = self._pack()
+        H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
+        x = inputs_embeds.to(self.norm.weight.dtype).contiguous().clone()
+        pos = cache.next_pos
+        cache.key_mask[:, slot] = 1
+        ws = cache.workspace(H)
+        y = o = None
+        for li, L in enumerate(pk["layers"]):
+            y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
+            qkv = ops.linear(y, L["wqkv"])
+            ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
+            ops.kv_append(qkv, cache.k[li], cache.v[li], 1, H, slot)
+            o = ops.attention_decode(qkv, cache.k[li], cache.v[li], cache.key_mask, H, slot + 1, dh ** -0.5, ws=ws, out=o)
+            ops.linear(o, L["wo"], residual=x, out=x)
+            y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
+            g = ops.linear_swiglu(y, L["wgu"])
+            ops.linear(g, L["wd"], residual=x, out=x)
+        cache.len = slot + 1
+        cache.next_pos = pos + 1
+        return ops.rmsnorm(x, pk["norm"], self.eps, out=y)
+
+
+_SAMPLING_ARGS = ("temperature", "top_p", "top_k", "num_beams", "penalty_alpha", "repetition_penalty")      # generate(): named so that they are refused by name
 
 
 def _refuse_unsupported_llama_fields(g) -> None:
@@ -266,6 +333,85 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             raise NotImplementedError(f"SetokimLlamaPrefill: sliding_window={sw} is shorter than the sequence ({inputs_embeds.shape[1]} positions): "
                                       "windowed attention is not implemented on the HIP path")
         return inputs_embeds, attention_mask, position_ids, new_labels
+
+    @torch.no_grad()
+    def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
+                 eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
+                 output_hidden_states: bool = False, output_logits: bool = False, images=None, **unsupported):
+        """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
+        the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
+        embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
+
+        Returns the NEW tokens only, (B, n_new) int64: the splice makes the prompt ragged (an image placeholder becomes L_i rows), and with
+        `inputs_embeds` HF's generate returns the new tokens only as well.  With `eos_token_id` (an int or a list) a finished sequence emits
+        `pad_token_id` (default: the first eos id, HF's rule) from then on and the loop ends when every sequence has finished (one small host read
+        per step).  `return_dict_in_generate` returns a generation.GenerateOutput: sequences, hidden_states (B, n_new, D) with
+        `output_hidden_states` — row j is the final-norm state that produced token j, what the reference hands its image head (:363-379) — and
+        logits (B, n_new, V) with `output_logits`.  Passing `inputs_embeds` (the spliced embeddings) is a superset of the reference, which raises.
+
+        Greedy is the implemented mode: `do_sample=True`, a temperature / top-p / top-k or beams raise NotImplementedError (the reference's own
+        defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here).  A
+        `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
+        from .generation import GenerateOutput, KVCache
+        sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
+        if do_sample or sampling:
+            raise NotImplementedError(f"SetokimLlamaPrefill.generate: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "
+                                      "is the implemented mode; sampling and beam search are not implemented on the HIP path")
+        unknown = [k for k in unsupported if k not in _SAMPLING_ARGS]
+        if unknown:
+            raise TypeError(f"SetokimLlamaPrefill.generate: unexpected arguments {unknown}")
+        if images is not None:
+            if comp_images is not None:
+                raise ValueError("SetokimLlamaPrefill.generate: pass the images as `comp_images` or as `images`, not both")
+            comp_images = images
+        if max_new_tokens < 1:
+            raise ValueError("SetokimLlamaPrefill.generate: max_new_tokens must be at least 1")
+        embeds, am, pos, _ = self._embed(inputs, attention_mask, position_ids, inputs_embeds, None, comp_images)
+        B, T, D = embeds.shape
+        dev = self.lm_head.weight.device
+        sw = config_get(self.config, "sliding_window")
+        if sw is not None and int(sw) < T + max_new_tokens:
+            raise NotImplementedError(f"SetokimLlamaPrefill.generate: sliding_window={sw} is shorter than prompt + max_new_tokens "
+                                      f"({T} + {max_new_tokens} positions): windowed attention is not implemented on the HIP path")
+        if am is not None:
+            am = am.to(dev)
+            if pos is None:                                                        # HF generate's rule for a padded prompt without position_ids
+                pos = (am.long().cumsum(-1) - 1).masked_fill(am == 0, 1)
+        eos = None
+        if eos_token_id is not None:
+            eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), dtype=torch.int64, device=dev)
+            pad = int(eos[0]) if pad_token_id is None else int(pad_token_id)
+        cache = KVCache.for_model(self.model, B, T + max_new_tokens, dev)
+        hidden = self.model.prefill(embeds.to(dev), am, pos, cache)
+        if am is None:
+            h = hidden[:, -1].contiguous()
+        else:
+            last = (am.bool() * torch.arange(T, device=dev)[None]).max(dim=1).values
+            h = hidden[torch.arange(B, device=dev), last].contiguous()
+        w_lm = self.lm_head.weight.detach().contiguous()
+        w_e = self.model.embed_tokens.weight.detach().contiguous()
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        toks, hids, lgs = [], [], []
+        for step in range(max_new_tokens):
+            logits = ops.linear(h, w_lm)                                           # (B, V): never copied to the host
+            tok = ops.argmax_rows(logits)
+            if eos is not None:
+                tok = torch.where(finished, torch.full_like(tok, pad), tok)
+                finished = finished | torch.isin(tok, eos)
+            toks.append(tok)
+            if output_hidden_states:
+                hids.append(h)
+            if output_logits:
+                lgs.append(logits)
+            if step + 1 == max_new_tokens or (eos is not None and bool(finished.all())):
+                break
+            e = ops.splice_rows(tok.to(torch.int32).reshape(B, 1), w_e, None)      # embed_tokens on the new ids
+            h = self.model.decode_step(e.reshape(B, D), cache)
+        seq = torch.stack(toks, dim=1)
+        if not return_dict_in_generate:
+            return seq
+        return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if output_hidden_states else None,
+                              logits=torch.stack(lgs, dim=1) if output_logits else None)
 
     def _head(self, inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss):
         hidden = self.model._forward(inputs_embeds, attention_mask, position_ids)  # setokim_llama.py:130-140

@@ -701,3 +701,51 @@ def attention_causal_bwd(qkv: Tensor, key_mask: Optional[Tensor], out: Tensor, d
     _lib.call("setok_attention_causal_bwd_gqa", _stream(), _code(qkv.dtype), _p(qkv), _p(key_mask), _p(out), _p(dout), _p(dqkv), B, T, H, Hkv, Dh, scale,
               _p(ws))
     return dqkv
+
+
+# ---- KV-cached decoding (csrc/attn_decode.hip) ------------------------------------------------------------------------------------------------
+DECODE_CHUNK = 128                                # SETOK_DECODE_CHUNK of include/setok_hip.h
+
+
+def kv_append(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, T: int, H: int, pos0: int) -> None:
+    """The post-rotary k / v columns of qkv (B*T rows [q: H | k: Hkv | v: Hkv]) -> slots [pos0, pos0 + T) of the (B, Hkv, cap, Dh) caches."""
+    B, Hkv, cap, Dh = k_cache.shape
+    assert v_cache.shape == k_cache.shape and k_cache.dtype == v_cache.dtype == qkv.dtype
+    assert qkv.shape == (B * T, (H + 2 * Hkv) * Dh)
+    _lib.call("setok_kv_append", _stream(), _code(qkv.dtype), _p(qkv), _p(k_cache), _p(v_cache), B, T, H, Hkv, Dh, cap, pos0)
+
+
+def attention_decode_workspace(B: int, H: int, Dh: int, length: int) -> int:
+    """Floats of workspace setok_attention_decode_gqa needs for `length` candidate slots."""
+    return B * H * ((length + DECODE_CHUNK - 1) // DECODE_CHUNK) * (Dh + 2)
+
+
+def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tensor, H: int, length: int, scale: float,
+                     ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """One query row per (sequence, query head) against slots [0, length) of the caches (B, Hkv, cap, Dh); q: (B, >= H*Dh) rows, row stride
+    q.stride(0) (the step's fused qkv buffer is read in place); key_mask (B, cap) uint8.  Returns (B, H*Dh)."""
+    B, Hkv, cap, Dh = k_cache.shape
+    assert v_cache.shape == k_cache.shape and k_cache.dtype == v_cache.dtype == q.dtype
+    assert q.shape[0] == B and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, cap)
+    need = attention_decode_workspace(B, H, Dh, length)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_decode_gqa", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_cache), _p(v_cache), _p(key_mask), _p(out),
+              B, H, Hkv, Dh, cap, length, scale, _p(ws), ws.numel())
+    return out
+
+
+def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """int64 (rows,): the lowest index of each row's maximum; x (rows, V) with any row stride."""
+    rows, V = x.shape
+    assert x.stride(1) == 1 and x.is_cuda
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=x.device)
+    assert out.dtype == torch.int64 and out.numel() == rows
+    _lib.call("setok_argmax_rows", _stream(), _code(x.dtype), x.data_ptr(), x.stride(0), rows, V, _p(out))
+    return out

@@ -1,0 +1,177 @@
+"""KV-cached greedy decoding at the cfg5 shape (Vicuna-7B dims, bf16, prompt T' = 552 spliced positions) against the only way the library had
+to produce token n + 1 before: the whole prefill again over the sequence grown by one token.
+
+    python tools/bench_generate.py [--layers 32] [--batches 32,8,1] [--prompt 552] [--new 200] [--reps 5]
+    python tools/bench_generate.py --steps-only 3 [--batch 32]          # prefill-free: a few decode steps and nothing else (what a kernel trace is pointed at)
+    python tools/bench_generate.py --attention-only [--gqa 4]           # the decode-attention launch pair alone (what a counter run is pointed at)
+
+Prints one JSON line.  Per batch size, in one process:
+  (a) ms per token the old way: forward(inputs_embeds of T' + 1 positions, last_token_only=True);
+  (b) ms per token with the cache at the first and at the `--new`-th new token (lm_head + argmax + embedding rows + decode_step), the
+      decode_step alone, and a whole generate() call divided by its tokens;
+  (c) the decode-attention launch pair (chunks + merge) over all layers' caches — each layer has its own, so the keys are never re-read from a
+      cache level — as live K/V bytes / time: TB/s, the fraction of 8 TB/s (HBM3E peak) and of the 6.0-6.3 TB/s the LayerNorm kernels reach
+      on this chip.
+The caches are filled with random data (zeros would flatter the softmax and the clocks)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+D, H, DH, FD, V = 4096, 32, 128, 11008, 32000
+
+
+def _time(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def _llm(layers, g, dev, dt, hkv=H):
+    from setok_amd.llama import SetokimLlamaPrefill
+    cfg = dict(vocab_size=V, hidden_size=D, intermediate_size=FD, num_hidden_layers=layers, num_attention_heads=H, num_key_value_heads=hkv,
+               rms_norm_eps=1e-5, rope_theta=10000.0)
+    with torch.device(dev):
+        llm = SetokimLlamaPrefill(cfg).to(dt)
+    for p in llm.parameters():
+        if p.dim() == 2:
+            p.data.normal_(0.0, 0.02, generator=g)
+        else:
+            p.data.fill_(1.0)
+    return llm.eval().requires_grad_(False)
+
+
+def _filled_cache(llm, B, cap, length, g):
+    """A cache as a prompt of `length` positions leaves it, with random keys / values (no prefill needed for timing)."""
+    from setok_amd.generation import KVCache
+    c = KVCache.for_model(llm.model, B, cap)
+    for t in c.k + c.v:
+        t.normal_(0.0, 1.0, generator=g)
+    c.key_mask[:, :length] = 1
+    c.next_pos.fill_(length)
+    c.len = length
+    return c
+
+
+def _set_len(c, length):
+    c.key_mask.zero_()
+    c.key_mask[:, :length] = 1
+    c.next_pos.fill_(length)
+    c.len = length
+
+
+def _attention_pair(c, q, length, reps):
+    """ms of the chunks + merge pair summed over every layer's cache, and the live K / V bytes it reads."""
+    from setok_amd import ops
+    ws = c.workspace(H)
+    out = torch.empty(c.B, H * DH, dtype=q.dtype, device=q.device)
+    fn = lambda: [ops.attention_decode(q, k, v, c.key_mask, H, length, DH ** -0.5, ws=ws, out=out) for k, v in zip(c.k, c.v)]
+    ms = _time(fn, reps)
+    live = 2.0 * len(c.k) * c.B * c.Hkv * length * DH * c.k[0].element_size()
+    return ms, live
+
+
+def _bw(ms, live):
+    tbs = live / (ms * 1e-3) / 1e12
+    return dict(ms_all_layers=round(ms, 4), live_kv_gb=round(live / 1e9, 3), tb_per_s=round(tbs, 3), of_8_tb_per_s=round(tbs / 8.0, 3),
+                of_layernorm_6p0_to_6p3=[round(tbs / 6.3, 3), round(tbs / 6.0, 3)])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--batches", default="32,8,1")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--prompt", type=int, default=552)
+    ap.add_argument("--new", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps-only", type=int, default=0)
+    ap.add_argument("--attention-only", action="store_true")
+    ap.add_argument("--gqa", type=int, default=4)
+    a = ap.parse_args()
+    from setok_amd import ops
+
+    dev, dt = "cuda:0", torch.bfloat16
+    g = torch.Generator(device=dev).manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float32).to(dt)
+    T, N = a.prompt, a.new
+
+    if a.attention_only:                             # one GQA shape, K / V well past the 256 MiB the last cache level holds; two launches of the pair
+        B, Hkv, n = 32, H // a.gqa, 4000
+        k, v = rnd(B, Hkv, n, DH), rnd(B, Hkv, n, DH)
+        q, mask = rnd(B, (H + 2 * Hkv) * DH), torch.ones(B, n, dtype=torch.uint8, device=dev)
+        for _ in range(2):
+            ops.attention_decode(q, k, v, mask, H, n, DH ** -0.5)
+        torch.cuda.synchronize()
+        print(json.dumps(dict(shape=dict(B=B, H=H, Hkv=Hkv, Dh=DH, len=n), launches_of_the_pair=2, live_kv_bytes_per_launch=2 * k.numel() * 2)))
+        return
+
+    llm = _llm(a.layers, g, dev, dt)
+    w_lm, w_e = llm.lm_head.weight.detach(), llm.model.embed_tokens.weight.detach()
+
+    def token_step(c, h):
+        tok = ops.argmax_rows(ops.linear(h, w_lm))
+        e = ops.splice_rows(tok.to(torch.int32).reshape(-1, 1), w_e, None)
+        return llm.model.decode_step(e.reshape(-1, D), c)
+
+    if a.steps_only:
+        B = a.batch
+        c = _filled_cache(llm, B, T + N, T, g)
+        h = rnd(B, D)
+        for _ in range(a.steps_only):
+            h = token_step(c, h)
+        torch.cuda.synchronize()
+        print(json.dumps(dict(batch=B, prompt=T, decode_steps=a.steps_only, layers=a.layers)))
+        return
+
+    res = {}
+    for B in [int(b) for b in a.batches.split(",")]:
+        grown = rnd(B, T + 1, D)
+        am = torch.ones(B, T + 1, dtype=torch.bool, device=dev)
+        t_old = _time(lambda: llm(inputs_embeds=grown, attention_mask=am, last_token_only=True), max(2, a.reps // 2))
+        c = _filled_cache(llm, B, T + N, T, g)
+        h, e1 = rnd(B, D), rnd(B, D)
+        r = dict(ms_per_token_by_full_prefill=round(t_old, 3), kv_cache_gb=round(c.nbytes() / 1e9, 3))
+        for tag, length in (("first", T), (f"token_{N}", T + N - 1)):
+            def step(fn):
+                _set_len(c, length)
+                return fn()
+            t_tok = _time(lambda: step(lambda: token_step(c, h)), a.reps)
+            t_dec = _time(lambda: step(lambda: llm.model.decode_step(e1, c)), a.reps)
+            ms_att, live = _attention_pair(c, rnd(B, 3 * D), length + 1, a.reps)
+            r[tag] = dict(cache_len=length + 1, ms_per_token=round(t_tok, 3), ms_decode_step=round(t_dec, 3),
+                          speedup_over_full_prefill=round(t_old / t_tok, 1), attention_pair=_bw(ms_att, live),
+                          attention_share_of_decode_step=round(ms_att / t_dec, 3))
+        del c
+        torch.cuda.synchronize()
+        e0, e9 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        prompt = grown[:, :T].contiguous()
+        llm.generate(inputs_embeds=prompt, max_new_tokens=2)
+        e0.record()
+        seq = llm.generate(inputs_embeds=prompt, max_new_tokens=N)
+        e9.record()
+        torch.cuda.synchronize()
+        t_prefill = _time(lambda: llm(inputs_embeds=prompt, last_token_only=True), 2)
+        r["generate"] = dict(new_tokens=int(seq.shape[1]), ms_total=round(e0.elapsed_time(e9), 1), ms_prefill=round(t_prefill, 2),
+                             ms_per_token_after_prefill=round((e0.elapsed_time(e9) - t_prefill) / max(1, seq.shape[1] - 1), 3))
+        res[f"B{B}"] = r
+        del grown, am, prompt
+    print(json.dumps(dict(
+        workload="cfg5 LLM decode: Llama at Vicuna-7B dims, bf16, greedy, KV cache of prompt + new slots; baseline = the prefill over the grown sequence",
+        layers=a.layers, prompt=T, new_tokens=N, reps=a.reps, decode_chunk=ops.DECODE_CHUNK, results=res, peak_bytes=torch.cuda.max_memory_allocated())))
+
+
+if __name__ == "__main__":
+    main()
