@@ -15,7 +15,7 @@
 // spread over the banks.  The accumulator of the first products is the B operand of the second ones without any lane movement (the contraction
 // index sits in the registers).  Causality is in the loop bounds; only tiles on a wave's diagonal, tiles with padded keys and the last partial
 // tile apply the per-element mask.  exp2 with the scale and the lse pre-multiplied by log2(e).
-#include "common.h"
+#include "lds_mma.h"
 
 namespace {
 
@@ -23,37 +23,8 @@ constexpr int BD = 128;                  // head dim
 constexpr int BROW = BD * 2;             // bytes per row of an LDS image
 constexpr int BQ = 128;                  // rows per workgroup (4 waves x 32)
 constexpr int TILE = 32 * BROW;          // one streamed tile: 32 rows
-typedef __attribute__((ext_vector_type(4))) short short4b;
-
-__device__ inline bf16x8 pack8b(const float* p) {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16)p[i];
-    return v;
-}
 
 __device__ inline int sw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }      // chunk permutation of a row: physical chunk = logical ^ sw(row)
-
-// 16 bytes per lane, global -> LDS, destination = m0 base + lane * 16 (wave-uniform base)
-__device__ inline void dma16(const char* sbase, unsigned off, unsigned dst) {
-    unsigned keep;
-    const unsigned long long b64 = (unsigned long long)sbase;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-    const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-    const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(sb64), "s"(dst) : "memory");
-}
-__device__ inline void dma16_ptr(const void* src, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-__device__ inline void dma4_ptr(const void* src, unsigned dst) {          // 4 bytes per lane, destination = m0 base + lane * 4
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
 
 // A 32-row tile of 128-element rows (row stride ldb bytes from `base`, first row r0, rows clamped to Tn - 1) -> the swizzled image at LDS byte
 // address `dst` (wave-uniform: image base + wave * 1024): 512 pieces of 16 bytes, 2 per thread.  offs[i]: this thread's constant source offsets.
@@ -61,13 +32,13 @@ __device__ inline void stage_tile(const char* base, size_t ldb, int r0, int Tn, 
     if (r0 + 32 <= Tn) {                                                 // (uniform) all 32 rows exist
         const char* tb = base + (size_t)r0 * ldb;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(tb, offs[i], dst + i * 4096);
+        for (int i = 0; i < 2; ++i) lds_dma16_sbase(tb, offs[i], dst + i * 4096);
         return;
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int p = i * 256 + tid, row = p >> 4, c = p & 15;
-        dma16_ptr(base + (size_t)min(r0 + row, Tn - 1) * ldb + ((c ^ sw(row)) << 4), dst + i * 4096);
+        lds_dma16(base + (size_t)min(r0 + row, Tn - 1) * ldb + ((c ^ sw(row)) << 4), dst + i * 4096);
     }
 }
 
@@ -75,12 +46,7 @@ __device__ inline void stage_tile(const char* base, size_t ldb, int r0, int Tn, 
 // offsets for (d, row group) computed once (tr_offsets)
 __device__ inline bf16x8 tr_frag(const char* img, int k2, unsigned o0, unsigned o1) {
     const char* a = img + k2 * 16 * BROW;
-    const short4b lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4b*)(a + o0));
-    const short4b hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4b*)(a + o1));
-    union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi[j]; }
-    return u.v;
+    return lds_read_tr16(a + o0, a + o1);
 }
 // lane 4q+p of a 16-lane group supplies row q, columns 4p..4p+3 of its block; group g: rows 4 (g >> 1).., columns 16 (g & 1)..  (+ 8 rows for e = 1)
 __device__ inline void tr_offsets(int lane, unsigned (&toff)[4][2]) {
@@ -236,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void attn_causal_bwd_dq_kernel(const bf16* 
                 t[r] = off ? 0.f : __builtin_amdgcn_exp2f(fmaf(s[r], scale_log2e, -L2)) * (dp[r] - D);
             }
         }
-        const bf16x8 p0 = pack8b(t), p1 = pack8b(t + 8);
+        const bf16x8 p0 = pack8(t), p1 = pack8(t + 8);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
 #pragma unroll
@@ -315,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void attn_causal_bwd_dkv_kernel(const bf16*
         stage_tile(oseq + (size_t)h * BD * 2, (size_t)C * 2, r0, Tn, tid, ooffs, lds0 + dst + TILE);
         if (wave == 0) {                                                 // lanes 0-31: lse of the tile's queries, lanes 32-63: their D
             const int64_t i = ((int64_t)b * H + h) * Tn + min(r0 + (lane & 31), Tn - 1);
-            dma4_ptr((lane < 32 ? lse2 : dsum) + i, lds_base + dst + 2 * TILE);
+            lds_dma4((lane < 32 ? lse2 : dsum) + i, lds_base + dst + 2 * TILE);
         }
     };
     auto scores = [&](const char* img, const bf16x8 (&bf)[8]) {
@@ -360,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void attn_causal_bwd_dkv_kernel(const bf16*
                 ds[r] = pv * (dp[r] - d4[j]);
             }
         }
-        const bf16x8 p0 = pack8b(p), p1 = pack8b(p + 8), s0 = pack8b(ds), s1 = pack8b(ds + 8);
+        const bf16x8 p0 = pack8(p), p1 = pack8(p + 8), s0 = pack8(ds), s1 = pack8(ds + 8);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
 #pragma unroll

@@ -333,8 +333,6 @@ int decode_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, c
     return SETOK_OK;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int setok_kv_append(void* stream, int dtype, const void* qkv, void* k_cache, void* v_cache, int B, int T, int H, int Hkv, int Dh, int cap,

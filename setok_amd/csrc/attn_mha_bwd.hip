@@ -263,8 +263,6 @@ __global__ __launch_bounds__(64 * MM_WAVES) void mha_bwd_kv_mfma(const bf16* __r
         }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // SETOK_ATTN_BWD_GENERIC=1: the wave-per-row kernels for every shape (A/B runs; read per call so one process can compare the forms)
 inline bool mfma_forced_off() {
     const char* e = getenv("SETOK_ATTN_BWD_GENERIC");
@@ -295,7 +293,7 @@ extern "C" int setok_mha_bwd(void* stream, int dtype, const void* q, int64_t ldq
     const int64_t C = (int64_t)H * Dh;
     SETOK_CHECK_ARG(ldq >= C && ldkv >= C && ldo >= C && lddo >= C && lddq >= C && lddkv >= C, "setok_mha_bwd: a row stride is below H*Dh");
     SETOK_CHECK_ARG(ldq % V == 0 && ldkv % V == 0 && ldo % V == 0 && lddo % V == 0 && lddq % V == 0 && lddkv % V == 0 &&
-                    al16(q) && al16(k) && al16(v) && al16(out) && al16(dout) && al16(dq) && al16(dk) && al16(dv),
+                    aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dk) && aligned16(dv),
                     "setok_mha_bwd: operands and row strides must be 16-byte aligned");
     SETOK_CHECK_ARG((int64_t)n_segs * q_len <= INT32_MAX && (int64_t)n_segs * max_kv <= INT32_MAX, "setok_mha_bwd: too many rows");
     if (n_segs == 0) return SETOK_OK;

@@ -14,22 +14,13 @@
 //   * O^T += V^T P^T on the wave's own 128 output dims: its V slice of the key tile (32 x 256 B) is DMA'd into wave-private LDS and
 //     read back through the hardware-transposing ds_read_b64_tr_b16.
 // Segment traffic: Q, K, V read once per 32-query tile, O written once.
-#include "common.h"
+#include "lds_mma.h"
 
 namespace {
 
 constexpr int SD = 512;                 // head dim
 constexpr int WD = 128;                 // dims per wave
 constexpr int VROW = WD * 2;            // bytes per V row slice in LDS
-
-typedef __attribute__((ext_vector_type(4))) short short4v;
-
-__device__ inline bf16x8 pack8s(const float* p) {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16)p[i];
-    return v;
-}
 
 // ---- segments of more than 32 rows (the inter encoder: an image's L_i cluster tokens): one workgroup per (segment, head); query and
 //      key tiles are aligned to the segment's first row, so a segment's arithmetic never depends on where it sits in the batch ----------
@@ -72,9 +63,7 @@ __device__ __forceinline__ void attn_seg_big_segment(const bf16* __restrict__ qk
             for (int i = 0; i < 8; ++i) {
                 const int p = i * 64 + lane, key = kt * 32 + (p >> 4), c = p & 15;
                 const bf16* src = vb + (int64_t)min(key, n - 1) * ld + c * 8;
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(vlds + i * 1024) : "memory");
+                lds_dma16(src, vlds + i * 1024);
             }
             f32x16 sp;
 #pragma unroll
@@ -116,7 +105,7 @@ __device__ __forceinline__ void attn_seg_big_segment(const bf16* __restrict__ qk
 #pragma unroll
             for (int r = 0; r < 16; ++r) { t[r] = __builtin_amdgcn_exp2f(fmaf(t[r], scale_log2e, -mc)); ls += t[r]; }
             l_run += ls;
-            const bf16x8 p0 = pack8s(t), p1 = pack8s(t + 8);
+            const bf16x8 p0 = pack8(t), p1 = pack8(t + 8);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the V slice has landed (wave-private: no barrier needed)
             const char* Vw = &Vs[wave][0];
 #pragma unroll
@@ -124,12 +113,7 @@ __device__ __forceinline__ void attn_seg_big_segment(const bf16* __restrict__ qk
 #pragma unroll
                 for (int k2 = 0; k2 < 2; ++k2) {
                     const char* va = Vw + (k2 * 16 + tr_row) * VROW + (d * 32 + tr_col) * 2;
-                    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va));
-                    const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va + 8 * VROW));
-                    union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi4[j]; }
-                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
+                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(va, va + 8 * VROW), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // the transposing reads are done before the next tile's DMA lands
@@ -230,7 +214,7 @@ __global__ __launch_bounds__(256) void attn_seg_small_kernel(const bf16* __restr
 #pragma unroll
     for (int r = 0; r < 16; ++r) { t[r] = __builtin_amdgcn_exp2f(fmaf(t[r], scale_log2e, -mc)); ls += t[r]; }
     const float inv = 1.0f / (ls + __shfl_xor(ls, 32, 64));
-    const bf16x8 p0 = pack8s(t), p1 = pack8s(t + 8);
+    const bf16x8 p0 = pack8(t), p1 = pack8(t + 8);
     const char* Vw = &Vs[wave][0];
 #pragma unroll 1
     for (int w = 0; w < 4; ++w) {
@@ -239,9 +223,7 @@ __global__ __launch_bounds__(256) void attn_seg_small_kernel(const bf16* __restr
         for (int i = 0; i < 8; ++i) {
             const int p = i * 64 + lane, key = p >> 4, c = p & 15;
             const bf16* src = vb + (int64_t)min(key, n - 1) * ld + c * 8;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(src), "s"(vlds + i * 1024) : "memory");
+            lds_dma16(src, vlds + i * 1024);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         f32x16 o[4];
@@ -252,12 +234,7 @@ __global__ __launch_bounds__(256) void attn_seg_small_kernel(const bf16* __restr
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const char* va = Vw + (k2 * 16 + tr_row) * VROW + (d * 32 + tr_col) * 2;
-                const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va));
-                const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va + 8 * VROW));
-                union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi4[j]; }
-                o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
+                o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(va, va + 8 * VROW), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // reads done before the next pass's DMA overwrites the slice

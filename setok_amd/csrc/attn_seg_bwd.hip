@@ -8,19 +8,11 @@
 //   kernel KV: per 32-key tile — S and dP = dO V^T tiles with the KEY in the lane (operands swapped), P, dS; dV^T += dO^T P,
 //              dK^T += Q^T dS (dO^T and Q^T through the transposing reads).
 // With s = scale q.k:  ds = p (dp - D) scale,  dq = sum_k ds k,  dk = sum_q ds q,  dv = sum_q p do.
-#include "common.h"
+#include "lds_mma.h"
 
 namespace {
 
 constexpr int SD = 512, WD = 128, VROW = WD * 2;
-typedef __attribute__((ext_vector_type(4))) short short4v;
-
-__device__ inline bf16x8 pk8(const float* p) {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16)p[i];
-    return v;
-}
 
 // wave-private 32 x 128 slice (rows r0 + t*32 .., dims of this wave) of a row-major matrix -> LDS (8 x 1 KiB LDS-DMA pieces)
 __device__ inline void stage_slice(const bf16* base, int64_t ld, int t, int n, unsigned lds, int lane) {
@@ -28,9 +20,7 @@ __device__ inline void stage_slice(const bf16* base, int64_t ld, int t, int n, u
     for (int i = 0; i < 8; ++i) {
         const int p = i * 64 + lane, row = t * 32 + (p >> 4), c = p & 15;
         const bf16* src = base + (int64_t)min(row, n - 1) * ld + c * 8;
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(lds + i * 1024) : "memory");
+        lds_dma16(src, lds + i * 1024);
     }
 }
 
@@ -41,12 +31,7 @@ __device__ inline void acc_xT(f32x16 (&o)[4], const char* Xw, int tr_row, int tr
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
             const char* va = Xw + (k2 * 16 + tr_row) * VROW + (d * 32 + tr_col) * 2;
-            const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va));
-            const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va + 8 * VROW));
-            union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi4[j]; }
-            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
+            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(va, va + 8 * VROW), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
         }
     }
 }
@@ -173,7 +158,7 @@ __global__ __launch_bounds__(256) void attn_seg_bwd_q_kernel(const bf16* __restr
                 t[r] = p * (dv - Dq) * scale;
             }
             __syncthreads();
-            const bf16x8 p0 = pk8(t), p1 = pk8(t + 8);
+            const bf16x8 p0 = pack8(t), p1 = pack8(t + 8);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the K slice has landed (wave-private)
             acc_xT(dq, &Ks[wave][0], tr_row, tr_col, p0, p1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // reads done before the next tile's DMA
@@ -250,7 +235,7 @@ __global__ __launch_bounds__(256) void attn_seg_bwd_kv_kernel(const bf16* __rest
                 td[r] = p * (dvv - d_ws[wi]) * scale;
             }
             __syncthreads();
-            const bf16x8 p0 = pk8(tp), p1 = pk8(tp + 8), s0 = pk8(td), s1 = pk8(td + 8);
+            const bf16x8 p0 = pack8(tp), p1 = pack8(tp + 8), s0 = pack8(td), s1 = pack8(td + 8);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's Q and dO slices have landed
             acc_xT(dv, Gw, tr_row, tr_col, p0, p1);                     // dV^T += dO^T P
             acc_xT(dk, Qw, tr_row, tr_col, s0, s1);                     // dK^T += Q^T dS

@@ -11,12 +11,7 @@
 //           k-slot order of P's registers is matched by the order of the two V reads, so P needs no
 //           cross-lane movement at all).
 // HBM traffic per (image, head): read Q, K, V once, write O once — the algorithmic minimum.
-#include "common.h"
-#if defined(ATTN_NT) && (ATTN_NT & 4)     // A/B switch: the K / V staging requests as streaming loads
-#define ATTN_KV_NT " nt"
-#else
-#define ATTN_KV_NT ""
-#endif
+#include "lds_mma.h"
 
 namespace {
 
@@ -30,30 +25,12 @@ int cu_count() {                       // of the CURRENT device
     return n;
 }
 
-#ifndef ATTN_STAGE_SBASE
-#define ATTN_STAGE_SBASE 1
-#endif
-#ifndef ATTN_O_SWAP
-#define ATTN_O_SWAP 1
-#endif
-#ifndef ATTN_DEFER_MAX
-#define ATTN_DEFER_MAX 8      // round 6: the running row maximum is raised — and the 32 output accumulators rescaled — only when some row's tile maximum exceeds it by more than this many
-#endif                        // powers of two (0 = at every rise, rounds 1-5).  The branch is per WAVE: with 32 rows a tile raised SOME row's maximum almost every time, so nearly every
-                              // tile paid 16 packed multiplies + an exp; with the threshold a query tile rescales once, after its first key tile.  Probabilities then reach 2^8 instead
-                              // of 1 — nothing for an fp32 sum, a bf16 / fp16 P operand or the final division; the result's bits change within rounding.
-#ifndef ATTN_SHORT_TAIL
-#define ATTN_SHORT_TAIL 1     // 1 (round 6): a last key tile with at most 8 valid keys (T = 257 / 577: ONE — every ViT with a class token; T = 197: 5) runs a short form of
-#endif                        // the softmax step — 4 of the 16 score registers, one of the two PV k-steps — instead of exponentiating 15 masked scores per lane
+// The running row maximum is raised — and the 32 output accumulators rescaled — only when some row's tile maximum exceeds it by more than this many powers of two.  The branch
+// is per WAVE: with 32 rows a tile raised SOME row's maximum almost every time, so nearly every tile paid 16 packed multiplies + an exp; with the threshold a query tile rescales
+// once, after its first key tile.  Probabilities then reach 2^8 instead of 1 — nothing for an fp32 sum, a bf16 / fp16 P operand or the final division; the result's bits change
+// within rounding.
+constexpr int DEFER_MAX = 8;
 constexpr int ROWB = 128;              // bytes per K / V row in LDS: 64 dims; a 48-dim head leaves two 16-byte slots of each row unused
-
-typedef __attribute__((ext_vector_type(4))) short short4v;
-
-__device__ inline bf16x8 pack8(const float* p) {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16)p[i];
-    return v;
-}
 
 // CROSS = false: self-attention over a fused [q | k | v] buffer, T rows per image (the ViT tower, the Q-Former's
 // query self-attention).  CROSS = true: the Tq query rows of image b (buffer qkv, row stride ldq) attend to the ragged key
@@ -61,11 +38,7 @@ __device__ inline bf16x8 pack8(const float* p) {
 // the image's cluster tokens (module.py:283-286), the additive -10000 mask of the padded reference realised as a segment.
 // DH = 64 or 48 (the decoder's 768 / 16 heads): 48 runs three QK^T k-steps instead of four and stores 48 of the 64 output
 // columns of the two PV tiles (the LDS slots past the head hold a copy of the head's first chunk: they only reach the unstored columns).
-// HP (experiment, round 4): heads per workgroup.  HP = 2: a workgroup takes a PAIR of adjacent heads of an image — both heads' K / V
-// staged (2 x the LDS: one workgroup per CU at T = 257), a wave loads its query tile for both heads up front (a row piece of 256 contiguous
-// bytes) and runs the two heads one after the other.  Same arithmetic per (head, query tile): identical bits.  Measured slower; kept behind
-// SETOK_ATTN_HEADPAIR=1 as the evidence (docs/PERF_NOTES.md E.5).
-template <int NW, bool CROSS, int DH, int HP = 1>
+template <int NW, bool CROSS, int DH>
 __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
                                                            int T, int H, float scale_log2e, int64_t ldq,
                                                            const bf16* __restrict__ kptr, const bf16* __restrict__ vptr,
@@ -75,7 +48,7 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
     // Workgroups are dealt to the 8 XCDs round-robin by linear id.  With 8 | images all heads of one image are put on ONE XCD
     // (image b on XCD b % 8): a 48-dim head is 96 bytes of a q|k|v row, so neighbouring heads share 128-byte lines, and lines
     // fetched by one XCD's L2 are not visible to another's.
-    int h = blockIdx.x * HP, b = blockIdx.y;
+    int h = blockIdx.x, b = blockIdx.y;
     if ((gridDim.y & 7) == 0 && DH != 64) {
         const int id = blockIdx.y * gridDim.x + blockIdx.x, xcd = id & 7, k = id >> 3;
         b = xcd + 8 * (k / (int)gridDim.x);
@@ -110,39 +83,21 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
         const int r8 = lane >> 3, c8 = lane & 7, kc8 = c8 ^ r8;
         const unsigned koff = (unsigned)r8 * (unsigned)(ldk * 2) + (unsigned)((kc8 < DH / 8 ? kc8 : 0) << 4);
         const unsigned voff = (unsigned)r8 * (unsigned)(ldk * 2) + (unsigned)((c8 < DH / 8 ? c8 : 0) << 4);
-        auto dma_s = [&](const char* base, unsigned off, unsigned dst) {
-            unsigned keep;
-            const unsigned long long b64 = (unsigned long long)base;
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-            const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-            const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ATTN_KV_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(off), "s"(sb64), "s"(dst) : "memory");
-        };
-#pragma unroll
-        for (int hh = 0; hh < HP; ++hh) {
-        const bf16* kbase_h = kbase + hh * DH;
-        const bf16* vbase_h = vbase + hh * DH;
-        const unsigned ldsh = lds0 + (unsigned)hh * 2u * (unsigned)Tp * ROWB;
         for (int p0 = wave_u * 64; p0 < npieces; p0 += NW * 64) {    // this wave's 64 consecutive pieces
             const int key0 = p0 >> 3;
-            if (ATTN_STAGE_SBASE && key0 + 8 <= T) {                  // (uniform) all eight rows exist
+            if (key0 + 8 <= T) {                                      // (uniform) all eight rows exist
                 const size_t rbytes = (size_t)key0 * (size_t)(ldk * 2);
-                dma_s(reinterpret_cast<const char*>(kbase_h) + rbytes, koff, ldsh + p0 * 16);
-                dma_s(reinterpret_cast<const char*>(vbase_h) + rbytes, voff, ldsh + Tp * ROWB + p0 * 16);
+                lds_dma16_sbase(reinterpret_cast<const char*>(kbase) + rbytes, koff, lds0 + p0 * 16);
+                lds_dma16_sbase(reinterpret_cast<const char*>(vbase) + rbytes, voff, lds0 + Tp * ROWB + p0 * 16);
                 continue;
             }
             const int p = p0 + lane, key = p >> 3, c = p & 7;
             const int64_t roff = (int64_t)min(key, T - 1) * ldk;
             const int kc = c ^ (key & 7);                               // physical slot c of row `key` holds logical chunk c ^ (key & 7)
-            const bf16* ksrc = kbase_h + roff + ((kc < DH / 8 ? kc : 0) << 3);   // chunks past the head are never read back: fetch something valid
-            const bf16* vsrc = vbase_h + roff + ((c < DH / 8 ? c : 0) << 3);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ATTN_KV_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(ksrc), "s"(ldsh + p0 * 16) : "memory");
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ATTN_KV_NT "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(vsrc), "s"(ldsh + Tp * ROWB + p0 * 16) : "memory");
-        }
+            const bf16* ksrc = kbase + roff + ((kc < DH / 8 ? kc : 0) << 3);   // chunks past the head are never read back: fetch something valid
+            const bf16* vsrc = vbase + roff + ((c < DH / 8 ? c : 0) << 3);
+            lds_dma16(ksrc, lds0 + p0 * 16);
+            lds_dma16(vsrc, lds0 + Tp * ROWB + p0 * 16);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -150,7 +105,7 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
 
     const int qi = lane & 31, hi = lane >> 5;
     const int nq = (Tq + 31) >> 5, nkv = Tp >> 5;
-    const float defer_raw = (float)ATTN_DEFER_MAX / scale_log2e;        // the threshold in raw score units
+    const float defer_raw = (float)DEFER_MAX / scale_log2e;        // the threshold in raw score units
     // transposing-read address pattern: lanes 4j+p of a 16-lane group supply row j, 4-column piece p
     const int g16 = lane >> 4, i16 = lane & 15;
     const int tr_row = (i16 >> 2) + 4 * (g16 >> 1);            // + 4*hi
@@ -168,23 +123,11 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
         const int q = qt * 32 + qi;
         const bf16* qp = base + (int64_t)min(q, Tq - 1) * ld + hi * 8;
         constexpr int NKS = DH / 16;
-        bf16x8 qfh[HP][NKS];
+        bf16x8 qf[NKS];
 #pragma unroll
-        for (int hh = 0; hh < HP; ++hh)
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-#if defined(ATTN_NT) && (ATTN_NT & 2)
-                qfh[hh][ks] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(qp + hh * DH + ks * 16));     // A/B: read-once rows as streaming loads
-#else
-                qfh[hh][ks] = *reinterpret_cast<const bf16x8*>(qp + hh * DH + ks * 16);
-#endif
-            }
-#pragma unroll
-        for (int hh = 0; hh < HP; ++hh) {
-        const bf16x8 (&qf)[NKS] = qfh[hh];
-        const char* Ks = lds + (size_t)hh * 2 * Tp * ROWB;
+        for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
+        const char* Ks = lds;
         const char* Vs = Ks + (size_t)Tp * ROWB;
-        const int hcur = h + hh;
 
         f32x16 o[2];
 #pragma unroll
@@ -208,7 +151,8 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
             float t[16];
             float mx = -INFINITY;
             const bool tail = (kt == nkv - 1) && (Tp != T);
-#if ATTN_SHORT_TAIL
+            // A last key tile with at most 8 valid keys (T = 257 / 577: ONE — every ViT with a class token; T = 197: 5) runs a short form of the softmax step — 4 of the 16
+            // score registers, one of the two PV k-steps — instead of exponentiating 15 masked scores per lane.
             if (tail && T - kt * 32 <= 8) {               // (wave-uniform)
                 // The tile's valid keys are kt * 32 + r + 4 hi, r = 0 .. 3 (registers 0-3 of the score tile): the other twelve registers hold masked scores whose
                 // probabilities are exactly 0 — the general form below exponentiates them, adds the zeros to the row sum and multiplies V's rows 16-31 by them.
@@ -219,7 +163,7 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
                 for (int r = 0; r < 4; ++r) { t[r] = (r + 4 * hi < nvalid) ? s[r] : -INFINITY; mx = fmaxf(mx, t[r]); }
                 mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
                 const float m_new = fmaxf(m_run, mx);
-                if (ATTN_DEFER_MAX ? __any(mx > m_run + defer_raw) : !__all(m_new == m_run)) {
+                if (__any(mx > m_run + defer_raw)) {
                     const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
                     l_run *= alpha;
 #pragma unroll
@@ -239,16 +183,10 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
 #pragma unroll
                 for (int d = 0; d < 2; ++d) {
                     const char* vb = Vs + (kt * 32 + tr_row) * ROWB + (d * 32 + tr_col) * 2;
-                    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(vb));
-                    const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(vb + 8 * ROWB));
-                    union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi4[j]; }
-                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, p0, o[d], 0, 0, 0);
+                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(vb, vb + 8 * ROWB), p0, o[d], 0, 0, 0);
                 }
                 continue;
             }
-#endif
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 t[r] = s[r];
@@ -257,7 +195,7 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             const float m_new = fmaxf(m_run, mx);
-            if (ATTN_DEFER_MAX ? __any(mx > m_run + defer_raw) : !__all(m_new == m_run)) {      // wave-uniform (see ATTN_DEFER_MAX)
+            if (__any(mx > m_run + defer_raw)) {                // wave-uniform (see DEFER_MAX)
                 const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
                 l_run *= alpha;
 #pragma unroll
@@ -277,18 +215,13 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
 #pragma unroll
                 for (int k2 = 0; k2 < 2; ++k2) {
                     const char* vb = Vs + (kt * 32 + k2 * 16 + tr_row) * ROWB + (d * 32 + tr_col) * 2;
-                    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(vb));
-                    const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(vb + 8 * ROWB));
-                    union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi4[j]; }
-                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
+                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(vb, vb + 8 * ROWB), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
                 }
             }
         }
         const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
         const float inv = 1.0f / l_tot;
-        if constexpr (!CROSS && DH == 64 && ATTN_O_SWAP) {
+        if constexpr (!CROSS && DH == 64) {
             // The lane pair (q, q + 32) holds the query's 64 output dims in alternating 4-dim chunks (chunk j = d * 4 + r4: dims 8 j + 4 hi .. + 3).
             // One v_permlane32_swap per register exchanges the upper lanes' chunk j with the lower lanes' chunk j + 4: afterwards lane q owns dims
             // 0-31 and lane q + 32 dims 32-63 in 16-byte pieces — 4 stores of 16 bytes per lane instead of 8 of 8.
@@ -311,20 +244,15 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
                     cw[j][w] = r[0]; cw[j + 4][w] = r[1];
                 }
             if (q < Tq) {
-                bf16* op = out + ((int64_t)b * Tq + q) * (int64_t)C + hcur * DH + hi * 32;
+                bf16* op = out + ((int64_t)b * Tq + q) * (int64_t)C + h * DH + hi * 32;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const uint4 piece = {cw[j][0], cw[j][1], cw[j + 4][0], cw[j + 4][1]};
-#if defined(ATTN_NT) && (ATTN_NT & 1)
-                    { typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-                      __builtin_nontemporal_store(u32x4_t{piece.x, piece.y, piece.z, piece.w}, reinterpret_cast<u32x4_t*>(op + 8 * j)); }                                 // A/B: streaming stores of the output rows
-#else
                     *reinterpret_cast<uint4*>(op + 8 * j) = piece;
-#endif
                 }
             }
         } else if (q < Tq) {
-            bf16* op = out + ((int64_t)b * Tq + q) * (CROSS ? ldo : (int64_t)C) + hcur * DH;
+            bf16* op = out + ((int64_t)b * Tq + q) * (CROSS ? ldo : (int64_t)C) + h * DH;
 #pragma unroll
             for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -336,7 +264,6 @@ __global__ __launch_bounds__(NW * 64) void attn_vit_kernel(const bf16* __restric
                     *reinterpret_cast<bf16x4*>(op + d * 32 + 8 * r4 + 4 * hi) = v;   // dims (r&3) + 8*(r>>2) + 4*hi
                 }
         }
-        }                                                            // hh
     }
 }
 
@@ -385,32 +312,20 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_vit_row16_kernel(const bf16* 
         const unsigned koff0 = rowoff + (unsigned)((c8 ^ (r8 >> 1)) << 4);                   // rows 16 k .. + 7:  (row >> 1) & 7 = r8 >> 1
         const unsigned koff1 = rowoff + (unsigned)((c8 ^ (4 + (r8 >> 1))) << 4);             // rows 16 k + 8 .. + 15
         const unsigned voff = rowoff + (unsigned)((c8 ^ ((r8 >> 1) << 1)) << 4);
-        auto dma_s = [&](const char* src, unsigned off, unsigned dst) {
-            unsigned keep;
-            const unsigned long long b64 = (unsigned long long)src;
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-            const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-            const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(off), "s"(sb64), "s"(dst) : "memory");
-        };
         for (int req = wave_u; req < Tp / 8; req += NW) {
             const int key0 = req * 8;
             if (key0 + 8 <= T) {
                 const size_t rbytes = (size_t)key0 * (size_t)(ld * 2);
-                dma_s(reinterpret_cast<const char*>(kbase) + rbytes, (req & 1) ? koff1 : koff0, lds0 + req * 1024);
-                dma_s(reinterpret_cast<const char*>(vbase) + rbytes, voff, lds0 + Tp * ROWB + req * 1024);
+                lds_dma16_sbase(reinterpret_cast<const char*>(kbase) + rbytes, (req & 1) ? koff1 : koff0, lds0 + req * 1024);
+                lds_dma16_sbase(reinterpret_cast<const char*>(vbase) + rbytes, voff, lds0 + Tp * ROWB + req * 1024);
                 continue;
             }
             const int key = key0 + r8;                                          // a request reaching past row T - 1: padding rows re-read row T - 1
             const int64_t roff = (int64_t)min(key, T - 1) * ld;
             const bf16* ksrc = kbase + roff + ((c8 ^ ((key >> 1) & 7)) << 3);
             const bf16* vsrc = vbase + roff + ((c8 ^ (((key >> 1) & 3) << 1)) << 3);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(ksrc), "s"(lds0 + req * 1024) : "memory");
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(vsrc), "s"(lds0 + Tp * ROWB + req * 1024) : "memory");
+            lds_dma16(ksrc, lds0 + req * 1024);
+            lds_dma16(vsrc, lds0 + Tp * ROWB + req * 1024);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -485,6 +400,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_vit_row16_kernel(const bf16* 
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const char* vb = Vs + (m * 32 + tr_row) * ROWB + (((2 * t + tr_sub) ^ tr_sw) << 4) + tr_b8;
+                // (the shared lds_read_tr16 glues the halves through a union; here that form schedules pass 1's K reads differently, so this kernel keeps the shuffle)
                 const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(vb));
                 const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(vb + 16 * ROWB));
                 typedef short short8v __attribute__((ext_vector_type(8)));
@@ -540,30 +456,7 @@ int launch(hipStream_t s, const bf16* qkv, bf16* out, int n_imgs, int T, int H, 
     static SetokDeviceOnce once;                   // one per instantiation; per device inside
     if (!once.run([] { return hipFuncSetAttribute((const void*)attn_vit_kernel<NW, false, DH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }))
         return setok_fail(SETOK_ELAUNCH, "attn_vit: cannot raise dynamic LDS limit");
-    // few (image, head) pairs: split the query tiles of a pair over QS workgroups so that the launch reaches ~2 workgroups per CU (SETOK_ATTN_QSPLIT=n forces n)
-    const int nq = (T + 31) >> 5;
-    int qs = 1;
-    {
-        const char* e = getenv("SETOK_ATTN_QSPLIT");            // (read per call: tests compare the forms in one process)
-        const int forced = e ? atoi(e) : 0;
-        const int pairs = H * n_imgs, slots = 2 * cu_count();
-        if (forced > 0) qs = forced;
-        else if (pairs * 4 <= slots) qs = slots / pairs;
-        if (qs > nq) qs = nq;
-        if (qs < 1) qs = 1;
-    }
-    if constexpr (DH == 64 && NW == 8) {                             // experiment: a workgroup per (image, PAIR of heads)
-        const char* hp = getenv("SETOK_ATTN_HEADPAIR");
-        if (hp && hp[0] == '1' && H % 2 == 0 && 2 * smem <= 160 * 1024) {
-            static SetokDeviceOnce once2;
-            if (!once2.run([] { return hipFuncSetAttribute((const void*)attn_vit_kernel<NW, false, DH, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; }))
-                return setok_fail(SETOK_ELAUNCH, "attn_vit: cannot raise dynamic LDS limit");
-            attn_vit_kernel<NW, false, DH, 2><<<dim3(H / 2, n_imgs, qs), NW * 64, 2 * smem, s>>>(qkv, out, T, H, scale * 1.44269504088896340736f, 0, nullptr, nullptr,
-                                                                                         0, nullptr, 0, 0);
-            SETOK_CHECK_LAUNCH("setok_attention(vit bf16, head pairs)");
-            return SETOK_OK;
-        }
-    }
+    const int qs = split_for(H * n_imgs, (T + 31) >> 5);
     attn_vit_kernel<NW, false, DH><<<dim3(H, n_imgs, qs), NW * 64, smem, s>>>(qkv, out, T, H, scale * 1.44269504088896340736f, 0, nullptr, nullptr,
                                                                           0, nullptr, 0, 0);
     SETOK_CHECK_LAUNCH("setok_attention(vit bf16)");

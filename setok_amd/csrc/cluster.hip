@@ -11,7 +11,7 @@
 // - 2 a.b, 0)) / sqrt(C)  (torch.cdist's matmul form, :82), density = exp(-mean_k(d^2)) (:90),
 // mask[i,j] = rho_j > rho_i and the row-j-max quirk (:96-99), score = delta * rho (:101), first-min
 // argmin over centre rows (:111-113), centres own themselves (:117-119).
-#include "common.h"
+#include "lds_mma.h"
 #include <atomic>
 #include <stdlib.h>
 #include <math.h>
@@ -60,17 +60,12 @@ __global__ __launch_bounds__(256, 2) void dpc_gram_bf16_kernel(const bf16* __res
         b_src[i] = Xb + (int64_t)min(c0 + row, N - 1) * C + kc * 8;
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem) + wave * 1024;
-    auto dma16 = [&](const bf16* ptr, unsigned lds_dst) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(ptr), "s"(lds_dst) : "memory");
-    };
     auto issue = [&](int stage, int k0) {
         const unsigned sb = lds0 + stage * GR_STAGE;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(a_src[i] + k0, sb + i * 4096);
+        for (int i = 0; i < 2; ++i) lds_dma16(a_src[i] + k0, sb + i * 4096);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dma16(b_src[i] + k0, sb + GR_BOFF + i * 4096);
+        for (int i = 0; i < 8; ++i) lds_dma16(b_src[i] + k0, sb + GR_BOFF + i * 4096);
     };
 
     f32x16 acc[2][2];
@@ -231,20 +226,11 @@ __global__ __launch_bounds__(512) void dpc_fused_kernel(FArgs g) {
         src_off[i] = (unsigned)min(row, N - 1) * (unsigned)(g.C * 2) + kc * 16;
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem) + wave * 1024;
-    auto dma16 = [&](const char* base, unsigned off, unsigned lds_dst) {
-        unsigned keep;
-        const unsigned long long b64 = (unsigned long long)base;
-        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-        const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-        const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(sb64), "s"(lds_dst) : "memory");
-    };
     auto issue = [&](int kt) {
         const unsigned sb = lds0 + (kt % F_NST) * F_STAGE;
         const char* base = reinterpret_cast<const char*>(Xb) + (size_t)kt * 128;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(base, src_off[i], sb + i * 8192);
+        for (int i = 0; i < 4; ++i) lds_dma16_sbase(base, src_off[i], sb + i * 8192);
     };
 
     f32x4 acc[2][16];
@@ -707,27 +693,18 @@ __global__ __launch_bounds__(512) void dpc_strip_kernel(SArgs g) {
         // the wave-uniform base; only when N < 576 the last pieces' rows are clamped to N - 1 (per-lane offsets, computed on the fly).
         const int prow = tid >> 3;
         const unsigned poff = (unsigned)prow * (unsigned)(g.C * 2) + (unsigned)(((tid & 7) ^ f_swz(prow)) << 4);
-        auto dma16 = [&](const char* base, unsigned off, unsigned lds_dst) {
-            unsigned keep;
-            const unsigned long long b64 = (unsigned long long)base;
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-            const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-            const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(off), "s"(sb64), "s"(lds_dst) : "memory");
-        };
         const bool full = N == SN;                          // uniform
         auto issue = [&](int kt) {
             const unsigned sb = lds0 + (kt & 1) * S_STAGE;
             const char* base = reinterpret_cast<const char*>(Xb) + (size_t)kt * 128;
             if (full) {
 #pragma unroll 1
-                for (int i = 0; i < 9; ++i) dma16(base + (size_t)i * 64 * (size_t)(g.C * 2), poff, sb + i * 8192);
+                for (int i = 0; i < 9; ++i) lds_dma16_sbase(base + (size_t)i * 64 * (size_t)(g.C * 2), poff, sb + i * 8192);
             } else {
 #pragma unroll 1
                 for (int i = 0; i < 9; ++i) {
                     const unsigned off = (unsigned)min(prow + 64 * i, N - 1) * (unsigned)(g.C * 2) + (unsigned)(((tid & 7) ^ f_swz(prow)) << 4);
-                    dma16(base, off, sb + i * 8192);
+                    lds_dma16_sbase(base, off, sb + i * 8192);
                 }
             }
         };

@@ -48,6 +48,7 @@ int setok_fail(int code, const char* fmt, ...);
     } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }      // what every 16-byte vector access and LDS-DMA request needs of a pointer
 
 // one entry point, two element types: the 16-bit type of the build (SETOK_BF16) or fp32
 #define DISPATCH_T(NAME, CALL_BF16, CALL_F32)                                  \

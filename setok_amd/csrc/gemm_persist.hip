@@ -4,7 +4,7 @@
 //   to bf16 first, then the residual is added and the sum rounded again)
 //
 // One workgroup (8 waves, 2 per SIMD) per CU walks output tiles of 256 x 256:
-//   * operands go HBM/L2 -> LDS with global_load_lds_dwordx4 (no VGPR round trip), every one issued from inline asm so that
+//   * operands go HBM/L2 -> LDS with global_load_lds_dwordx4 (no VGPR round trip), every one issued from inline asm (lds_mma.h) so that
 //     no wait in the kernel is the compiler's guess.  The LDS image is lane-linear, so the 16-B-slot XOR swizzle is applied to
 //     the per-lane SOURCE address and to the ds_read_b128 address.  Two 64 KiB stages.
 //   * the K-tiles of consecutive output tiles form ONE continuous stream: while the last K-tile of a tile is multiplied, the
@@ -23,7 +23,7 @@
 // The chip is POWER-bound on this kernel (measured with rocm-smi under load: 1.37-1.38 kW of the 1.4 kW cap, sclk 1.73-1.95 GHz on
 // random operands vs 2.39 GHz / 0.95 kW on all-zero operands), so removing stall cycles converts only partly into speed: the
 // tile-boundary change above cut 9 % of the cycles per tile and 3 % of the time.
-#include "common.h"
+#include "lds_mma.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -163,21 +163,12 @@ __global__ __launch_bounds__(512) void gemm_persist_kernel(PArgs g) {
         }
     };
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem) + wave * 1024;
-    auto dma16 = [&](const char* base, unsigned off, unsigned lds_dst) {
-        unsigned keep;
-        const unsigned long long b64 = (unsigned long long)base;
-        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);          // (readfirstlane returns int: widen as unsigned)
-        const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-        const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(sb64), "s"(lds_dst) : "memory");
-    };
     auto issue_ktile = [&](int stage, int k0) {                      // a whole K-tile at once (tile boundaries only)
         const unsigned sb = lds0 + stage * STAGE;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(a_base + k0 * 2, a_off[i], sb + i * 8192);
+        for (int i = 0; i < 4; ++i) lds_dma16_sbase(a_base + k0 * 2, a_off[i], sb + i * 8192);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(b_base + k0 * 2, b_off[i], sb + BOFF + i * 8192);
+        for (int i = 0; i < 4; ++i) lds_dma16_sbase(b_base + k0 * 2, b_off[i], sb + BOFF + i * 8192);
     };
 
     // The bias of a tile is fetched ONE TILE AHEAD (4 floats per lane: columns j * 16 + (lane & 15) of the wave's 64), before the previous
@@ -279,8 +270,8 @@ __global__ __launch_bounds__(512) void gemm_persist_kernel(PArgs g) {
                         if (LOAD && ks == 0) {
                             if (do_load) {
                                 __builtin_amdgcn_sched_barrier(0);
-                                if (half == 0) dma16(a_base + k_next * 2, a_off[t], sb + t * 8192);
-                                else dma16(b_base + k_next * 2, b_off[t], sb + BOFF + t * 8192);
+                                if (half == 0) lds_dma16_sbase(a_base + k_next * 2, a_off[t], sb + t * 8192);
+                                else lds_dma16_sbase(b_base + k_next * 2, b_off[t], sb + BOFF + t * 8192);
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                         }
@@ -553,18 +544,13 @@ __device__ __forceinline__ void gemm_tail_tile(const PArgs& g, const int tile, c
         b_src[i] = g.W + (int64_t)min(n0 + row, g.N - 1) * g.K + kc * 8;
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem) + wave * 1024;
-    auto dma16 = [&](const bf16* ptr, unsigned lds_dst) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(ptr), "s"(lds_dst) : "memory");
-    };
     auto issue = [&](int kt) {                              // LPT loads per lane per K-tile
         const unsigned sb = lds0 + (kt % NS) * STG;
         const int k0 = kt * TK;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) dma16(a_src[i] + k0, sb + i * 4096);
+        for (int i = 0; i < NI; ++i) lds_dma16(a_src[i] + k0, sb + i * 4096);
 #pragma unroll
-        for (int i = 0; i < NJ; ++i) dma16(b_src[i] + k0, sb + TTM * TK * 2 + i * 4096);
+        for (int i = 0; i < NJ; ++i) lds_dma16(b_src[i] + k0, sb + TTM * TK * 2 + i * 4096);
     };
     // The K loop used to be latency-serial per K-tile (4 waves, one per SIMD: counted wait -> barrier release ~80 cycles -> ds_read latency -> a
     // handful of MFMAs): ~590 cycles per K-tile at the 32 x 32 shape against 64 of MFMA issue — and the launches of one image are exactly this loop
@@ -860,15 +846,6 @@ __device__ __forceinline__ void gemm_pp_body(const PArgs& g, char* smem) {
     const unsigned a_off = (unsigned)prow * (unsigned)(g.lda * 2) + kc16;
     const unsigned w_off = (unsigned)prow * (unsigned)(g.K * 2) + kc16;
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem) + wave * 1024;
-    auto dma16 = [&](const char* base, unsigned off, unsigned lds_dst) {
-        unsigned keep;
-        const unsigned long long b64 = (unsigned long long)base;
-        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-        const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-        const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(sb64), "s"(lds_dst) : "memory");
-    };
     int m0, n0, nm0 = 0, nn0 = 0, round = 0;
     if (!tile_of(0, m0, n0)) return;
     bool has_next = tile_of(1, nm0, nn0);
@@ -889,12 +866,12 @@ __device__ __forceinline__ void gemm_pp_body(const PArgs& g, char* smem) {
         const unsigned sb = lds0 + stage * STAGE + (q >> 1) * BOFF + (q & 1) * QT;
         if (q >> 1) {
             const char* base = wt + (q & 1) * w_half + (size_t)u * 128;
-            dma16(base, w_off, sb);
-            dma16(base + w_piece, w_off, sb + 8192);
+            lds_dma16_sbase(base, w_off, sb);
+            lds_dma16_sbase(base + w_piece, w_off, sb + 8192);
         } else {
             const char* base = at + (q & 1) * a_half + (size_t)u * 128;
-            dma16(base, a_off, sb);
-            dma16(base + a_piece, a_off, sb + 8192);
+            lds_dma16_sbase(base, a_off, sb);
+            lds_dma16_sbase(base + a_piece, a_off, sb + 8192);
         }
     };
     // ... of the CURRENT tile's K-tile u; u >= nk runs into the next tile's K-tile u - nk (the stream does not stop at tile boundaries)

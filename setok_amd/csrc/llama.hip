@@ -6,7 +6,7 @@
 //   setok_swiglu            act_fn(gate) * up on a fused [gate | up] buffer
 //   setok_attention_causal  causal + key-padding-masked attention over uniform sequences: MFMA kernel for bf16 / head dim 128 (keys and
 //                           values streamed through LDS in tiles of 32, online softmax in registers), generic wave-per-row kernel otherwise
-#include "common.h"
+#include "lds_mma.h"
 
 namespace {
 
@@ -191,14 +191,6 @@ __global__ __launch_bounds__(64) void attn_causal_generic_kernel(const T* __rest
 constexpr int CD = 128;                  // head dim
 constexpr int CROW = CD * 2;             // bytes per K / V row in LDS
 constexpr int CQ = 128;                  // queries per workgroup (4 waves x 32)
-typedef __attribute__((ext_vector_type(4))) short short4v;
-
-__device__ inline bf16x8 pack8c(const float* p) {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16)p[i];
-    return v;
-}
 
 __global__ __launch_bounds__(256) void attn_causal_kernel(const bf16* __restrict__ qkv, const uint8_t* __restrict__ kmask, bf16* __restrict__ out,
                                                           int Tn, int H, int Hkv, float scale_log2e) {
@@ -244,22 +236,13 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const bf16* __restrict
         koffs[i] = (unsigned)row * (unsigned)(ld * 2) + (unsigned)((c ^ (row & 15)) << 4);
         voffs[i] = (unsigned)row * (unsigned)(ld * 2) + (unsigned)(c << 4);
     }
-    auto dma_sb = [&](const char* sbase, unsigned off, unsigned dst) {
-        unsigned keep;
-        const unsigned long long b64 = (unsigned long long)sbase;
-        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b64);
-        const unsigned hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
-        const unsigned long long sb64 = (unsigned long long)lo | ((unsigned long long)hi32 << 32);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(sb64), "s"(dst) : "memory");
-    };
     auto stage = [&](int kt, int buf) {                                  // K and V tile kt -> LDS buffer buf: 512 pieces of 16 B each, 2 per thread
         if (kt * 32 + 32 <= Tn) {                                        // (uniform) all 32 rows exist
             const char* tb = reinterpret_cast<const char*>(base) + (size_t)kt * 32 * (size_t)(ld * 2);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                dma_sb(tb + KO * 2, koffs[i], klds + buf * (32 * CROW) + i * 4096);
-                dma_sb(tb + VO * 2, voffs[i], vlds + buf * (32 * CROW) + i * 4096);
+                lds_dma16_sbase(tb + KO * 2, koffs[i], klds + buf * (32 * CROW) + i * 4096);
+                lds_dma16_sbase(tb + VO * 2, voffs[i], vlds + buf * (32 * CROW) + i * 4096);
             }
             return;
         }
@@ -269,11 +252,8 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const bf16* __restrict
             const bf16* src = base + (int64_t)min(kt * 32 + row, Tn - 1) * ld;
             const bf16* ksrc = src + KO + ((c ^ (row & 15)) << 3);       // physical slot c of a row holds logical chunk c ^ (row & 15)
             const bf16* vsrc = src + VO + (c << 3);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(ksrc), "s"(klds + buf * (32 * CROW) + i * 4096) : "memory");
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(vsrc), "s"(vlds + buf * (32 * CROW) + i * 4096) : "memory");
+            lds_dma16(ksrc, klds + buf * (32 * CROW) + i * 4096);
+            lds_dma16(vsrc, vlds + buf * (32 * CROW) + i * 4096);
         }
     };
     stage(0, 0);
@@ -334,19 +314,14 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const bf16* __restrict
         for (int r = 0; r < 16; ++r) { t[r] = t[r] <= NEG ? 0.f : __builtin_amdgcn_exp2f(fmaf(t[r], scale_log2e, -mc)); ls += t[r]; }
         }
         l_run += ls;
-        const bf16x8 p0 = pack8c(t), p1 = pack8c(t + 8);
+        const bf16x8 p0 = pack8(t), p1 = pack8(t + 8);
         const char* Vb = &Vs[buf][0];
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const char* va = Vb + (k2 * 16 + tr_row) * CROW + (d * 32 + tr_col) * 2;
-                const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va));
-                const short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(va + 8 * CROW));
-                union { short s8[8]; bf16x8 v; } u;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { u.s8[j] = lo[j]; u.s8[4 + j] = hi4[j]; }
-                o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u.v, k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
+                o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(va, va + 8 * CROW), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
             }
         }
     }

@@ -738,8 +738,6 @@ def test_vit_attention_query_split_keeps_its_bits(T, B):
         for qs in (1, 2, 5, 64):
             assert torch.equal(form(lambda: _with_env("SETOK_ATTN_QSPLIT", str(qs), run)), auto), (row, qs)
         assert _rel_err(auto.float().cpu(), ref) < 2e-2                    # and they are the right bits
-        if row is None:                                                    # the head-pair experiment (a workgroup per pair of adjacent heads of the online kernel): same bits
-            assert torch.equal(form(lambda: _with_env("SETOK_ATTN_HEADPAIR", "1", run)), auto)
 
 
 def test_vit_attention_row_kernel_is_batch_invariant_and_closer_to_fp32():
