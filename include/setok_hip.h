@@ -40,7 +40,8 @@ extern "C" {
 #define SETOK_ABI_VERSION 9
 
 enum { SETOK_F32 = 0, SETOK_BF16 = 1, SETOK_F16 = 2 };
-enum { SETOK_ACT_NONE = 0, SETOK_ACT_QUICK_GELU = 1, SETOK_ACT_GELU_ERF = 2 };
+enum { SETOK_ACT_NONE = 0, SETOK_ACT_QUICK_GELU = 1, SETOK_ACT_GELU_ERF = 2,
+       SETOK_ACT_SILU = 3 /* x * sigmoid(x): setok_activation only; setok_linear / setok_linear_ln / setok_activation_dropout refuse it */ };
 enum { SETOK_OK = 0, SETOK_EINVAL = -1, SETOK_ELAUNCH = -2, SETOK_EUNSUPPORTED = -3 };
 
 int setok_abi_version(void);
@@ -146,7 +147,8 @@ int setok_layernorm(void* stream, int dtype, const void* x, const float* gamma, 
                     void* y, int rows, int C, float eps);
 
 /* y = act(x) elementwise (n elements) — nn.GELU placed after a LayerNorm in the `mlp{N}x_gelu_Norm`
- * projector (multimodal_projector/builder.py:48-58), where it cannot be fused into a GEMM epilogue. */
+ * projector (multimodal_projector/builder.py:48-58), where it cannot be fused into a GEMM epilogue; SETOK_ACT_SILU: the nn.SiLU inside
+ * TimestepEmbedder.mlp and ResBlock.mlp of the DiffLoss head (loss/diffloss.py:67,115). */
 int setok_activation(void* stream, int dtype, const void* x, void* y, int64_t n, int act);
 
 /* Training-mode dropout of the head's Block: nn.Dropout(proj_drop) after the attention projection (module.py:59,72), after the Mlp's activation
@@ -503,6 +505,46 @@ int setok_attention_decode_gqa(void* stream, int dtype, const void* q, int64_t l
  * out[r] (int64) = the LOWEST index of the maximum of row r of x (rows x V in `dtype`, row stride ld elements, any alignment, V = 32003 included);
  * a NaN counts as the maximum.  Deterministic. */
 int setok_argmax_rows(void* stream, int dtype, const void* x, int64_t ld, int rows, int V, int64_t* out);
+
+/* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
+ * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest
+ * (csrc/diffusion.hip).  Every entry is asynchronous on `stream`, allocates nothing, synchronises nothing, accepts rows == 0, uses 16-byte
+ * accesses (row lengths % 8 == 0, operands and row strides 16-byte aligned), one wave per row, fp32 arithmetic, no atomics; a row's bits depend
+ * on that row's operands alone.  Pure additions: the ABI version stays 9. */
+
+/* TimestepEmbedder.timestep_embedding (diffloss.py:73-91): emb[r, j] = cos(t[r] * f_j), emb[r, half + j] = sin(t[r] * f_j) for j < half = dim / 2,
+ * f_j = exp(-ln(max_period) * j / half) — fp32 arguments and the accurate cosf / sinf (the arguments reach 999 rad), rounded to `dtype` once.
+ * t: fp32 (rows,) on the device; emb: (rows, dim); dim % 16 == 0. */
+int setok_timestep_embedding(void* stream, int dtype, const float* t, void* emb, int rows, int dim, float max_period);
+
+/* y[r, :] = SiLU(a[r, :] + b[r * ldb + :]): the `y = t + c` of SimpleMLPAdaLN.forward (diffloss.py:229) with the nn.SiLU every adaLN_modulation
+ * starts with (:120,140) applied once for all of them.  ldb = 0 broadcasts ONE row b (the sampler: one timestep for all rows). rows x C. */
+int setok_add_silu(void* stream, int dtype, const void* a, const void* b, int64_t ldb, void* y, int rows, int C);
+
+/* One launch per ResBlock boundary (diffloss.py:124-128,144-148):
+ *     if h:  x[r, :] <- x[r, :] + gate[r, :] * h[r, :]                         (the previous block's gated residual, written back in place)
+ *     y[r, :] = LayerNorm(x[r, :]; gamma, beta, eps) * (1 + scale[r, :]) + shift[r, :]     (modulate(in_ln(x), shift, scale))
+ * gamma / beta: fp32 (C,), both NULL for a LayerNorm without affine (FinalLayer.norm_final).  shift, scale, gate: column windows of ONE wider
+ * row-major buffer of `dtype` — each a pointer to its first column, with the buffer's row stride ldm (elements) — so the output of the fused
+ * adaLN_modulation GEMM is consumed in place, without `chunk` copies.  h, gate: both NULL (no residual) or both given.  x, h, y: rows x C
+ * contiguous; y must not alias x.  Two-pass fp32 statistics of the STORED (rounded) x; one rounding to `dtype` per output. */
+int setok_adaln_modulate(void* stream, int dtype, void* x, const void* h, const void* gate, const float* gamma, const float* beta,
+                         const void* shift, const void* scale, int64_t ldm, void* y, int rows, int C, float eps);
+
+/* One reverse step of the sampler: GaussianDiffusion.p_mean_variance + p_sample (gaussian_diffusion.py:285-339,404-419; EPSILON mean type,
+ * LEARNED_RANGE variance, clip_denoised = False) on the net's output `out` (rows x 2C, row stride ldo, element type out_dtype = `dtype` or SETOK_F32):
+ *     eps    = out[r, :C]                                  (half == 0)
+ *            = u + cfg_scale * (c - u),  c = out[r mod half, :C],  u = out[r mod half + half, :C]      (half > 0: rows == 2 * half, forward_with_cfg)
+ *     v      = out[r, C:2C]
+ *     x0     = sqrt_recip * x[r] - sqrt_recipm1 * eps;    mean = coef1 * x0 + coef2 * x[r]
+ *     logvar = f * max_log + (1 - f) * min_log,  f = (v + 1) / 2
+ *     x[r]  <- mean + nonzero * exp(0.5 * logvar) * noise[r mod noise_rows] * temperature
+ * x: fp32 (rows, C), updated in place — the sampler's state stays fp32 in every dtype mode; noise: fp32 (noise_rows, C), noise_rows = rows or, with one draw
+ * shared by both halves, half.  nonzero = 0 at the last step makes the noise term exactly 0 for finite noise.  x_in: (rows, C) in `dtype`, the next
+ * evaluation's input_proj operand: row r gets the new x[r] (half == 0) or the new x[r mod half] (the conditional half duplicated). */
+int setok_ddpm_step(void* stream, int dtype, int out_dtype, const void* out, int64_t ldo, float* x, const float* noise, int noise_rows, void* x_in,
+                    int rows, int C, int half, float cfg_scale, float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, float min_log,
+                    float max_log, float nonzero, float temperature);
 
 #ifdef __cplusplus
 }

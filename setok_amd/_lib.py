@@ -25,7 +25,7 @@ class _HalfCode(int):
 F32, BF16 = 0, 1
 F16 = _HalfCode(2)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1, 2
+ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF, ACT_SILU = 0, 1, 2, 3
 
 class SetokConfig(C.Structure):
     """`setok_config` of include/setok_hip.h, field for field."""
@@ -105,6 +105,10 @@ SIGNATURES = {
     "setok_kv_append": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_argmax_rows": [_vp, _i, _vp, _i64, _i, _i, _vp],
+    "setok_timestep_embedding": [_vp, _i, _vp, _vp, _i, _i, _f],
+    "setok_add_silu": [_vp, _i, _vp, _vp, _i64, _vp, _i, _i],
+    "setok_adaln_modulate": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _f],
+    "setok_ddpm_step": [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f],
 }
 
 _libs = {}

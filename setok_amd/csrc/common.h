@@ -254,10 +254,12 @@ __device__ inline T swiglu16(float gate, float up) {
     else s = g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * g));
     return (T)((float)(T)s * u);
 }
-constexpr int SETOK_ACT_SWIGLU_PAIRS = 3;      // internal (not an `act` of setok_linear): the ping-pong GEMM's SwiGLU epilogue, reached through setok_linear_swiglu only
+constexpr int SETOK_ACT_SWIGLU_PAIRS = 100;    // internal (not an `act` of setok_linear): the ping-pong GEMM's SwiGLU epilogue, reached through setok_linear_swiglu only;
+                                               // far from the public SETOK_ACT_* codes, so that no public code can ever be read as it
 
 __device__ inline float act_apply(float v, int act) {
     if (act == SETOK_ACT_QUICK_GELU) return v / (1.0f + expf(-1.702f * v));
     if (act == SETOK_ACT_GELU_ERF) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+    if (act == SETOK_ACT_SILU) return v / (1.0f + expf(-v));
     return v;
 }

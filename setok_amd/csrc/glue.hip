@@ -205,7 +205,7 @@ __global__ void activation_kernel(const T* x, T* y, int64_t n, int act) {
 
 extern "C" int setok_activation(void* stream, int dtype, const void* x, void* y, int64_t n, int act) {
     SETOK_CHECK_ARG(x && y && n >= 0, "setok_activation: bad operand");
-    SETOK_CHECK_ARG(act >= SETOK_ACT_NONE && act <= SETOK_ACT_GELU_ERF, "setok_activation: bad act %d", act);
+    SETOK_CHECK_ARG(act >= SETOK_ACT_NONE && act <= SETOK_ACT_SILU, "setok_activation: bad act %d", act);
     if (n == 0) return SETOK_OK;
     const int grid = (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
     hipStream_t s = (hipStream_t)stream;

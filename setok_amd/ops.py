@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICK_GELU, BF16, F16, F32  # noqa: F401
+from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, BF16, F16, F32  # noqa: F401
 
 Tensor = torch.Tensor
 
@@ -749,3 +749,66 @@ def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     assert out.dtype == torch.int64 and out.numel() == rows
     _lib.call("setok_argmax_rows", _stream(), _code(x.dtype), x.data_ptr(), x.stride(0), rows, V, _p(out))
     return out
+
+
+# ---- the DiffLoss image head (csrc/diffusion.hip) ---------------------------------------------------------------------------------------------
+def timestep_embedding(t: Tensor, dim: int, dtype: torch.dtype, max_period: float = 10000.0, out: Optional[Tensor] = None) -> Tensor:
+    """[cos(t f_j) | sin(t f_j)], f_j = exp(-ln(max_period) j / (dim / 2)): t fp32 (rows,) on the device -> (rows, dim) in `dtype`."""
+    rows = t.numel()
+    _f32(t)
+    if out is None:
+        out = torch.empty((rows, dim), dtype=dtype, device=t.device)
+    assert out.shape == (rows, dim) and out.dtype == dtype
+    if rows == 0:                                    # (an empty tensor has no storage: nothing to hand to the library)
+        return out
+    _lib.call("setok_timestep_embedding", _stream(), _code(dtype), _p(t), _p(out), rows, dim, float(max_period))
+    return out
+
+
+def add_silu(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """SiLU(a + b); b: a's shape, or ONE row (C,) / (1, C) added to every row of a."""
+    rows, Cc = a.shape
+    assert b.dtype == a.dtype and b.shape[-1] == Cc and b.stride(-1) == 1 and b.is_cuda
+    one = b.dim() == 1 or b.shape[0] == 1
+    assert one or (b.dim() == 2 and b.shape[0] == rows)
+    if out is None:
+        out = torch.empty_like(a)
+    if rows == 0:
+        return out
+    _lib.call("setok_add_silu", _stream(), _code(a.dtype), _p(a), b.data_ptr(), 0 if one else b.stride(0), _p(out), rows, Cc)
+    return out
+
+
+def adaln_modulate(x: Tensor, shift: Tensor, scale: Tensor, gamma: Optional[Tensor] = None, beta: Optional[Tensor] = None, eps: float = 1e-6,
+                   h: Optional[Tensor] = None, gate: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """[x += gate * h, in place;]  LayerNorm(x; gamma, beta) * (1 + scale) + shift.  shift / scale / gate: (rows, C) column windows of ONE wider
+    row-major buffer (they share its row stride); gamma / beta None: no affine."""
+    rows, Cc = x.shape
+    wins = [shift, scale] + ([gate] if gate is not None else [])
+    for w in wins:
+        assert w.shape == (rows, Cc) and w.dtype == x.dtype and w.stride(1) == 1 and w.is_cuda and (rows <= 1 or w.stride(0) == shift.stride(0))
+    ldm = shift.stride(0) if rows > 1 else max(shift.stride(0), Cc)
+    assert (h is None) == (gate is None) and (h is None or (h.shape == x.shape and h.dtype == x.dtype))
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype
+    if rows == 0:
+        return out
+    _lib.call("setok_adaln_modulate", _stream(), _code(x.dtype), _p(x), _p(h), None if gate is None else gate.data_ptr(), _p(_f32(gamma)), _p(_f32(beta)),
+              shift.data_ptr(), scale.data_ptr(), ldm, _p(out), rows, Cc, float(eps))
+    return out
+
+
+def ddpm_step(out: Tensor, x: Tensor, noise: Tensor, x_in: Tensor, coef, nonzero: float, temperature: float = 1.0, cfg: float = 1.0, half: int = 0) -> None:
+    """One reverse DDPM step in place on the fp32 state x (rows, C) from the net's output `out` (rows, 2 C; x_in's dtype or fp32); x_in (rows, C): the
+    next evaluation's operand.  coef: (sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+    posterior_log_variance_clipped, log beta) of the step.  half > 0: classifier-free guidance over rows [0, half) | [half, 2 half)."""
+    rows, Cc = x.shape
+    _f32(x), _f32(noise)
+    assert out.shape == (rows, 2 * Cc) and out.stride(1) == 1 and out.is_cuda and out.dtype in (x_in.dtype, torch.float32)
+    assert x_in.shape == (rows, Cc) and noise.dim() == 2 and noise.shape[1] == Cc
+    a, b, c1, c2, lo, hi = (float(v) for v in coef)
+    if rows == 0:
+        return
+    _lib.call("setok_ddpm_step", _stream(), _code(x_in.dtype), _code(out.dtype), out.data_ptr(), out.stride(0) if rows > 1 else max(out.stride(0), 2 * Cc),
+              _p(x), _p(noise), noise.shape[0], _p(x_in), rows, Cc, int(half), float(cfg), a, b, c1, c2, lo, hi, float(nonzero), float(temperature))
