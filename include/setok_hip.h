@@ -134,9 +134,31 @@ int setok_encode(setok_ctx* ctx, void* stream, const void* images, int B, int k,
  * tokenizer.py:180 (`out`), multimodal_projector/builder.py:37-59 (mm_in_projector) and the HF CLIP
  * q/k/v/out_proj/fc1/fc2 linears reached from clip_encoder.py:59.  `act` fuses nn.GELU (exact erf,
  * module.py:41) or CLIP's quick_gelu.  A and W have element type `dtype`; C and residual have
- * `out_dtype` (C may alias residual).  lda/ldc are row strides in elements; K % 64 == 0 (bf16) or
- * K % 16 == 0 (fp32).  `batch` > 1 runs independent problems with the given element strides
- * (bias shared). */
+ * `out_dtype` (C may alias residual): the 16-bit type of `dtype` or SETOK_F32 for 16-bit inputs, SETOK_F32 for
+ * fp32 inputs (anything else is refused).  K % 64 == 0 (16-bit) or K % 16 == 0 (fp32).
+ *
+ * Strides, all in elements.  A, C and residual may be column windows of wider buffers — e.g. two column windows of
+ * one fused projection buffer — the pointer names the window's first element; W is dense (row stride K):
+ *   - lda >= K is A's row stride: a multiple of 8 (16-bit) or 4 (fp32) — A's rows are read in 16-byte pieces, so A
+ *     itself is 16-byte aligned (not checked);
+ *   - ldc >= N is the row stride of C AND of residual; any value is accepted.  C / residual rows that are 16-byte
+ *     aligned (ldc % 8 == 0 for a 16-bit, ldc % 4 == 0 for an fp32 output) are what the fast kernels below need;
+ *   - `batch` >= 1 runs independent problems: member b reads A + b * strideA and W + b * strideW and writes
+ *     C + b * strideC; residual is read at the same b * strideC; the bias is shared by all members.  With batch > 1
+ *     strideA and strideW are multiples of 8 (16-bit) or 4 (fp32); strideW = 0 (one weight for every member) is
+ *     allowed, and so are strides larger than the matrices.  With batch == 1 the strides are ignored.
+ * No element outside rows [0, M) x columns [0, K) of A is read and none outside [0, M) x [0, N) of C is written,
+ * at any stride.
+ *
+ * Which bits a row gets.  fp32 inputs: always the same (a k-ordered chain that depends on neither M, the strides
+ * nor the batch).  16-bit inputs: a 16-bit output with batch == 1, N % 64 == 0 and ldc % 8 == 0 is computed by the
+ * LDS-DMA kernels, whose result for a row depends on nothing but that row, W and the bias — not on M, lda, ldc or
+ * the rows around it (a sample alone equals the sample inside a batch of images).  Every other combination
+ * (batch > 1, an fp32 output, N % 64 != 0 or ldc % 8 != 0) is computed by the 128 x 128 kernel — except fp32-out
+ * problems without bias, activation and residual whose batch is large enough (split-K weight gradients).  These have another
+ * summation order: a row's bits there are those of the same kernel at batch == 1, but not those of the LDS-DMA
+ * kernels, and an activation is evaluated in its exact form for an fp32 output and in its fast form for a 16-bit one.
+ * Within any one of these kernels a stride changes addresses only, never bits. */
 int setok_linear(void* stream, int dtype, int out_dtype, const void* A, int64_t lda, const void* W,
                  const float* bias, const void* residual, void* C, int64_t ldc, int M, int N, int K,
                  int act, int batch, int64_t strideA, int64_t strideW, int64_t strideC);
@@ -218,7 +240,9 @@ int setok_ln_fold(void* stream, const void* W, const float* gamma, const float* 
                   float* w_colsum, float* bias_folded, float* col_frag, int N, int K);
 
 /* C[M,N] = act(LN(A)[M,K] . W[N,K]^T + bias) from w_gamma / col_frag of setok_ln_fold and the row statistics of A (bf16 in, bf16 out;
- * K % 64 == 0, N % 64 == 0, lda / ldc multiples of 8). */
+ * K % 64 == 0, N % 64 == 0, lda >= K and ldc >= N multiples of 8: A and C may be column windows of wider buffers as in setok_linear;
+ * w_gamma, col_frag and row_stats are dense).  The kernel is the one setok_linear picks for the same 16-bit problem: a row's bits depend on
+ * neither M nor the strides. */
 int setok_linear_ln(void* stream, const void* A, int64_t lda, const void* w_gamma, const float* col_frag, const float* row_stats,
                     void* C, int64_t ldc, int M, int N, int K, int act);
 
@@ -415,7 +439,8 @@ int setok_swiglu_pairs(void* stream, int dtype, const void* gate_up_pairs, void*
  * /root/reference/src/model/language_model/setokim_llama.py:130-143) with SwiGLU in the GEMM's epilogue — the (M, 2 F) intermediate is never written.
  * W_pairs (2 F, K): row 2 j = gate_proj.weight[j], row 2 j + 1 = up_proj.weight[j].  torch's 16-bit rounding points are kept (gate and up rounded to the
  * element type, the activation rounded, the product rounded), so the result equals setok_linear(W_pairs) followed by setok_swiglu_pairs bit for bit.
- * 16-bit element types; M % 256 == 0, (2 F) % 256 == 0, K % 64 == 0, K >= 128, else SETOK_EUNSUPPORTED (send those rows through the unfused pair). */
+ * 16-bit element types; M % 256 == 0, (2 F) % 256 == 0, K % 64 == 0, K >= 128, else SETOK_EUNSUPPORTED (send those rows through the unfused pair).
+ * lda >= K and ldo >= F are the row strides of A and out in elements, multiples of 8 (SETOK_EINVAL otherwise); a stride changes addresses only. */
 int setok_linear_swiglu(void* stream, int dtype, const void* A, int64_t lda, const void* W_pairs, void* out, int64_t ldo, int M, int F, int K);
 
 /* Causal self-attention of LlamaAttention (eager_attention_forward: softmax(q k^T * scale + mask) v, fp32 softmax) over B

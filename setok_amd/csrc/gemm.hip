@@ -278,6 +278,7 @@ int setok_linear_dev(void* stream, int dtype, int out_dtype, const void* A, int6
     if (dtype == SETOK_BF16) {
         SETOK_CHECK_ARG(K % BK == 0, "setok_linear(bf16): K=%d must be a multiple of %d", K, BK);
         SETOK_CHECK_ARG(lda % 8 == 0, "setok_linear(bf16): lda must be a multiple of 8");
+        SETOK_CHECK_ARG(batch == 1 || (strideA % 8 == 0 && strideW % 8 == 0), "setok_linear(bf16): strideA / strideW must be multiples of 8");
         switch (kern) {
             case Bf16Kernel::Persist:
                 return setok_gemm_persist_bf16(s, (const bf16*)A, lda, (const bf16*)W, bias, (const bf16*)residual, (bf16*)C, ldc, M, N, K, act, nullptr, nullptr, m_dev);
@@ -296,6 +297,7 @@ int setok_linear_dev(void* stream, int dtype, int out_dtype, const void* A, int6
         SETOK_CHECK_ARG(out_dtype == SETOK_F32, "setok_linear(f32): out_dtype must be f32");
         SETOK_CHECK_ARG(K % FK == 0, "setok_linear(f32): K=%d must be a multiple of %d", K, FK);
         SETOK_CHECK_ARG(lda % 4 == 0, "setok_linear(f32): lda must be a multiple of 4");
+        SETOK_CHECK_ARG(batch == 1 || (strideA % 4 == 0 && strideW % 4 == 0), "setok_linear(f32): strideA / strideW must be multiples of 4");
         dim3 grid(cdiv(N, FN), cdiv(M, FM), batch);
         gemm_f32_kernel<<<grid, 256, 0, s>>>(g);
     } else {

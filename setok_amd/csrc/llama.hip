@@ -500,7 +500,9 @@ int setok_gemm_swiglu_bf16(hipStream_t s, const bf16* A, int64_t lda, const bf16
 
 extern "C" int setok_linear_swiglu(void* stream, int dtype, const void* A, int64_t lda, const void* W_pairs, void* out, int64_t ldo, int M, int F, int K) {
     SETOK_CHECK_ARG(A && W_pairs && out, "setok_linear_swiglu: null operand");
-    SETOK_CHECK_ARG(M >= 0 && F > 0 && K > 0 && lda >= K && ldo >= F && lda % 8 == 0 && ldo % 8 == 0, "setok_linear_swiglu: bad shape M=%d F=%d K=%d", M, F, K);
+    SETOK_CHECK_ARG(M >= 0 && F > 0 && K > 0, "setok_linear_swiglu: bad shape M=%d F=%d K=%d", M, F, K);
+    SETOK_CHECK_ARG(lda >= K && ldo >= F, "setok_linear_swiglu: lda/ldo too small");
+    SETOK_CHECK_ARG(lda % 8 == 0 && ldo % 8 == 0, "setok_linear_swiglu: lda and ldo must be multiples of 8");
     if (dtype != SETOK_BF16) return setok_fail(SETOK_EUNSUPPORTED, "setok_linear_swiglu: 16-bit element types only (the caller runs setok_linear + setok_swiglu_pairs in fp32)");
     if (M == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;

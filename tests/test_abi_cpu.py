@@ -53,6 +53,59 @@ def test_abi_version_and_error_plumbing(lib):
         lib.call("setok_layernorm", None, 0, 1, 1, 1, 1, 4, 12, 1e-5)   # C not a multiple of 8
 
 
+P = 4096        # stands in for a device pointer: the calls below are refused before anything is launched or dereferenced
+
+
+def _linear_args(dtype, out_dtype, lda=64, ldc=64, M=4, N=64, K=64, batch=1, sA=0, sW=0, sC=0):
+    return (None, dtype, out_dtype, P, lda, P, None, None, P, ldc, M, N, K, 0, batch, sA, sW, sC)
+
+
+@pytest.mark.parametrize("half", [False, True])
+@pytest.mark.parametrize("kw,fp32,names", [
+    (dict(lda=56), False, b"lda/ldc too small"),                      # lda < K
+    (dict(ldc=56), False, b"lda/ldc too small"),                      # ldc < N
+    (dict(lda=16), True, b"lda/ldc too small"),
+    (dict(lda=68), False, b"lda must be a multiple of 8"),            # 16-bit rows are read in 16-byte pieces
+    (dict(lda=66), True, b"lda must be a multiple of 4"),             # ... and so are fp32 rows
+    (dict(batch=0), False, b"batch=0"),
+    (dict(batch=-2), True, b"batch=-2"),
+    (dict(batch=2, sA=4 * 64 + 4, sW=64 * 64), False, b"strideA / strideW must be multiples of 8"),
+    (dict(batch=2, sA=4 * 64, sW=64 * 64 + 2), True, b"strideA / strideW must be multiples of 4"),
+])
+def test_linear_refuses_bad_strides_and_batches_on_the_host(lib, half, kw, fp32, names):
+    """include/setok_hip.h, setok_linear: row strides no smaller than the logical widths, 16-byte granules for A's rows and the batch strides of A and W,
+    batch >= 1.  Refused with a message that names the problem, before any launch (no GPU needed)."""
+    l = lib.load(half)
+    dt = 0 if fp32 else (2 if half else 1)
+    assert l.setok_linear(*_linear_args(dt, dt, **kw)) == -1
+    assert names in l.setok_last_error(), l.setok_last_error()
+
+
+@pytest.mark.parametrize("half", [False, True])
+def test_linear_refuses_a_16_bit_output_of_fp32_inputs(lib, half):
+    l = lib.load(half)
+    assert l.setok_linear(*_linear_args(0, 2 if half else 1)) == -1 and b"out_dtype must be f32" in l.setok_last_error()
+
+
+@pytest.mark.parametrize("half", [False, True])
+def test_linear_ln_and_linear_swiglu_refuse_bad_strides_on_the_host(lib, half):
+    l = lib.load(half)
+    # setok_linear_ln(stream, A, lda, w_gamma, col_frag, row_stats, C, ldc, M, N, K, act)
+    for lda, ldc, N in ((64, 132, 128),        # ldc % 8 != 0
+                        (64, 96, 96),          # N % 64 != 0
+                        (68, 128, 128),        # lda % 8 != 0
+                        (56, 128, 128),        # lda < K
+                        (64, 120, 128)):       # ldc < N
+        assert l.setok_linear_ln(None, P, lda, P, P, P, P, ldc, 4, N, 64, 0) == -1, (lda, ldc, N)
+        assert b"N % 64 == 0, 16-byte aligned rows" in l.setok_last_error(), l.setok_last_error()
+    # setok_linear_swiglu(stream, dtype, A, lda, W_pairs, out, ldo, M, F, K)
+    dt = 2 if half else 1
+    assert l.setok_linear_swiglu(None, dt, P, 128, P, P, 120, 256, 128, 128) == -1 and b"lda/ldo too small" in l.setok_last_error()
+    assert l.setok_linear_swiglu(None, dt, P, 120, P, P, 128, 256, 128, 128) == -1 and b"lda/ldo too small" in l.setok_last_error()
+    assert l.setok_linear_swiglu(None, dt, P, 128, P, P, 132, 256, 128, 128) == -1 and b"ldo must be multiples of 8" in l.setok_last_error()
+    assert l.setok_linear_swiglu(None, dt, P, 132, P, P, 128, 256, 128, 128) == -1 and b"ldo must be multiples of 8" in l.setok_last_error()
+
+
 def test_each_build_refuses_the_other_builds_16_bit_type(lib):
     """libsetok_hip.so serves float32 + bfloat16, libsetok_hip_f16.so float32 + float16 (include/setok_hip.h, `dtype`): a buffer of the other
     16-bit type must be refused on the host, never read as something else.  Routing: a call carrying the F16 code goes to the fp16 build."""

@@ -100,10 +100,11 @@ def test_linear_bf16_large_no_bias_and_alias():
 @pytest.mark.parametrize("N,K", [(1024, 1024), (4096, 1024), (1024, 4096)])
 @pytest.mark.parametrize("act,use_res", [(0, False), (1, False), (2, True), (0, True)])
 def test_linear_bf16_rows_do_not_depend_on_the_kernel(act, use_res, N, K):
-    """The same rows through the persistent 256 x 256 kernel (M = 25 k: 392 tiles), through its small-problem kernel in all three shapes
-    (64 x 32 tiles where 64 x 64 ones would leave half the chip idle: M = 1, 63, 257 at N = 1024; four stages / two workgroups per CU where
-    there are more tiles than CUs: M = 1028 at N = 1024, M = 257 at N = 4096; 64 x 64 with eight stages otherwise) and inside a mid-size
-    problem give the same bits: a sample alone equals the sample inside a batch."""
+    """The same rows through the persistent 256 x 256 kernel (M = 25 k: 392 tiles), through its small-problem kernel in every shape it can take
+    (32 x 32 tiles where up to two of them per CU fit one round: M = 1, 63, 257 at N = 1024 — the 64 x 32 shape of tail_shape_for is never picked,
+    the 32 x 32 rule above it fires first; four stages / two workgroups per CU where there are more 64 x 64 tiles than CUs: M = 1028 at N = 1024,
+    M = 257 at N = 4096; 128 x 64 tiles + the rows behind them: M = 2056, 2048 at N = 1024; 64 x 64 with eight stages otherwise) and inside a
+    mid-size problem give the same bits: a sample alone equals the sample inside a batch."""
     M = 25088
     a, w = _rand(M, K, seed=11).bfloat16().to(DEV), (_rand(N, K, seed=12, scale=K ** -0.5)).bfloat16().to(DEV)
     b = _rand(N, seed=13).to(DEV)
