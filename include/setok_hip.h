@@ -531,6 +531,48 @@ int setok_attention_decode_gqa(void* stream, int dtype, const void* q, int64_t l
  * a NaN counts as the maximum.  Deterministic. */
 int setok_argmax_rows(void* stream, int dtype, const void* x, int64_t ld, int rows, int V, int64_t* out);
 
+/* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip): the decode step streams every projection weight once per token, so the stack's Linear
+ * weights may be STORED as OCP e4m3fn bytes with one power-of-two scale per output row.  A matrix W (N, K) becomes q (N, K) uint8 + e (N,) int8 and
+ * means exactly
+ *     W'[n, k] = value_e4m3fn(q[n, k]) * 2^e[n],      e[n] in [-15, 7].
+ * Because the scale is a power of two inside that range, W' is exactly representable in bf16, in fp16 (2^-9 * 2^-15 is its smallest subnormal,
+ * 448 * 2^7 < 65504) and in fp32: a quantised model is an ordinary model whose weights lie on a grid, and setok_linear on the dequantised W'
+ * computes the same function.  Pure additions: the ABI version stays 9. */
+
+/* The quantiser, per row n:  amax = max_k |W[n, k]| over the finite entries;  e[n] = the smallest integer with amax <= 448 * 2^e, clamped to
+ * [-15, 7], and 0 for a row without a non-zero finite entry (exponent arithmetic, no log2);  q[n, k] = round-to-nearest-even_e4m3fn(W[n, k] * 2^-e[n]),
+ * subnormals included, saturating at +-448 (reachable only where the clamp at 7 binds);  a non-finite W[n, k] becomes the NaN code 0x7f.
+ * W: (N, K) in `dtype`, row stride ldw >= K elements;  q: row stride ldq >= K bytes;  any alignment, any K >= 1.  One workgroup per row, two
+ * passes over the row, no atomics. */
+int setok_quantize_fp8_rows(void* stream, int dtype, const void* W, int64_t ldw, uint8_t* q, int64_t ldq, int8_t* e, int N, int K);
+
+/* The exact inverse: W[n, k] = value(q[n, k]) * 2^e[n] in `dtype` — no rounding happens, by the contract above.  Same strides. */
+int setok_dequantize_fp8_rows(void* stream, int dtype, const uint8_t* q, int64_t ldq, const int8_t* e, void* W, int64_t ldw, int N, int K);
+
+/* C[M, N] = A[M, K] · W'^T + residual[M, N]   (residual optional; C may alias it) for 1 <= M <= 64: the weight-streaming GEMM of a decode step.
+ * A, residual and C have element type `dtype`; products of the exact element-type values of A and value(q), fp32 accumulation, the scale 2^e[n]
+ * applied once in fp32, one rounding to `dtype`.  K % 64 == 0 (16-bit) or K % 16 == 0 (fp32), any N >= 1.
+ * Strides as in setok_linear: lda >= K (A's row stride in elements, a multiple of 8 / 4: 16-byte pieces, A 16-byte aligned), ldc >= N (C AND
+ * residual, any value), ldq >= K (q's row stride in bytes, a multiple of 16, q 16-byte aligned).  Anything else — M > 64 included: dequantise
+ * and call setok_linear — is SETOK_EINVAL with a message naming the argument, before any launch.
+ * No element outside A's [0, M) x [0, K) or q's [0, N) x [0, K) is read and none outside C's [0, M) x [0, N) is written, at any stride.
+ * A row's bits depend on that row of A (and of residual), q and e alone — not on M, the strides or the rows around it: there is one summation
+ * order, fixed by K.  It is NOT setok_linear's order: bit equality with setok_linear on the dequantised W' is not promised, only the same
+ * function within fp32 accumulation error.  No atomics, no hand-off between workgroups.
+ * SETOK_F32 is the parity mode and a DIFFERENT algorithm from the 16-bit MFMA path: plain fp32 arithmetic that carries its rounding errors
+ * (error-free products and sums), so each output is the fp32 value next to the exact dot product — better than an fp32-accumulated chain.
+ * Its agreement with fp64 says the layout, the scales and the bounds are right; it is no evidence for the accumulation of the 16-bit path. */
+int setok_linear_fp8w(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const int8_t* e,
+                      const void* residual, void* C, int64_t ldc, int M, int N, int K);
+
+/* setok_linear_fp8w with the floor of its band rule as an argument.  A workgroup of the 16-bit path owns 16, 32 or 64 output columns — the widest
+ * band (64 from three row tiles of 16 rows, 32 at two, 16 at one) that still leaves ceil(N / band) >= min_wgs workgroups; setok_linear_fp8w
+ * passes 256, the CU count of an MI355X.  min_wgs >= 1: 1 always takes the widest band, a value above N / 32 always the narrowest.  The band
+ * decides which workgroup computes a column and never a bit of C: this entry exists for parts with fewer active CUs, and so that the tests can
+ * hold every band to that at small N.  SETOK_F32 ignores it. */
+int setok_linear_fp8w_wgs(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const int8_t* e,
+                          const void* residual, void* C, int64_t ldc, int M, int N, int K, int min_wgs);
+
 /* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
  * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest
  * (csrc/diffusion.hip).  Every entry is asynchronous on `stream`, allocates nothing, synchronises nothing, accepts rows == 0, uses 16-byte

@@ -105,6 +105,10 @@ SIGNATURES = {
     "setok_kv_append": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_argmax_rows": [_vp, _i, _vp, _i64, _i, _i, _vp],
+    "setok_quantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i, _i],
+    "setok_dequantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _i],
+    "setok_linear_fp8w": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i],
+    "setok_linear_fp8w_wgs": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i],
     "setok_timestep_embedding": [_vp, _i, _vp, _vp, _i, _i, _f],
     "setok_add_silu": [_vp, _i, _vp, _vp, _i64, _vp, _i, _i],
     "setok_adaln_modulate": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _f],

@@ -81,9 +81,79 @@ class LlamaModel(PackCacheMixin, nn.Module):
                                      for _ in range(num_hidden_layers)])
         self.norm = _RMSNorm(hidden_size, rms_norm_eps)
         self._init_pack_cache()
+        self._fp8 = None                                                        # quantize_fp8_(): the packed stack in fp8 storage
+
+    @property
+    def weight_format(self) -> str:
+        """"native" (the Linear weights in the model's element type) or "fp8_e4m3" after quantize_fp8_()."""
+        return "native" if self._fp8 is None else "fp8_e4m3"
+
+    @torch.no_grad()
+    def quantize_fp8_(self, free_master: bool = True):
+        """Store the stack's projection weights as e4m3fn bytes with one power-of-two exponent per output row (include/setok_hip.h, "FP8
+        weight-only decode"): the four fused operands `_pack` builds per layer — q|k|v, o, pair-interleaved gate|up, down — quantised on the device,
+        one layer at a time.  Rows are independent, so quantising a fused matrix equals quantising its parts.  embed_tokens, the norms and
+        lm_head stay as they are.  The model then IS the Llama whose weights are W' = value(q) * 2^e (exactly representable in the element
+        type): `_forward` / `prefill` dequantise each matrix into one reusable scratch buffer and run the existing kernels on it,
+        `decode_step` streams the bytes through `ops.linear_fp8w`.  With `free_master` the Linear parameters release their storage (N * K + N
+        bytes per matrix remain) and `state_dict()` is refused; without it the masters stay for `state_dict()` only — the fp8 copy computes, and an
+        in-place update of any stack parameter afterwards is refused at the next forward instead of being silently ignored.  Call it on the device and in the dtype the model will run in.  Inference only."""
+        if self._fp8 is not None:
+            raise NotImplementedError("LlamaModel.quantize_fp8_: the stack is already in fp8 storage (a second quantisation would re-round it)")
+        f32 = lambda t: t.detach().float().contiguous()
+        w0 = self.norm.weight
+        if not w0.is_cuda:
+            raise NotImplementedError("LlamaModel.quantize_fp8_: the fp8 quantiser runs on the device; move the model there first")
+        layers, largest = [], 0
+        for l in self.layers:
+            a, m = l.self_attn, l.mlp
+            fused = dict(wqkv=torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), wo=a.o_proj.weight.contiguous(),
+                         wgu=ops.interleave_gate_up(m.gate_proj.weight, m.up_proj.weight), wd=m.down_proj.weight.contiguous())
+            L = dict(n1=f32(l.input_layernorm.weight), n2=f32(l.post_attention_layernorm.weight))
+            for k, w in fused.items():
+                L[k] = ops.quantize_fp8_rows(w)
+                largest = max(largest, w.numel())
+            layers.append(L)
+            del fused
+            if free_master:
+                for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj):
+                    lin.weight.requires_grad_(False)
+                    lin.weight.data = torch.empty(0, dtype=w0.dtype, device=w0.device)
+        self._fp8 = dict(key=(w0.dtype, str(w0.device)), layers=layers, norm=f32(self.norm.weight), largest=largest, scratch=None,
+                         freed=bool(free_master), versions=self._versions(self.parameters()))
+        self._packed = {}
+        return self
+
+    def state_dict(self, *args, **kwargs):
+        if self._fp8 is not None and self._fp8["freed"]:
+            raise NotImplementedError("LlamaModel.state_dict: the Linear weights were released by quantize_fp8_(free_master=True); saving an fp8 "
+                                      "stack is not implemented (quantise with free_master=False to keep the masters)")
+        return super().state_dict(*args, **kwargs)
+
+    def _w(self, w):
+        """A packed operand as `linear` takes it: itself, or — fp8 storage, a (q, e) pair — dequantised into the one scratch buffer (stream order
+        makes the reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
+        if not isinstance(w, tuple):
+            return w
+        return ops.dequantize_fp8_rows(w[0], w[1], out=self._fp8_scratch()[:w[0].numel()].view(w[0].shape))
+
+    def _fp8_scratch(self):
+        f = self._fp8
+        if f["scratch"] is None:
+            f["scratch"] = torch.empty(f["largest"], dtype=f["key"][0], device=self.norm.weight.device)
+        return f["scratch"]
 
     def _pack(self):
         w = self.norm.weight
+        if self._fp8 is not None:
+            if self._fp8["key"] != (w.dtype, str(w.device)):
+                raise NotImplementedError(f"LlamaModel: the stack was quantised to fp8 as {self._fp8['key']} and cannot follow a move to "
+                                          f"{(w.dtype, str(w.device))}")
+            if self._versions(self.parameters()) != self._fp8["versions"]:
+                # (free_master=False keeps the masters for state_dict(); the fp8 copy is what computes, and it cannot follow them)
+                raise NotImplementedError("LlamaModel: a parameter of the stack was modified in place after quantize_fp8_ (a LoRA merge, an optimiser "
+                                          "step): the fp8 copy is stale and re-quantising is not implemented; quantise after the last update")
+            return self._fp8
         key = (w.dtype, str(w.device), self._versions(self.parameters()))      # every tensor: a LoRA merge into q_proj / v_proj alone must rebuild the fused copies
         if self._packed.get("key") == key:
             return self._packed
@@ -107,6 +177,8 @@ class LlamaModel(PackCacheMixin, nn.Module):
                                                                  weights is the reference's HF-Trainer side (SURVEY.md §2 "OUT")
           the stack is frozen and inputs_embeds requires one     the same values with a grad_fn (autograd.LlamaFn): backward() delivers
                                                                  d loss / d inputs_embeds"""
+        if self._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            raise NotImplementedError("LlamaModel.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 weights)")
         if torch.is_grad_enabled() and inputs_embeds.requires_grad and not self.stack_requires_grad():
             return autograd.LlamaFn.apply(self, inputs_embeds, attention_mask, position_ids)
         with torch.no_grad():
@@ -133,15 +205,15 @@ class LlamaModel(PackCacheMixin, nn.Module):
         y = None
         for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = ops.linear(y, L["wqkv"])
+            qkv = ops.linear(y, self._w(L["wqkv"]))                      # (_w: the operand itself; fp8 storage dequantises it into the scratch buffer first)
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
             if cache is not None:
                 ops.kv_append(qkv, cache.k[li], cache.v[li], T, H, 0)
             o = ops.attention_causal(qkv, km, B, T, H, dh, dh ** -0.5, Hkv)
-            ops.linear(o, L["wo"], residual=x, out=x)
+            ops.linear(o, self._w(L["wo"]), residual=x, out=x)
             y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-            g = ops.linear_swiglu(y, L["wgu"])                           # gate|up Linear with SwiGLU in its epilogue (16-bit modes; the unfused pair otherwise: same bits)
-            ops.linear(g, L["wd"], residual=x, out=x)
+            g = ops.linear_swiglu(y, self._w(L["wgu"]))                  # gate|up Linear with SwiGLU in its epilogue (16-bit modes; the unfused pair otherwise: same bits)
+            ops.linear(g, self._w(L["wd"]), residual=x, out=x)
         if cache is not None:
             # every sequence's next rotary position: the position of its last attended token + 1 (HF extends `cumsum(attention_mask) - 1` the same way)
             p2 = pos.reshape(B, T)
@@ -186,12 +258,20 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.key_mask[:, slot] = 1
         ws = cache.workspace(H)
         y = o = None
+        fp8 = self._fp8 is not None
+        big = self._fp8_scratch() if fp8 and B > ops.FP8W_MAX_M else None          # more rows than the streaming kernel takes: dequantise, then `linear`
         for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = ops.linear(y, L["wqkv"])
+            qkv = ops.linear_fp8w(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
             ops.kv_append(qkv, cache.k[li], cache.v[li], 1, H, slot)
             o = ops.attention_decode(qkv, cache.k[li], cache.v[li], cache.key_mask, H, slot + 1, dh ** -0.5, ws=ws, out=o)
+            if fp8:                                                                 # the same step on the fp8 bytes: four weight-streaming GEMMs
+                ops.linear_fp8w(o, *L["wo"], residual=x, out=x, scratch=big)
+                y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
+                g = ops.swiglu_pairs(ops.linear_fp8w(y, *L["wgu"], scratch=big))
+                ops.linear_fp8w(g, *L["wd"], residual=x, out=x, scratch=big)
+                continue
             ops.linear(o, L["wo"], residual=x, out=x)
             y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
             g = ops.linear_swiglu(y, L["wgu"])
@@ -271,6 +351,15 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     def get_model(self):
         return self.model
 
+    @property
+    def weight_format(self) -> str:
+        return self.model.weight_format
+
+    def quantize_fp8_(self, free_master: bool = True):
+        """`LlamaModel.quantize_fp8_`: the decoder stack's projection weights into fp8 storage (embed_tokens, the norms and lm_head stay)."""
+        self.model.quantize_fp8_(free_master)
+        return self
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, inputs_embeds=None, labels=None, comp_images=None,
                 last_token_only: bool = False, return_loss: bool = False):
         """Returns (logits, new_labels, attention_mask): logits (B, T', vocab) — or (B, vocab) for every sequence's last token with
@@ -289,6 +378,9 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         given = inputs_embeds
         with torch.set_grad_enabled(may_train):
             inputs_embeds, attention_mask, position_ids, new_labels = self._embed(input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images)
+        if self.model._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            raise NotImplementedError("SetokimLlamaPrefill.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 "
+                                      "weights); run it under torch.no_grad() or detach inputs_embeds")
         if may_train and inputs_embeds.requires_grad:
             if last_token_only:
                 what = "SetokimLlamaPrefill.forward with last_token_only=True (a generation step: inference-only)"

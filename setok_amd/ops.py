@@ -751,6 +751,69 @@ def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+# ---- fp8 weight-only storage (csrc/gemm_fp8w.hip) -----------------------------------------------------------------------------------------------
+FP8W_MAX_M = 64                                   # rows setok_linear_fp8w takes; more rows dequantise and go through `linear`
+
+
+def _rows_ld(t: Tensor) -> int:
+    """Row stride of a 2-d tensor whose rows are dense (a column window of a wider buffer is fine)."""
+    assert t.dim() == 2 and t.is_cuda and (t.stride(1) == 1 or t.shape[1] == 1), "2-d device tensor with dense rows required"
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def quantize_fp8_rows(w: Tensor, q: Optional[Tensor] = None, e: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """w (N, K) fp32 / bf16 / fp16 -> (q (N, K) uint8 of e4m3fn codes, e (N,) int8) with w' = value(q) * 2^e[:, None] (include/setok_hip.h)."""
+    N, K = w.shape
+    if q is None:
+        q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    if e is None:
+        e = torch.empty(N, dtype=torch.int8, device=w.device)
+    assert q.shape == (N, K) and q.dtype == torch.uint8 and e.shape == (N,) and e.dtype == torch.int8 and e.is_contiguous()
+    _lib.call("setok_quantize_fp8_rows", _stream(), _code(w.dtype), w.data_ptr(), _rows_ld(w), q.data_ptr(), _rows_ld(q), _p(e), N, K)
+    return q, e
+
+
+def dequantize_fp8_rows(q: Tensor, e: Tensor, dtype: Optional[torch.dtype] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The exact inverse of quantize_fp8_rows into `dtype` (or into `out`, whose rows may be wider than K)."""
+    N, K = q.shape
+    if out is None:
+        out = torch.empty((N, K), dtype=dtype, device=q.device)
+    assert out.shape == (N, K) and (dtype is None or out.dtype == dtype)
+    assert q.dtype == torch.uint8 and e.shape == (N,) and e.dtype == torch.int8 and e.is_contiguous()
+    _lib.call("setok_dequantize_fp8_rows", _stream(), _code(out.dtype), q.data_ptr(), _rows_ld(q), _p(e), out.data_ptr(), _rows_ld(out), N, K)
+    return out
+
+
+def linear_fp8w(a: Tensor, q: Tensor, e: Tensor, residual: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                scratch: Optional[Tensor] = None, min_wgs: Optional[int] = None) -> Tensor:
+    """out = a @ w'.T + residual with w' = value(q) * 2^e[:, None];  a: (M, K), q: (N, K) uint8, e: (N,) int8.  M <= 64 is ONE launch of the
+    weight-streaming kernel (a, residual and out may be column windows of wider buffers).  More rows dequantise w' into `scratch` — the
+    caller's, at least N * K elements of a.dtype — and run the existing `linear` on it: the same function, `linear`'s summation order.
+    `min_wgs` replaces the floor of the kernel's band rule (setok_linear_fp8w_wgs; None: the library's own, one workgroup per CU): it moves
+    columns between workgroups and changes no bit."""
+    M, K = a.shape
+    N, K2 = q.shape
+    assert K == K2 and q.dtype == torch.uint8 and e.shape == (N,) and e.dtype == torch.int8 and e.is_contiguous()
+    if M > FP8W_MAX_M:
+        if scratch is None or scratch.dtype != a.dtype or scratch.numel() < N * K:
+            raise ValueError(f"linear_fp8w: M={M} > {FP8W_MAX_M} dequantises the weight: pass `scratch`, {N * K} elements of {a.dtype}")
+        w = dequantize_fp8_rows(q, e, out=scratch.reshape(-1)[:N * K].view(N, K))
+        return linear(a, w, residual=residual, out=out)
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    assert out.shape == (M, N) and out.dtype == a.dtype
+    ldc = _rows_ld(out)
+    if residual is not None:
+        assert residual.shape == (M, N) and residual.dtype == a.dtype and (M == 1 or _rows_ld(residual) == ldc), "residual shares out's row stride"
+    args = (_stream(), _code(a.dtype), a.data_ptr(), _rows_ld(a), q.data_ptr(), _rows_ld(q), _p(e),
+            None if residual is None else residual.data_ptr(), out.data_ptr(), ldc, M, N, K)
+    if min_wgs is None:
+        _lib.call("setok_linear_fp8w", *args)
+    else:
+        _lib.call("setok_linear_fp8w_wgs", *args, int(min_wgs))
+    return out
+
+
 # ---- the DiffLoss image head (csrc/diffusion.hip) ---------------------------------------------------------------------------------------------
 def timestep_embedding(t: Tensor, dim: int, dtype: torch.dtype, max_period: float = 10000.0, out: Optional[Tensor] = None) -> Tensor:
     """[cos(t f_j) | sin(t f_j)], f_j = exp(-ln(max_period) j / (dim / 2)): t fp32 (rows,) on the device -> (rows, dim) in `dtype`."""

@@ -4,6 +4,9 @@ to produce token n + 1 before: the whole prefill again over the sequence grown b
     python tools/bench_generate.py [--layers 32] [--batches 32,8,1] [--prompt 552] [--new 200] [--reps 5]
     python tools/bench_generate.py --steps-only 3 [--batch 32]          # prefill-free: a few decode steps and nothing else (what a kernel trace is pointed at)
     python tools/bench_generate.py --attention-only [--gqa 4]           # the decode-attention launch pair alone (what a counter run is pointed at)
+    python tools/bench_generate.py --weights fp8 ...                    # any of the above with the stack in fp8 storage (quantize_fp8_)
+    python tools/bench_generate.py --compare-weights [--rounds 3]       # native and fp8 arms alternated in one process: decode step + the four GEMMs
+    python tools/bench_generate.py --compare-bands [--rounds 3]         # linear_fp8w's 16 / 32 / 64-column bands alternated in one process, four GEMMs
 
 Prints one JSON line.  Per batch size, in one process:
   (a) ms per token the old way: forward(inputs_embeds of T' + 1 positions, last_token_only=True);
@@ -83,6 +86,103 @@ def _attention_pair(c, q, length, reps):
     return ms, live
 
 
+LAYER_SHAPES = ((3 * D, D), (D, D), (2 * FD, D), (D, FD))          # (N, K) of the fused q|k|v, o, gate|up and down projections
+
+
+def _spread(xs):
+    xs = sorted(xs)
+    return dict(median=round(xs[len(xs) // 2], 4), min=round(xs[0], 4), max=round(xs[-1], 4), runs=[round(x, 4) for x in xs])
+
+
+def _compare_weights(a, g, dev, dt, rnd):
+    """Both arms in ONE process, alternated round by round after a warm-up, every timing ended by a device synchronise: the decode step of a
+    native and of an fp8-quantised stack (two models with the same weights up to the rounding) at the prompt length, and `linear_fp8w` against
+    `linear` on the dequantised weight at the four layer shapes.  Every arm runs `--rounds` times: min / median / max are reported."""
+    from setok_amd import ops
+    T, N = a.prompt, a.new
+    native = _llm(a.layers, g, dev, dt)
+    fp8 = _llm(a.layers, g, dev, dt)
+    fp8.load_state_dict(native.state_dict())
+    fp8.quantize_fp8_()
+    arms = (("native", native), ("fp8", fp8))
+    step = {}
+    for B in [int(b) for b in a.batches.split(",")]:
+        caches = {k: _filled_cache(m, B, T + N, T, g) for k, m in arms}
+        e1 = rnd(B, D)
+
+        def one(k, m):
+            _set_len(caches[k], T)
+            return m.model.decode_step(e1, caches[k])
+
+        runs = {k: [] for k, _ in arms}
+        for _ in range(a.rounds):
+            for k, m in arms:
+                runs[k].append(_time(lambda: one(k, m), a.reps))
+        r = {k: _spread(v) for k, v in runs.items()}
+        r["fp8_over_native_median"] = round(r["fp8"]["median"] / r["native"]["median"], 3)
+        r["faster_by_more_than_the_spread"] = r["fp8"]["max"] < r["native"]["min"]
+        step[f"B{B}"] = r
+        del caches
+    del native, fp8
+    torch.cuda.empty_cache()
+    kern = {}
+    for Nn, K in LAYER_SHAPES:
+        # as many copies of each operand as hold 1.2 GB of q (23 to 71 at the layer shapes), visited round robin: the weights come from HBM, as
+        # the 32 layers of a step do
+        copies = max(2, int(1.2e9 // (Nn * K)))
+        w = [(torch.randn(Nn, K, generator=g, device=dev, dtype=torch.float32) * 0.02).to(dt) for _ in range(copies)]
+        qe = [ops.quantize_fp8_rows(x) for x in w]
+        w = [ops.dequantize_fp8_rows(q, e, dtype=dt) for q, e in qe]
+        for M in (1, 8, 32, 64):
+            x = rnd(M, K)
+            out = torch.empty(M, Nn, dtype=dt, device=dev)
+            f_native = lambda: [ops.linear(x, wi, out=out) for wi in w]
+            f_fp8 = lambda: [ops.linear_fp8w(x, q, e, out=out) for q, e in qe]
+            runs = {"native": [], "fp8": []}
+            for _ in range(a.rounds):
+                runs["native"].append(_time(f_native, a.reps) / copies)
+                runs["fp8"].append(_time(f_fp8, a.reps) / copies)
+            r = {k: _spread(v) for k, v in runs.items()}
+            r["fp8_q_tb_per_s"] = round(Nn * K / (r["fp8"]["median"] * 1e-3) / 1e12, 3)
+            r["native_w_tb_per_s"] = round(2 * Nn * K / (r["native"]["median"] * 1e-3) / 1e12, 3)
+            kern[f"N{Nn}_K{K}_M{M}"] = r
+        del w, qe
+    print(json.dumps(dict(
+        workload="cfg5 LLM decode step, Llama at Vicuna-7B dims, bf16: the stack's projection weights native (bf16) against fp8 e4m3 storage; "
+                 "ms per decode step at cache length = prompt, and ms per GEMM call at the four layer shapes (operands cycled through >= 1.2 GB)",
+        layers=a.layers, prompt=T, reps=a.reps, rounds=a.rounds, device=torch.cuda.get_device_name(0), decode_step_ms=step, gemm_ms=kern,
+        peak_bytes=torch.cuda.max_memory_allocated())))
+
+
+def _compare_bands(a, g, dev, dt, rnd):
+    """`linear_fp8w` at the four layer shapes with the band named through the floor of its rule (`min_wgs`; setok_linear_fp8w_wgs): 16, 32 and
+    64 columns per workgroup where the row tiles allow them, and the library's own choice.  One process, the arms alternated round by round,
+    every timing ended by a device synchronise, `--rounds` runs per arm.  The bits do not depend on the band; the time does."""
+    from setok_amd import ops
+    cdiv = lambda x, y: -(-x // y)
+    out_ = {}
+    for Nn, K in LAYER_SHAPES:
+        copies = max(2, int(1.2e9 // (Nn * K)))              # 1.2 GB of q, visited round robin: the weights come from HBM
+        qe = [ops.quantize_fp8_rows((torch.randn(Nn, K, generator=g, device=dev, dtype=torch.float32) * 0.02).to(dt)) for _ in range(copies)]
+        for M in (32, 64):
+            x = rnd(M, K)
+            out = torch.empty(M, Nn, dtype=dt, device=dev)
+            widest = 2 if M <= 32 else 4
+            arms = {f"cols{16 * nt}": cdiv(Nn, 16 * nt) for nt in (1, 2, 4) if nt <= widest}      # the floor that this band just meets
+            arms["library"] = None
+            runs = {k: [] for k in arms}
+            for _ in range(a.rounds):
+                for k, floor in arms.items():
+                    runs[k].append(_time(lambda: [ops.linear_fp8w(x, q, e, out=out, min_wgs=floor) for q, e in qe], a.reps) / copies)
+            r = {k: dict(_spread(v), workgroups=arms[k]) for k, v in runs.items()}
+            out_[f"N{Nn}_K{K}_M{M}"] = r
+        del qe
+    print(json.dumps(dict(
+        workload="linear_fp8w, bf16, ms per call at the four layer shapes of Vicuna-7B (operands cycled through >= 1.2 GB): the columns a workgroup "
+                 "owns, named through min_wgs, against the library's own rule (the widest band that leaves 256 workgroups)",
+        reps=a.reps, rounds=a.rounds, device=torch.cuda.get_device_name(0), gemm_ms=out_)))
+
+
 def _bw(ms, live):
     tbs = live / (ms * 1e-3) / 1e12
     return dict(ms_all_layers=round(ms, 4), live_kv_gb=round(live / 1e9, 3), tb_per_s=round(tbs, 3), of_8_tb_per_s=round(tbs / 8.0, 3),
@@ -100,6 +200,10 @@ def main():
     ap.add_argument("--steps-only", type=int, default=0)
     ap.add_argument("--attention-only", action="store_true")
     ap.add_argument("--gqa", type=int, default=4)
+    ap.add_argument("--weights", choices=("native", "fp8"), default="native")
+    ap.add_argument("--compare-weights", action="store_true")
+    ap.add_argument("--compare-bands", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     from setok_amd import ops
 
@@ -118,7 +222,16 @@ def main():
         print(json.dumps(dict(shape=dict(B=B, H=H, Hkv=Hkv, Dh=DH, len=n), launches_of_the_pair=2, live_kv_bytes_per_launch=2 * k.numel() * 2)))
         return
 
+    if a.compare_weights:
+        _compare_weights(a, g, dev, dt, rnd)
+        return
+    if a.compare_bands:
+        _compare_bands(a, g, dev, dt, rnd)
+        return
+
     llm = _llm(a.layers, g, dev, dt)
+    if a.weights == "fp8":
+        llm.quantize_fp8_()
     w_lm, w_e = llm.lm_head.weight.detach(), llm.model.embed_tokens.weight.detach()
 
     def token_step(c, h):
@@ -133,7 +246,7 @@ def main():
         for _ in range(a.steps_only):
             h = token_step(c, h)
         torch.cuda.synchronize()
-        print(json.dumps(dict(batch=B, prompt=T, decode_steps=a.steps_only, layers=a.layers)))
+        print(json.dumps(dict(batch=B, prompt=T, decode_steps=a.steps_only, layers=a.layers, weights=a.weights)))
         return
 
     res = {}
@@ -170,7 +283,7 @@ def main():
         del grown, am, prompt
     print(json.dumps(dict(
         workload="cfg5 LLM decode: Llama at Vicuna-7B dims, bf16, greedy, KV cache of prompt + new slots; baseline = the prefill over the grown sequence",
-        layers=a.layers, prompt=T, new_tokens=N, reps=a.reps, decode_chunk=ops.DECODE_CHUNK, results=res, peak_bytes=torch.cuda.max_memory_allocated())))
+        weights=a.weights, layers=a.layers, prompt=T, new_tokens=N, reps=a.reps, decode_chunk=ops.DECODE_CHUNK, results=res, peak_bytes=torch.cuda.max_memory_allocated())))
 
 
 if __name__ == "__main__":
