@@ -573,6 +573,36 @@ int setok_linear_fp8w(void* stream, int dtype, const void* A, int64_t lda, const
 int setok_linear_fp8w_wgs(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const int8_t* e,
                           const void* residual, void* C, int64_t ldc, int M, int N, int K, int min_wgs);
 
+/* ---- FP8 KV cache (csrc/attn_decode.hip): the decode attention is bound by the K / V bytes it reads, so the cache may be STORED by the rule
+ * above, one cache row — the Dh post-rotary elements of one (sequence, key / value head, slot), of K or of V — taking the place of a weight row:
+ * Dh e4m3fn bytes and one int8 exponent, meaning exactly value(q[d]) * 2^e with e in [-15, 7]; amax over the finite entries, e the smallest
+ * exponent with amax <= 448 * 2^e (0 for a row of zeros), round-to-nearest-even including the subnormals, saturation at +-448, the NaN code for
+ * a non-finite entry.  Per layer: k_q, v_q (B, Hkv, cap, Dh) uint8 and k_e, v_e (B, Hkv, cap) int8.  The stored K', V' are exactly
+ * representable in fp32, bf16 and fp16, so an attention over the fp8 cache is an ordinary attention over K', V'.  Only the cache is
+ * quantised: the prefill attends over its own unquantised q | k | v.  Pure additions: the ABI version stays 9. */
+
+/* Keys of one chunk of the decode attention over the fp8 cache (what SETOK_DECODE_CHUNK is to setok_attention_decode_gqa): a wave streams 64
+ * rows of 16-byte pieces, which keeps as many bytes in flight per wave as the 16-bit kernel has with 32 rows. */
+#define SETOK_DECODE_CHUNK_FP8KV 256
+
+/* setok_kv_append with the quantiser: the post-rotary k and v columns of B*T rows of a fused [q: H | k: Hkv | v: Hkv] buffer in `dtype` are
+ * quantised row by row (the rule above) into slots [pos0, pos0 + T) of k_q / k_e and v_q / v_e.  One pass, a row in the registers of the
+ * lanes that hold it; no atomics; no byte outside those slots is written.  Dh % 8 == 0 and Dh <= 512; qkv, k_q and v_q 16-byte aligned. */
+int setok_kv_append_fp8(void* stream, int dtype, const void* qkv, uint8_t* k_q, int8_t* k_e, uint8_t* v_q, int8_t* v_e, int B, int T, int H,
+                        int Hkv, int Dh, int cap, int pos0);
+
+/* setok_attention_decode_gqa over the fp8 cache: q and out in `dtype`, the keys / values K', V' as stored.  Everything that call states holds
+ * here — which keys count, zeros for a sequence without one, fp32 softmax, the probabilities rounded to the 16-bit element type before they
+ * multiply V, one read of each cache byte per group of query heads, chunk partials merged in chunk order by a second launch, output bits that
+ * depend on the sequence's own operands and `len` alone — with SETOK_DECODE_CHUNK_FP8KV in the place of SETOK_DECODE_CHUNK:
+ * ws_floats >= B * H * ceil(len / SETOK_DECODE_CHUNK_FP8KV) * (Dh + 2).  2^e of a K row multiplies the finished dot product, 2^e of a V row the
+ * rounded probability (both exact).  A slot that does not count (>= len, or masked) may hold ANY code and ANY exponent byte, values outside
+ * [-15, 7] included: it is discarded by selection and no scale is ever built from its exponent.  Dh % 8 == 0; Dh in {16, 32, 64, 128} take the
+ * lane-layout kernel, the others a generic one.  q, k_q and v_q 16-byte aligned. */
+int setok_attention_decode_gqa_fp8kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const int8_t* k_e,
+                                     const uint8_t* v_q, const int8_t* v_e, const uint8_t* key_mask, void* out, int B, int H, int Hkv, int Dh,
+                                     int cap, int len, float scale, float* ws, int64_t ws_floats);
+
 /* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
  * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest
  * (csrc/diffusion.hip).  Every entry is asynchronous on `stream`, allocates nothing, synchronises nothing, accepts rows == 0, uses 16-byte

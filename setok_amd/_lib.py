@@ -109,6 +109,8 @@ SIGNATURES = {
     "setok_dequantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _i],
     "setok_linear_fp8w": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i],
     "setok_linear_fp8w_wgs": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i],
+    "setok_kv_append_fp8": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
+    "setok_attention_decode_gqa_fp8kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_timestep_embedding": [_vp, _i, _vp, _vp, _i, _i, _f],
     "setok_add_silu": [_vp, _i, _vp, _vp, _i64, _vp, _i, _i],
     "setok_adaln_modulate": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _f],

@@ -18,40 +18,12 @@
 // widest band of 1, 2, 4 column tiles (at most 2 at two row tiles, 1 at one) that leaves every CU a workgroup (fp8w_dispatch).  DESIGN.md §7 f7
 // has the resource report and the measurements.
 #include "common.h"
+#include "fp8.h"
 
 constexpr int FP8W_BN = 16;          // output columns per column tile: one MFMA tile; a workgroup owns NT of them
 constexpr int FP8W_WAVES = 4;        // waves per workgroup: the K split
 constexpr int FP8W_MAX_M = 64;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;      // 16 bytes as they come from memory
-
-// ---- e4m3fn <-> fp32 -------------------------------------------------------------------------------------------------------------------------
-__device__ inline float fp8w_scale(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }      // 2^e exactly, e in [-15, 7]
-
-// round-to-nearest-even to OCP e4m3fn (subnormals included), saturating at +-448; v is finite
-__device__ inline unsigned fp8w_encode(float v) {
-    const unsigned sign = (__builtin_bit_cast(unsigned, v) >> 24) & 0x80u;
-    const float a = fminf(fabsf(v), 448.0f);
-    unsigned code;
-    if (a < 0.015625f) {                                           // below 2^-6: multiples of 2^-9 (8 rounds up into the first normal code, 0x08)
-        code = (unsigned)rintf(a * 512.0f);
-    } else {
-        unsigned b = __builtin_bit_cast(unsigned, a);
-        b += 0x7ffffu + ((b >> 20) & 1u);                          // nearest even at 3 mantissa bits; a carry walks into the exponent
-        code = (((b >> 23) - 120u) << 3) | ((b >> 20) & 7u);       // biased exponent 127 + x -> 7 + x
-    }
-    return sign | code;
-}
-
-// the 16 values of a lane's 16 weight bytes, in byte order
-__device__ inline void fp8w_decode16(const u32x4& w, float* f) {
-    const unsigned u[4] = {w[0], w[1], w[2], w[3]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[i], false);
-        const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[i], true);
-        f[4 * i + 0] = lo[0]; f[4 * i + 1] = lo[1]; f[4 * i + 2] = hi[0]; f[4 * i + 3] = hi[1];
-    }
-}
+// (e4m3fn <-> fp32 and the row-exponent rule: fp8.h, shared with the fp8 KV cache of attn_decode.hip)
 
 // ---- the quantiser: one workgroup per row, two passes, no atomics ------------------------------------------------------------------------------
 template <typename T>
@@ -69,13 +41,7 @@ __global__ __launch_bounds__(256) void fp8w_quantize_kernel(const T* __restrict_
     if ((tid & 63) == 0) red[tid >> 6] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    // the smallest e with amax <= 448 * 2^e = 1.75 * 2^(8 + e): exponent arithmetic on amax = 1.m * 2^x (an fp32 subnormal reads as x = -127: clamped)
-    int ex = 0;
-    if (amax > 0.f) {
-        const unsigned b = __builtin_bit_cast(unsigned, amax);
-        ex = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
-        ex = ex < -15 ? -15 : (ex > 7 ? 7 : ex);
-    }
+    const int ex = fp8w_exponent(amax);                            // the smallest e with amax <= 448 * 2^e, clamped; 0 for a row of zeros
     if (tid == 0) e[n] = (int8_t)ex;
     const float inv = fp8w_scale(-ex);
     uint8_t* o = q + (int64_t)n * ldq;

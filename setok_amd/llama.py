@@ -208,7 +208,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
             qkv = ops.linear(y, self._w(L["wqkv"]))                      # (_w: the operand itself; fp8 storage dequantises it into the scratch buffer first)
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
             if cache is not None:
-                ops.kv_append(qkv, cache.k[li], cache.v[li], T, H, 0)
+                cache.append(li, qkv, T, H, 0)                                  # (the cache's own format; the prefill attends over qkv itself)
             o = ops.attention_causal(qkv, km, B, T, H, dh, dh ** -0.5, Hkv)
             ops.linear(o, self._w(L["wo"]), residual=x, out=x)
             y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
@@ -235,9 +235,9 @@ class LlamaModel(PackCacheMixin, nn.Module):
         if cache is None:
             raise ValueError("LlamaModel.prefill needs a generation.KVCache to fill (forward() is the prefill without one)")
         B, T, _ = inputs_embeds.shape
-        if cache.len != 0 or cache.B != B or cache.cap < T or len(cache.k) != len(self.layers) or cache.k[0].dtype != self.norm.weight.dtype:
-            raise ValueError(f"LlamaModel.prefill: the cache (B={cache.B}, cap={cache.cap}, len={cache.len}, {len(cache.k)} layers, "
-                             f"{cache.k[0].dtype}) does not fit an empty prefill of B={B}, T={T}")
+        if cache.len != 0 or cache.B != B or cache.cap < T or cache.num_layers != len(self.layers) or cache.dtype != self.norm.weight.dtype:
+            raise ValueError(f"LlamaModel.prefill: the cache (B={cache.B}, cap={cache.cap}, len={cache.len}, {cache.num_layers} layers, "
+                             f"{cache.dtype}, {cache.kv_format}) does not fit an empty prefill of B={B}, T={T}")
         return self._forward(inputs_embeds, attention_mask, position_ids, cache)
 
     @torch.no_grad()
@@ -264,8 +264,8 @@ class LlamaModel(PackCacheMixin, nn.Module):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
             qkv = ops.linear_fp8w(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
-            ops.kv_append(qkv, cache.k[li], cache.v[li], 1, H, slot)
-            o = ops.attention_decode(qkv, cache.k[li], cache.v[li], cache.key_mask, H, slot + 1, dh ** -0.5, ws=ws, out=o)
+            cache.append(li, qkv, 1, H, slot)                                       # (native or fp8: the cache's format decides these two calls)
+            o = cache.attend(li, qkv, H, slot + 1, dh ** -0.5, ws, o)
             if fp8:                                                                 # the same step on the fp8 bytes: four weight-streaming GEMMs
                 ops.linear_fp8w(o, *L["wo"], residual=x, out=x, scratch=big)
                 y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
@@ -429,7 +429,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     @torch.no_grad()
     def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
                  eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
-                 output_hidden_states: bool = False, output_logits: bool = False, images=None, **unsupported):
+                 output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", **unsupported):
         """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
         the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
         embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
@@ -440,6 +440,10 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         per step).  `return_dict_in_generate` returns a generation.GenerateOutput: sequences, hidden_states (B, n_new, D) with
         `output_hidden_states` — row j is the final-norm state that produced token j, what the reference hands its image head (:363-379) — and
         logits (B, n_new, V) with `output_logits`.  Passing `inputs_embeds` (the spliced embeddings) is a superset of the reference, which raises.
+
+        `kv_cache="fp8"` keeps the cache as e4m3fn rows with one power-of-two exponent per row (generation.KVCache, half the bytes of a 16-bit
+        cache): the prefill is unchanged, a decode step quantises the new token's k / v on append and attends over the stored values.  It is
+        independent of `quantize_fp8_()`.  "native" (the default) is the cache in the model's element type.
 
         Greedy is the implemented mode: `do_sample=True`, a temperature / top-p / top-k or beams raise NotImplementedError (the reference's own
         defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here).  A
@@ -458,6 +462,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             comp_images = images
         if max_new_tokens < 1:
             raise ValueError("SetokimLlamaPrefill.generate: max_new_tokens must be at least 1")
+        if kv_cache not in KVCache.FORMATS:
+            raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8'")
         embeds, am, pos, _ = self._embed(inputs, attention_mask, position_ids, inputs_embeds, None, comp_images)
         B, T, D = embeds.shape
         dev = self.lm_head.weight.device
@@ -473,7 +479,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         if eos_token_id is not None:
             eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), dtype=torch.int64, device=dev)
             pad = int(eos[0]) if pad_token_id is None else int(pad_token_id)
-        cache = KVCache.for_model(self.model, B, T + max_new_tokens, dev)
+        cache = KVCache.for_model(self.model, B, T + max_new_tokens, dev, kv_format=kv_cache)
         hidden = self.model.prefill(embeds.to(dev), am, pos, cache)
         if am is None:
             h = hidden[:, -1].contiguous()

@@ -715,9 +715,9 @@ def kv_append(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, T: int, H: int, pos
     _lib.call("setok_kv_append", _stream(), _code(qkv.dtype), _p(qkv), _p(k_cache), _p(v_cache), B, T, H, Hkv, Dh, cap, pos0)
 
 
-def attention_decode_workspace(B: int, H: int, Dh: int, length: int) -> int:
-    """Floats of workspace setok_attention_decode_gqa needs for `length` candidate slots."""
-    return B * H * ((length + DECODE_CHUNK - 1) // DECODE_CHUNK) * (Dh + 2)
+def attention_decode_workspace(B: int, H: int, Dh: int, length: int, chunk: int = DECODE_CHUNK) -> int:
+    """Floats of workspace setok_attention_decode_gqa needs for `length` candidate slots (chunk=DECODE_CHUNK_FP8KV: the fp8-cache call)."""
+    return B * H * ((length + chunk - 1) // chunk) * (Dh + 2)
 
 
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tensor, H: int, length: int, scale: float,
@@ -737,6 +737,42 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tens
     assert out.shape == (B, H * Dh) and out.dtype == q.dtype
     _lib.call("setok_attention_decode_gqa", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_cache), _p(v_cache), _p(key_mask), _p(out),
               B, H, Hkv, Dh, cap, length, scale, _p(ws), ws.numel())
+    return out
+
+
+DECODE_CHUNK_FP8KV = 256                          # SETOK_DECODE_CHUNK_FP8KV of include/setok_hip.h
+
+
+def _fp8kv_shapes(k_q: Tensor, k_e: Tensor, v_q: Tensor, v_e: Tensor) -> Tuple[int, int, int, int]:
+    B, Hkv, cap, Dh = k_q.shape
+    assert v_q.shape == k_q.shape and k_q.dtype == v_q.dtype == torch.uint8 and k_q.is_contiguous() and v_q.is_contiguous()
+    assert k_e.shape == v_e.shape == (B, Hkv, cap) and k_e.dtype == v_e.dtype == torch.int8 and k_e.is_contiguous() and v_e.is_contiguous()
+    return B, Hkv, cap, Dh
+
+
+def kv_append_fp8(qkv: Tensor, k_q: Tensor, k_e: Tensor, v_q: Tensor, v_e: Tensor, T: int, H: int, pos0: int) -> None:
+    """kv_append into an fp8 cache: the post-rotary k / v rows of qkv are quantised (e4m3fn codes + one power-of-two exponent per row, the
+    rule of quantize_fp8_rows) into slots [pos0, pos0 + T) of k_q / v_q (B, Hkv, cap, Dh) uint8 and k_e / v_e (B, Hkv, cap) int8."""
+    B, Hkv, cap, Dh = _fp8kv_shapes(k_q, k_e, v_q, v_e)
+    assert qkv.shape == (B * T, (H + 2 * Hkv) * Dh) and qkv.is_contiguous()
+    _lib.call("setok_kv_append_fp8", _stream(), _code(qkv.dtype), _p(qkv), _p(k_q), _p(k_e), _p(v_q), _p(v_e), B, T, H, Hkv, Dh, cap, pos0)
+
+
+def attention_decode_fp8kv(q: Tensor, k_q: Tensor, k_e: Tensor, v_q: Tensor, v_e: Tensor, key_mask: Tensor, H: int, length: int, scale: float,
+                           ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """attention_decode over an fp8 cache (the keys / values are value(code) * 2^exponent, exactly); q and the result in q.dtype."""
+    B, Hkv, cap, Dh = _fp8kv_shapes(k_q, k_e, v_q, v_e)
+    assert q.shape[0] == B and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, cap)
+    need = attention_decode_workspace(B, H, Dh, length, DECODE_CHUNK_FP8KV)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_decode_gqa_fp8kv", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_q), _p(k_e), _p(v_q), _p(v_e),
+              _p(key_mask), _p(out), B, H, Hkv, Dh, cap, length, scale, _p(ws), ws.numel())
     return out
 
 

@@ -7,6 +7,7 @@ to produce token n + 1 before: the whole prefill again over the sequence grown b
     python tools/bench_generate.py --weights fp8 ...                    # any of the above with the stack in fp8 storage (quantize_fp8_)
     python tools/bench_generate.py --compare-weights [--rounds 3]       # native and fp8 arms alternated in one process: decode step + the four GEMMs
     python tools/bench_generate.py --compare-bands [--rounds 3]         # linear_fp8w's 16 / 32 / 64-column bands alternated in one process, four GEMMs
+    python tools/bench_generate.py --compare-kv [--attention-only]      # native and fp8 KV caches alternated in one process: the decode step, or the attention pair alone
 
 Prints one JSON line.  Per batch size, in one process:
   (a) ms per token the old way: forward(inputs_embeds of T' + 1 positions, last_token_only=True);
@@ -154,6 +155,88 @@ def _compare_weights(a, g, dev, dt, rnd):
         peak_bytes=torch.cuda.max_memory_allocated())))
 
 
+def _fp8_twin(c):
+    """The fp8 cache that holds what the native cache `c` holds, quantised row by row (the library's own quantiser: the same rule)."""
+    from setok_amd import ops
+    from setok_amd.generation import KVCache
+    f = KVCache(len(c.k), c.B, c.Hkv, c.cap, c.Dh, c.dtype, c.key_mask.device, kv_format="fp8")
+    for li in range(len(c.k)):
+        for src, q, e in ((c.k[li], f.k_q[li], f.k_e[li]), (c.v[li], f.v_q[li], f.v_e[li])):
+            ops.quantize_fp8_rows(src.view(-1, c.Dh), q=q.view(-1, c.Dh), e=e.view(-1))
+    f.key_mask.copy_(c.key_mask)
+    f.next_pos.copy_(c.next_pos)
+    f.len = c.len
+    return f
+
+
+def _compare_kv(a, g, dev, dt, rnd):
+    """The native and the fp8 KV cache in ONE process, alternated round by round after a warm-up, every timing ended by a device synchronise,
+    `--rounds` runs of `--reps` steps per arm: the decode step of one model over the two caches — or, with --attention-only, the decode-attention
+    launch pair over every layer's cache — at cache lengths prompt + 1 and prompt + new, with the pair's rate in TB/s of LIVE cache bytes (codes
+    + exponents in the fp8 arm).  The fp8 cache holds the native cache's random rows, quantised.  Every run is appended to `--out`."""
+    from setok_amd import ops
+    from setok_amd.generation import KVCache
+    T, N = a.prompt, a.new
+    llm = None if a.attention_only else _llm(a.layers, g, dev, dt)      # (the pair needs no model: one cache per layer, as a step has)
+    res = {}
+    for B in [int(b) for b in a.batches.split(",")]:
+        native = KVCache(a.layers, B, H, T + N, DH, dt, dev)
+        for t in native.k + native.v:
+            t.normal_(0.0, 1.0, generator=g)
+        _set_len(native, T)
+        caches = {"native": native, "fp8": _fp8_twin(native)}
+        e1, q = rnd(B, D), rnd(B, 3 * D)
+        out = torch.empty(B, H * DH, dtype=dt, device=dev)
+        rb = dict(kv_cache_gb={k: round(c.nbytes() / 1e9, 3) for k, c in caches.items()})
+        for length in (T + 1, T + N):
+            def pair(k):
+                c = caches[k]
+                ws = c.workspace(H)
+                return [c.attend(li, q, H, length, DH ** -0.5, ws, out) for li in range(a.layers)]
+
+            def step(k):
+                _set_len(caches[k], length - 1)
+                return llm.model.decode_step(e1, caches[k])
+
+            fn = pair if a.attention_only else step
+            for c in caches.values():
+                _set_len(c, length)                                      # (the pair reads the mask of `length` slots)
+            for k in caches:
+                _time(lambda: fn(k), 1)                                  # warm-up of both arms before the first timed round
+            runs = {k: [] for k in caches}
+            for _ in range(a.rounds):
+                for k in caches:
+                    runs[k].append(_time(lambda: fn(k), a.reps))
+            r = {k: _spread(v) for k, v in runs.items()}
+            r["fp8_over_native_median"] = round(r["fp8"]["median"] / r["native"]["median"], 3)
+            r["faster_by_more_than_the_spread"] = r["fp8"]["max"] < r["native"]["min"]
+            if a.attention_only:
+                rows = 2.0 * a.layers * B * H * length                   # K and V rows the pair reads (Hkv = H)
+                for k, per_row in (("native", DH * 2), ("fp8", DH + 1)):
+                    r[k]["live_cache_gb"] = round(rows * per_row / 1e9, 3)
+                    r[k]["tb_per_s"] = round(rows * per_row / (r[k]["median"] * 1e-3) / 1e12, 3)
+            rb[f"len{length}"] = r
+        res[f"B{B}"] = rb
+        del caches, native
+        torch.cuda.empty_cache()
+    what = "decode-attention launch pair (chunks + merge) over all layers' caches" if a.attention_only else "decode step"
+    run = dict(workload=f"cfg5 LLM decode, Llama at Vicuna-7B dims, bf16: the KV cache native (bf16) against fp8 e4m3 rows + a power-of-two exponent "
+                        f"per row; ms per {what}, arms alternated in one process",
+               measured="attention_pair" if a.attention_only else "decode_step", layers=a.layers, prompt=T, new_tokens=N, reps=a.reps, rounds=a.rounds,
+               decode_chunk=dict(native=ops.DECODE_CHUNK, fp8=ops.DECODE_CHUNK_FP8KV), device=torch.cuda.get_device_name(0), results=res,
+               peak_bytes=torch.cuda.max_memory_allocated())
+    runs = []
+    if os.path.isfile(a.out):
+        with open(a.out) as f:
+            runs = json.load(f)
+    runs.append(run)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(runs, f, indent=1)
+        f.write("\n")
+    print(json.dumps(run))
+
+
 def _compare_bands(a, g, dev, dt, rnd):
     """`linear_fp8w` at the four layer shapes with the band named through the floor of its rule (`min_wgs`; setok_linear_fp8w_wgs): 16, 32 and
     64 columns per workgroup where the row tiles allow them, and the library's own choice.  One process, the arms alternated round by round,
@@ -203,6 +286,9 @@ def main():
     ap.add_argument("--weights", choices=("native", "fp8"), default="native")
     ap.add_argument("--compare-weights", action="store_true")
     ap.add_argument("--compare-bands", action="store_true")
+    ap.add_argument("--compare-kv", action="store_true")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "generate_fp8kv_bench.json"),
+                    help="--compare-kv appends its run to this JSON list")
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     from setok_amd import ops
@@ -211,6 +297,10 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float32).to(dt)
     T, N = a.prompt, a.new
+
+    if a.compare_kv:
+        _compare_kv(a, g, dev, dt, rnd)
+        return
 
     if a.attention_only:                             # one GQA shape, K / V well past the 256 MiB the last cache level holds; two launches of the pair
         B, Hkv, n = 32, H // a.gqa, 4000
