@@ -531,6 +531,33 @@ int setok_attention_decode_gqa(void* stream, int dtype, const void* q, int64_t l
  * a NaN counts as the maximum.  Deterministic. */
 int setok_argmax_rows(void* stream, int dtype, const void* x, int64_t ld, int rows, int V, int64_t* out);
 
+/* ---- Sampling (csrc/sample.hip): `do_sample=True` of HF GenerationMixin with TemperatureLogitsWarper, TopKLogitsWarper and TopPLogitsWarper in
+ * HF's order, which is what SetokimLlamaForCausalLM.generate asks for (setokim_llama.py:341-356).  The draw itself is one uniform number per row,
+ * and that number is an INPUT: out[r] is a pure function of (row r of the logits, u[r], temperature, top_k, top_p), the same bits in every run.
+ * Pure addition: the ABI version stays 9.
+ *
+ * Per row (logits: rows x V in `dtype`, row stride ld >= V elements, any alignment; columns >= V are never read):
+ *   1. s_i = float(logit_i) / temperature in fp32 (HF casts the step's logits to fp32 before its processors, for every model dtype).
+ *   2. top-k (top_k > 0): keep i iff s_i >= the top_k-th largest value of the row; ties at the threshold are all kept.  top_k == 0 and
+ *      top_k >= V mean no filter.
+ *   3. top-p (top_p < 1): keep i iff the probability mass of the kept tokens with a STRICTLY LARGER score is < top_p, probabilities taken over the
+ *      set that survived top-k.  Equal scores are kept or dropped together; the top token always survives.  (HF sorts and cuts inside a run of
+ *      equal scores by sort position; on rows without ties at the cut the kept sets are identical.)
+ *   4. Fixed-point weights: w_i = rint(exp(s_i - max s) * 2^32) as a 64-bit integer, 0 for a filtered token.  Every later sum - histogram masses,
+ *      the normaliser W = sum of the kept w_i, the prefix - is an integer sum, exact in any association.  A token whose probability is below
+ *      2^-33 of the maximum's has weight 0: it cannot be drawn and its `probs` entry is 0.
+ *   5. The draw: u24 = (uint32)(clamp(u[r], 0, 1 - 2^-24) * 2^24); target = (W * u24) >> 24 through the 128-bit product; out[r] (int64) = the
+ *      unique i, in INDEX order, with prefix_i <= target < prefix_i + w_i (prefix_i = the sum of w_j, j < i).
+ *   6. A row that contains a NaN or +inf, or has no finite entry, is bad: out[r] = -1 and, when given, zeros in its `probs` row (HF raises
+ *      "probability tensor contains either inf, nan or element < 0").  The other rows are unaffected.
+ *   7. probs (may be NULL): (rows, V) fp32, row stride ld_probs >= V, receives w_i / W.
+ * Refused on the host before any launch (-1, setok_last_error): a null logits / u / out, V < 1 or V > 2^20, ld < V, ld_probs < V with probs,
+ * a temperature that is not finite or <= 0, top_k < 0, top_p outside (0, 1], a dtype the library does not serve.  rows == 0 launches nothing.
+ * One workgroup of 1024 threads per row; the row is read from memory once and kept in LDS as fp32 (V <= 36864; a longer row is re-read through
+ * L2 by every pass).  No float atomics and no float prefix sums anywhere. */
+int setok_sample_rows(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u, float temperature, int top_k,
+                      float top_p, int64_t* out, float* probs, int64_t ld_probs);
+
 /* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip): the decode step streams every projection weight once per token, so the stack's Linear
  * weights may be STORED as OCP e4m3fn bytes with one power-of-two scale per output row.  A matrix W (N, K) becomes q (N, K) uint8 + e (N,) int8 and
  * means exactly

@@ -5,6 +5,7 @@ keeps between steps as HF's `past_key_values` (:99,133,189), and what it returns
 one slot for all sequences.  The loop itself is `SetokimLlamaPrefill.generate` (llama.py)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -76,6 +77,49 @@ class KVCache:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1), dtype=torch.float32, device=self.key_mask.device)
         return self._ws
+
+
+class Sampler:
+    """Sampled token selection for `SetokimLlamaPrefill.generate(sampler=...)`: temperature, then top-k, then top-p (HF's order), one launch of
+    `setok_sample_rows` per step (include/setok_hip.h, "Sampling", states the rule).  The draw is one uniform number per row per step and that
+    number is an input of the kernel, so a run is reproducible from its uniforms alone:
+
+      u=          (max_new_tokens, B) float32 in [0, 1): step j uses row j.  The reproducible path.
+      generator=  otherwise step j draws `torch.rand(B, generator=generator, device=...)` (the device's default generator when None).
+
+    One uniform is consumed per row per step whether or not the row has finished, so a row's stream does not depend on its neighbours.
+    `top_k=0` and `top_p=1.0` mean no filter.  The arguments are validated like the C call's and raise ValueError."""
+
+    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, generator: Optional[torch.Generator] = None,
+                 u: Optional[torch.Tensor] = None):
+        temperature, top_p = float(temperature), float(top_p)
+        if not math.isfinite(temperature) or temperature <= 0.0:
+            raise ValueError(f"Sampler: temperature={temperature} must be finite and > 0 (greedy decoding is generate(sampler=None) or top_k=1)")
+        if isinstance(top_k, bool) or int(top_k) != top_k or int(top_k) < 0:
+            raise ValueError(f"Sampler: top_k={top_k!r} must be an integer >= 0 (0 = no filter)")
+        if not (0.0 < top_p <= 1.0):
+            raise ValueError(f"Sampler: top_p={top_p} is not a probability: it must lie in (0, 1] (1.0 = no filter; the reference's default "
+                             "top_p=10.0 is not a valid nucleus either)")
+        if u is not None:
+            if generator is not None:
+                raise ValueError("Sampler: pass the uniforms as `u` or a `generator` to draw them, not both")
+            if u.dim() != 2 or u.dtype != torch.float32:
+                raise ValueError(f"Sampler: u must be a (max_new_tokens, B) float32 tensor, got {tuple(u.shape)} {u.dtype}")
+        self.temperature, self.top_k, self.top_p, self.generator, self.u = temperature, int(top_k), top_p, generator, u
+
+    def uniforms(self, step: int, B: int, device) -> torch.Tensor:
+        """The (B,) float32 uniforms of decode step `step`, on `device`."""
+        if self.u is not None:
+            if step >= self.u.shape[0] or self.u.shape[1] != B:
+                raise ValueError(f"Sampler: u has shape {tuple(self.u.shape)}, step {step} of a batch of {B} needs (at least {step + 1}, {B})")
+            if self.u.device != torch.device(device):
+                self.u = self.u.to(device)                                         # once: a step's row is then a view, no copy per step
+            return self.u[step]
+        return torch.rand(B, generator=self.generator, device=device, dtype=torch.float32)
+
+    def select(self, logits: torch.Tensor, step: int) -> torch.Tensor:
+        """int64 (B,): the step's tokens, -1 for a row whose logits hold a NaN or +inf or no finite entry."""
+        return ops.sample_rows(logits, self.uniforms(step, logits.shape[0], logits.device), self.temperature, self.top_k, self.top_p)
 
 
 @dataclass

@@ -284,6 +284,17 @@ class LlamaModel(PackCacheMixin, nn.Module):
 _SAMPLING_ARGS = ("temperature", "top_p", "top_k", "num_beams", "penalty_alpha", "repetition_penalty")      # generate(): named so that they are refused by name
 
 
+def _raise_undrawable(raws) -> None:
+    """generate(sampler=...): `raws` holds every step's tokens as drawn, (B,) each, -1 where a row's logits could not be drawn from."""
+    if not raws:
+        return
+    bad = (torch.stack(raws, dim=1) < 0).nonzero().cpu().tolist()                  # (sequence, step) pairs, sequence-major
+    if bad:
+        b, s = min(bad, key=lambda bs: (bs[1], bs[0]))                             # the first step, its first sequence
+        raise RuntimeError(f"SetokimLlamaPrefill.generate: the logits of sequence {b} at step {s} contain a NaN or +inf, or no finite entry: "
+                           f"no token can be drawn ((sequence, step) pairs affected: {bad[:8]}{' ...' if len(bad) > 8 else ''})")
+
+
 def _refuse_unsupported_llama_fields(g) -> None:
     """The prefill reads hidden / intermediate sizes, layer and head counts, `num_key_value_heads`, `rms_norm_eps` and `rope_theta` — plain
     multi-head or grouped-query Llama (Vicuna-7B, the reference's LLM: scripts/finetune.sh).  A checkpoint whose config carries anything
@@ -429,7 +440,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     @torch.no_grad()
     def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
                  eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
-                 output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", **unsupported):
+                 output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", sampler=None, **unsupported):
         """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
         the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
         embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
@@ -445,10 +456,16 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         cache): the prefill is unchanged, a decode step quantises the new token's k / v on append and attends over the stored values.  It is
         independent of `quantize_fp8_()`.  "native" (the default) is the cache in the model's element type.
 
-        Greedy is the implemented mode: `do_sample=True`, a temperature / top-p / top-k or beams raise NotImplementedError (the reference's own
-        defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here).  A
+        `sampler=` (a generation.Sampler: temperature, top_k, top_p and the uniforms, given or drawn from a generator) replaces the step's argmax
+        by one `setok_sample_rows` launch; everything else in the loop is the same, and `sampler=None` is the greedy path bit for bit.  A row
+        whose logits hold a NaN or +inf (HF: "probability tensor contains either inf, nan") raises RuntimeError naming the sequence and the step:
+        at the per-step host read when `eos_token_id` is given, otherwise once after the loop.
+
+        HF's own spelling stays refused: `do_sample=True`, temperature= / top_p= / top_k= or beams raise NotImplementedError (the reference's
+        defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here: pass a
+        `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
-        from .generation import GenerateOutput, KVCache
+        from .generation import GenerateOutput, KVCache, Sampler
         sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
         if do_sample or sampling:
             raise NotImplementedError(f"SetokimLlamaPrefill.generate: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "
@@ -464,6 +481,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             raise ValueError("SetokimLlamaPrefill.generate: max_new_tokens must be at least 1")
         if kv_cache not in KVCache.FORMATS:
             raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8'")
+        if sampler is not None and not isinstance(sampler, Sampler):
+            raise TypeError(f"SetokimLlamaPrefill.generate: sampler must be a generation.Sampler or None, got {type(sampler).__name__}")
         embeds, am, pos, _ = self._embed(inputs, attention_mask, position_ids, inputs_embeds, None, comp_images)
         B, T, D = embeds.shape
         dev = self.lm_head.weight.device
@@ -490,9 +509,15 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         w_e = self.model.embed_tokens.weight.detach().contiguous()
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         toks, hids, lgs = [], [], []
+        raws = []                                                                  # sampler only: the tokens as drawn, -1 where a row could not be drawn from
         for step in range(max_new_tokens):
             logits = ops.linear(h, w_lm)                                           # (B, V): never copied to the host
-            tok = ops.argmax_rows(logits)
+            if sampler is None:
+                tok = ops.argmax_rows(logits)
+            else:
+                raw = sampler.select(logits, step)
+                raws.append(raw)
+                tok = raw.clamp_min(0)                                             # a valid row for the embedding lookup; the error is raised below
             if eos is not None:
                 tok = torch.where(finished, torch.full_like(tok, pad), tok)
                 finished = finished | torch.isin(tok, eos)
@@ -501,10 +526,16 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                 hids.append(h)
             if output_logits:
                 lgs.append(logits)
-            if step + 1 == max_new_tokens or (eos is not None and bool(finished.all())):
+            if step + 1 == max_new_tokens:
                 break
+            if eos is not None:
+                stop = finished.all() if sampler is None else finished.all() | (raw < 0).any()
+                if bool(stop):                                                     # the one host read per step
+                    _raise_undrawable(raws)                                        # raises iff a row could not be drawn; else every sequence has finished
+                    break
             e = ops.splice_rows(tok.to(torch.int32).reshape(B, 1), w_e, None)      # embed_tokens on the new ids
             h = self.model.decode_step(e.reshape(B, D), cache)
+        _raise_undrawable(raws)
         seq = torch.stack(toks, dim=1)
         if not return_dict_in_generate:
             return seq

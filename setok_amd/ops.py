@@ -787,6 +787,26 @@ def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+def sample_rows(logits: Tensor, u: Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, out: Optional[Tensor] = None,
+                probs: Optional[Tensor] = None) -> Tensor:
+    """int64 (rows,): the token each row of `logits` (rows, V; any row stride) draws with its uniform u[r] (fp32, (rows,)) after temperature, top-k
+    and top-p in HF's order (include/setok_hip.h, "Sampling"); -1 for a row with a NaN, +inf or no finite entry.  `probs` (rows, V) fp32, if
+    given, receives the distribution drawn from."""
+    rows, V = logits.shape
+    assert logits.stride(1) == 1 and logits.is_cuda
+    assert u.dtype == torch.float32 and u.numel() == rows
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and out.numel() == rows
+    ldp = 0
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.shape == (rows, V) and probs.stride(1) == 1 and probs.is_cuda
+        ldp = probs.stride(0) if rows > 1 else max(probs.stride(0), V)
+    _lib.call("setok_sample_rows", _stream(), _code(logits.dtype), logits.data_ptr(), logits.stride(0) if rows > 1 else max(logits.stride(0), V), rows, V,
+              _p(u), float(temperature), int(top_k), float(top_p), _p(out), None if probs is None else probs.data_ptr(), ldp)
+    return out
+
+
 # ---- fp8 weight-only storage (csrc/gemm_fp8w.hip) -----------------------------------------------------------------------------------------------
 FP8W_MAX_M = 64                                   # rows setok_linear_fp8w takes; more rows dequantise and go through `linear`
 
