@@ -531,6 +531,47 @@ int setok_attention_decode_gqa(void* stream, int dtype, const void* q, int64_t l
  * a NaN counts as the maximum.  Deterministic. */
 int setok_argmax_rows(void* stream, int dtype, const void* x, int64_t ld, int rows, int V, int64_t* out);
 
+/* ---- Extending a cache (csrc/attn_extend.hip): Tn >= 1 new tokens per sequence against a cache that already holds len0 older slots — chunked
+ * prefill, the next turn of a conversation, scoring several candidate tokens in one pass (HF LlamaAttention.forward with `past_key_values` on a
+ * Tn-token input).  setok_kv_append with T = Tn, pos0 = len0 runs first, unchanged.  Pure additions: the ABI version stays 9. */
+
+/* Keys of one chunk of the extend attention, counted from slot 0: its work is cut over (chunk, key / value head x tile of stacked query rows,
+ * sequence).  A constant, so that how a row's keys are partitioned (and every summation order with it) depends on len0, Tn, the row and the mask
+ * alone.  256 and not SETOK_DECODE_CHUNK: every (query row, query head, chunk) leaves Dh + 2 fp32 partials, and with Tn rows per sequence those are the
+ * call's largest traffic and its workspace; 2048 cached slots still give 9 chunks x Hkv workgroups per sequence at Tn = 8. */
+#define SETOK_EXTEND_CHUNK 256
+/* Chunks a workgroup of the MFMA kernel (head dim 128 in the 16-bit type) carries its online softmax across before it writes a partial, when a group
+ * brings more than 32 stacked rows (H / Hkv * Tn > 32): with hundreds of rows per sequence the partials are the call's largest traffic.  A rule in
+ * H / Hkv * Tn alone, so what the bits depend on does not change. */
+#define SETOK_EXTEND_SPAN 4
+
+/* Floats of workspace setok_attention_extend_gqa needs for the same arguments: B * Tn * H * P * (Dh + 2), P partials per (query row, query head):
+ * P = ceil((len0 + Tn) / SETOK_EXTEND_CHUNK), or — the MFMA kernel (this build's 16-bit `dtype`, Dh = 128) with H / Hkv * Tn > 32 —
+ * P = ceil((len0 + Tn) / (SETOK_EXTEND_SPAN * SETOK_EXTEND_CHUNK)).  The ONE statement of that rule: hosts size their workspace by this call.  With
+ * SETOK_F32 it is the first formula, which suffices for every dtype.  0 for shapes the entry point refuses. */
+int64_t setok_attention_extend_workspace(int dtype, int B, int Tn, int H, int Hkv, int Dh, int len0);
+
+/* eager_attention_forward for Tn new tokens per sequence.  q: rows b * Tn + i of the step's fused post-rotary [q | k | v] buffer, read in place with
+ * row stride ldq elements (H heads of Dh).  k_cache, v_cache: (B, Hkv, cap, Dh) in `dtype`; they already hold the new tokens' keys and values in
+ * slots [len0, len0 + Tn).  key_mask: (B, cap) uint8.  out: (B * Tn, H * Dh).
+ * The rule for which keys count:
+ *   - Query i of sequence b counts slot j iff j <= len0 + i and key_mask[b][j] != 0.
+ *   - A query with no counted key gets zeros.  This is the convention of setok_attention_causal_gqa and setok_attention_decode_gqa.
+ *   - Slots that do not count are never allowed to reach the output, whatever bytes they hold.  This covers slots >= len0 + Tn.  It also covers
+ *     slots > len0 + i, which hold real keys of later queries.
+ * Slots >= len0 + Tn are never read; a masked slot below len0 + Tn is read and discarded by selection (it may hold NaN).
+ * Scores and softmax in fp32; in the 16-bit types exp(s - m) is rounded to the element type before it multiplies V, the normaliser sums the unrounded
+ * values.  len0 = 0 is a causal prefill read from the cache; Tn = 1 agrees with setok_attention_decode_gqa to tolerance, not to the bit (another chunk
+ * length, another summation order).  Each K / V byte of a (sequence, key / value head) is read once per 128 stacked (query row, group head) rows.
+ * workspace: fp32, 8-byte aligned, workspace_floats >= setok_attention_extend_workspace(dtype, B, Tn, H, Hkv, Dh, len0): per (sequence, query row,
+ * query head, chunk) the chunk's maximum, sum and Dh accumulators, merged in chunk order by a second launch: no atomics.  A row's output bits depend only on its sequence's
+ * q, keys, values, mask, len0, Tn and i: not on B, not on cap, not on the run.  Dh % 8 == 0; Dh = 128 in the 16-bit type runs the MFMA kernel, everything
+ * else a generic wave-per-(row, head, chunk) kernel.  Refused on the host (-1, setok_last_error): null operands, bad shapes, len0 + Tn > cap, a
+ * workspace that is too small. */
+int setok_attention_extend_gqa(void* stream, int dtype, const void* q, int64_t ldq, const void* k_cache, const void* v_cache, const uint8_t* key_mask,
+                               void* out, int B, int Tn, int H, int Hkv, int Dh, int cap, int len0, float scale, float* workspace,
+                               int64_t workspace_floats);
+
 /* ---- Sampling (csrc/sample.hip): `do_sample=True` of HF GenerationMixin with TemperatureLogitsWarper, TopKLogitsWarper and TopPLogitsWarper in
  * HF's order, which is what SetokimLlamaForCausalLM.generate asks for (setokim_llama.py:341-356).  The draw itself is one uniform number per row,
  * and that number is an INPUT: out[r] is a pure function of (row r of the logits, u[r], temperature, top_k, top_p), the same bits in every run.

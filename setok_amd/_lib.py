@@ -35,7 +35,8 @@ class SetokConfig(C.Structure):
                 ("min_cluster_num", _i), ("threshold", _f), ("dtype", _i), ("fold_layernorm", _i)]
 
 
-RESTYPES = {"setok_last_error": C.c_char_p, "setok_ctx_error": C.c_char_p, "setok_encode_workspace_bytes": _i64, "setok_destroy": None}
+RESTYPES = {"setok_last_error": C.c_char_p, "setok_ctx_error": C.c_char_p, "setok_encode_workspace_bytes": _i64, "setok_destroy": None,
+            "setok_attention_extend_workspace": _i64}
 
 # name -> argtypes; mirrors include/setok_hip.h declaration by declaration
 SIGNATURES = {
@@ -105,6 +106,8 @@ SIGNATURES = {
     "setok_kv_append": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_argmax_rows": [_vp, _i, _vp, _i64, _i, _i, _vp],
+    "setok_attention_extend_workspace": [_i, _i, _i, _i, _i, _i, _i],
+    "setok_attention_extend_gqa": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_sample_rows": [_vp, _i, _vp, _i64, _i, _i, _vp, _f, _i, _f, _vp, _vp, _i64],
     "setok_quantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i, _i],
     "setok_dequantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _i],

@@ -20,6 +20,7 @@
 // A key counts iff its slot is < len and its mask byte is non-zero; a sequence without such a key gets zeros (the prefill kernel's convention).
 #include "common.h"
 #include "fp8.h"
+#include "attn_partials.h"
 
 namespace {
 
@@ -33,12 +34,6 @@ constexpr int DEC_CHUNK = SETOK_DECODE_CHUNK;
 constexpr int DEC_WAVES = 4;
 constexpr int DEC_WKEYS = DEC_CHUNK / DEC_WAVES;          // keys per wave
 static_assert(DEC_WKEYS == 32, "the wave's slice is 32 keys: NSTEP = LPR / 2 below");
-
-// exp(x) for x <= 0: the accurate expf in fp32 (parity mode), v_exp_f32 in the 16-bit types (far below the rounding of the probability)
-template <typename T> __device__ inline float dec_exp(float x) {
-    if constexpr (sizeof(T) == 4) return expf(x);
-    else return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
-}
 
 // Sum over aligned groups of N lanes (N a power of two), every lane of a group ending with the same bits: an xor butterfly.  Inside a row of 16 lanes the
 // exchanges are DPP modifiers on the add (quad_perm for xor 1 and 2; once a quad's lanes agree, row_half_mirror and row_mirror pair the same partial sums
@@ -245,29 +240,6 @@ __global__ __launch_bounds__(64) void attn_decode_any_kernel(const T* __restrict
         for (int jj = 0; jj < DEC_CHUNK; ++jj)
             if (ps[jj] != 0.f) o = fmaf(rnd<T>(ps[jj]), (float)vb[(int64_t)(j0 + jj) * Dh + d], o);      // (a non-zero weight: slot < len and unmasked)
         part[2 + d] = o;
-    }
-}
-
-// ---- merge: one workgroup per (sequence, query head), the chunks in chunk order ----------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* __restrict__ ws, T* __restrict__ out, int nch, int H, int Dh) {
-    const int64_t bh = blockIdx.x;                                     // b * H + h; out rows are H * Dh wide
-    const float* part = ws + bh * nch * (Dh + 2);
-    float M = -INFINITY;
-    for (int c = 0; c < nch; ++c) M = fmaxf(M, part[(int64_t)c * (Dh + 2)]);
-    float L = 0.f;
-    for (int c = 0; c < nch; ++c) {
-        const float mc = part[(int64_t)c * (Dh + 2)];
-        L = fmaf(mc == -INFINITY ? 0.f : dec_exp<T>(mc - M), part[(int64_t)c * (Dh + 2) + 1], L);
-    }
-    const float inv = L > 0.f ? 1.0f / L : 0.f;
-    for (int d = threadIdx.x; d < Dh; d += 64) {
-        float o = 0.f;
-        for (int c = 0; c < nch; ++c) {
-            const float mc = part[(int64_t)c * (Dh + 2)];
-            o = fmaf(mc == -INFINITY ? 0.f : dec_exp<T>(mc - M), part[(int64_t)c * (Dh + 2) + 2 + d], o);
-        }
-        out[bh * Dh + d] = (T)(o * inv);
     }
 }
 

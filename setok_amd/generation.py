@@ -2,7 +2,8 @@
 keeps between steps as HF's `past_key_values` (:99,133,189), and what it returns.
 
 `KVCache` is allocated once per `generate` call; `LlamaModel.prefill` fills slots [0, T') of every layer, every `LlamaModel.decode_step` appends
-one slot for all sequences.  The loop itself is `SetokimLlamaPrefill.generate` (llama.py)."""
+one slot for all sequences, `LlamaModel.extend` appends Tn >= 1 slots (chunked prefill, the next turn of a conversation).  The loop itself is
+`SetokimLlamaPrefill.generate` (llama.py); `GenerationState` is what it hands back so that a later call can continue from the same cache."""
 from __future__ import annotations
 
 import math
@@ -65,15 +66,43 @@ class KVCache:
             return ops.attention_decode_fp8kv(q, self.k_q[li], self.k_e[li], self.v_q[li], self.v_e[li], self.key_mask, H, length, scale, ws=ws, out=out)
         return ops.attention_decode(q, self.k[li], self.v[li], self.key_mask, H, length, scale, ws=ws, out=out)
 
+    def extend_attend(self, li: int, q: torch.Tensor, H: int, Tn: int, len0: int, scale: float, ws: torch.Tensor,
+                      out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Layer `li`: Tn query rows per (sequence, query head) against slots [0, len0 + Tn), causal inside the new rows (ops.attention_extend).  The
+        native format only: reading several query rows over e4m3 rows is a second kernel."""
+        if self.kv_format == "fp8":
+            raise NotImplementedError("KVCache.extend_attend: extending an fp8 KV cache by several tokens is not implemented (the extend attention "
+                                      "over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
+        return ops.attention_extend(q, self.k[li], self.v[li], self.key_mask, H, Tn, len0, scale, ws=ws, out=out)
+
+    def grown(self, cap: int) -> "KVCache":
+        """A cache of capacity `cap` >= self.len holding the same filled slots, mask and positions (`cap` is part of the layout, so growing copies)."""
+        if self.kv_format == "fp8":
+            raise NotImplementedError("KVCache.grown: an fp8 KV cache cannot be extended by several tokens, so it is never grown")
+        if cap < self.len:
+            raise ValueError(f"KVCache.grown: cap={cap} is below the {self.len} filled slots")
+        new = KVCache(self.num_layers, self.B, self.Hkv, cap, self.Dh, self.dtype, self.key_mask.device)
+        n = self.len
+        for dst, src in ((new.k, self.k), (new.v, self.v)):
+            for d, t in zip(dst, src):
+                d[:, :, :n].copy_(t[:, :, :n])
+        new.key_mask[:, :n].copy_(self.key_mask[:, :n])
+        new.next_pos.copy_(self.next_pos)
+        new.len = n
+        return new
+
     def nbytes(self) -> int:
         if self.kv_format == "fp8":                                    # codes + exponents
             return sum(t.numel() * t.element_size() for t in self.k_q + self.k_e + self.v_q + self.v_e)
         return sum(t.numel() * t.element_size() for t in self.k + self.v)
 
-    def workspace(self, H: int) -> torch.Tensor:
-        """The decode attention's fp32 partials, sized once for the full capacity."""
+    def workspace(self, H: int, Tn: int = 0, len0: int = 0) -> torch.Tensor:
+        """The attention's fp32 partials: the decode step's, sized once for the full capacity, or — with Tn > 0 — the larger of that and what an
+        extend of Tn rows behind len0 slots needs."""
         chunk = ops.DECODE_CHUNK_FP8KV if self.kv_format == "fp8" else ops.DECODE_CHUNK
         need = ops.attention_decode_workspace(self.B, H, self.Dh, self.cap, chunk)
+        if Tn > 0:
+            need = max(need, ops.attention_extend_workspace(self.B, Tn, H, self.Dh, len0, self.Hkv, self.dtype))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1), dtype=torch.float32, device=self.key_mask.device)
         return self._ws
@@ -123,10 +152,22 @@ class Sampler:
 
 
 @dataclass
+class GenerationState:
+    """What `generate(return_past=True)` hands back and `generate(past=...)` continues from: the `KVCache` and `pending` (B,) int64 — the last real
+    token of each sequence that the stack has not consumed yet, -1 where there is none.  The state is equivalent to each sequence having consumed
+    exactly its prompt plus its emitted tokens up to and including its first eos (all of them without an eos), the last real token possibly
+    still pending: the slots a finished sequence's pads went to are masked out and its next position is set back.  The call that continues a
+    state extends its cache in place when the capacity allows (`cache_capacity=` reserves it), so a state is continued once."""
+    cache: KVCache
+    pending: torch.Tensor
+
+
+@dataclass
 class GenerateOutput:
     """`generate(return_dict_in_generate=True)`: sequences (B, n_new) int64 — the NEW tokens only; hidden_states (B, n_new, D): row j is the final-norm
     state that produced token j (what the reference collects as `x[-1]` per step, setokim_llama.py:363, for its image head); logits (B, n_new, V)
-    when requested."""
+    when requested; past (a GenerationState) with `return_past`."""
     sequences: torch.Tensor
     hidden_states: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
+    past: Optional[GenerationState] = None

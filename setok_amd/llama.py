@@ -18,7 +18,9 @@ reads key / value head h // (H // Hkv), HF's `repeat_kv` without the copies.
 
 Generation (`SetokimLlamaForCausalLM.generate`, setokim_llama.py:329-396) is greedy decoding with a KV cache: `LlamaModel.prefill` is the same
 prefill that also fills a `generation.KVCache`, `LlamaModel.decode_step` runs one token per sequence against it (csrc/attn_decode.hip), and
-`SetokimLlamaPrefill.generate` is the loop.
+`SetokimLlamaPrefill.generate` is the loop.  `LlamaModel.extend` adds Tn >= 1 tokens per sequence to a cache that already holds
+some (csrc/attn_extend.hip): `generate(prefill_chunk=)` feeds a prompt in windows through it and `generate(past=)` continues a conversation from the
+state an earlier call returned.
 """
 from __future__ import annotations
 
@@ -280,6 +282,63 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.next_pos = pos + 1
         return ops.rmsnorm(x, pk["norm"], self.eps, out=y)
 
+    @torch.no_grad()
+    def extend(self, inputs_embeds, cache, attention_mask=None):
+        """Tn >= 1 tokens per sequence against the cache: inputs_embeds (B, Tn, D) -> the final-norm hidden states (B, Tn, D).  `decode_step`
+        generalised (chunked prefill, the next turn of a conversation, scoring several candidate tokens in one pass): the rows go to slots
+        [cache.len, cache.len + Tn) and attend causally over the older slots plus themselves (csrc/attn_extend.hip).  attention_mask (B, Tn),
+        1 = attended (None = all): row i of sequence b is rotated to cache.next_pos[b] + (the attended rows before i in the chunk); a masked row's slot
+        stays masked and its hidden state means nothing.  HF LlamaDecoderLayer.forward with `past_key_values` on a Tn-token input; the GEMMs are the
+        prefill's at M = B * Tn (fp8 weights: `decode_step`'s streaming GEMM up to FP8W_MAX_M rows, the dequantise scratch above).
+        Refused with the cache untouched: an fp8 KV cache (NotImplementedError), a wrong B, Tn == 0 on an empty cache, len + Tn > cap (ValueError)."""
+        B, Tn, D = inputs_embeds.shape
+        len0 = cache.len
+        if cache.kv_format == "fp8":
+            raise NotImplementedError("LlamaModel.extend: extending an fp8 KV cache by several tokens is not implemented (the extend attention over "
+                                      "e4m3fn rows is a follow-up kernel); use kv_cache='native'")
+        if (B != cache.B or (Tn == 0 and len0 == 0) or len0 + Tn > cache.cap or cache.num_layers != len(self.layers)
+                or cache.dtype != self.norm.weight.dtype):
+            raise ValueError(f"LlamaModel.extend: the cache (B={cache.B}, cap={cache.cap}, len={len0}, {cache.num_layers} layers, {cache.dtype}) "
+                             f"cannot take B={B} x Tn={Tn} more tokens (len + Tn > cap, a different B, or nothing to attend to)")
+        dev = inputs_embeds.device
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, Tn):
+            raise ValueError(f"LlamaModel.extend: attention_mask {tuple(attention_mask.shape)} is not (B, Tn) = ({B}, {Tn})")
+        if Tn == 0:
+            return inputs_embeds.to(self.norm.weight.dtype).reshape(B, 0, D)
+        pk = self._pack()
+        H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
+        M = B * Tn
+        x = inputs_embeds.to(self.norm.weight.dtype).reshape(M, D).contiguous().clone()
+        if attention_mask is None:
+            am = torch.ones((B, Tn), dtype=torch.int64, device=dev)
+        else:
+            am = attention_mask.to(device=dev).bool().long()
+        pos = (cache.next_pos[:, None] + am.cumsum(1) - am).reshape(M).contiguous()     # attended rows before i; a masked row gets the next row's (valid) position
+        cache.key_mask[:, len0:len0 + Tn] = am.to(torch.uint8)
+        ws = cache.workspace(H, Tn, len0)
+        y = o = None
+        fp8 = self._fp8 is not None
+        stream8 = fp8 and M <= ops.FP8W_MAX_M                                   # few rows: the weight-streaming GEMM on the fp8 bytes, as in decode_step
+        for li, L in enumerate(pk["layers"]):
+            y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
+            qkv = ops.linear_fp8w(y, *L["wqkv"]) if stream8 else ops.linear(y, self._w(L["wqkv"]))
+            ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
+            cache.append(li, qkv, Tn, H, len0)
+            o = cache.extend_attend(li, qkv, H, Tn, len0, dh ** -0.5, ws, o)
+            if stream8:
+                ops.linear_fp8w(o, *L["wo"], residual=x, out=x)
+                y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
+                g = ops.swiglu_pairs(ops.linear_fp8w(y, *L["wgu"]))
+                ops.linear_fp8w(g, *L["wd"], residual=x, out=x)
+                continue
+            ops.linear(o, self._w(L["wo"]), residual=x, out=x)
+            y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
+            g = ops.linear_swiglu(y, self._w(L["wgu"]))
+            ops.linear(g, self._w(L["wd"]), residual=x, out=x)
+        cache.len = len0 + Tn
+        cache.next_pos = cache.next_pos + am.sum(1)
+        return ops.rmsnorm(x, pk["norm"], self.eps, out=y).reshape(B, Tn, D)
+
 
 _SAMPLING_ARGS = ("temperature", "top_p", "top_k", "num_beams", "penalty_alpha", "repetition_penalty")      # generate(): named so that they are refused by name
 
@@ -440,7 +499,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     @torch.no_grad()
     def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
                  eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
-                 output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", sampler=None, **unsupported):
+                 output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", sampler=None, prefill_chunk: Optional[int] = None,
+                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, **unsupported):
         """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
         the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
         embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
@@ -461,11 +521,24 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         whose logits hold a NaN or +inf (HF: "probability tensor contains either inf, nan") raises RuntimeError naming the sequence and the step:
         at the per-step host read when `eos_token_id` is given, otherwise once after the loop.
 
+        `prefill_chunk=N` (an int >= 1) feeds the spliced prompt as `prefill` over columns [0, N) and `LlamaModel.extend` over each following window
+        of N columns, each with its columns of the mask: the activations scale with N rows instead of the whole prompt.  None, or N >= the prompt
+        length, is the unchunked path bit for bit.  Positions continue from the cache, so explicit `position_ids` cannot be combined with windows.
+
+        `return_past=True` (with `return_dict_in_generate`) adds `GenerateOutput.past`, a generation.GenerationState: the cache and every sequence's
+        pending token.  `generate(past=state, inputs= / inputs_embeds=, comp_images=, attention_mask=(B, Tn'))` continues the conversation: the new turn
+        is spliced as usual, one column with the pending tokens' embedding rows (masked where there is none) is put in front of it, and the cache is
+        extended by that chunk — through `prefill_chunk` windows if given — before decoding as before.  A cache without room for the turn plus
+        `max_new_tokens` is replaced by a larger one holding the same slots; `cache_capacity=` lets a call reserve the room up front.  With `past`,
+        `position_ids` must be None (ValueError); a state of another batch size or element type (ValueError) or with an fp8 cache
+        (NotImplementedError: the extend attention over e4m3fn rows is a follow-up) is refused without being touched.  `kv_cache="fp8"` with a
+        `prefill_chunk` that cuts the prompt is refused the same way.
+
         HF's own spelling stays refused: `do_sample=True`, temperature= / top_p= / top_k= or beams raise NotImplementedError (the reference's
         defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here: pass a
         `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
-        from .generation import GenerateOutput, KVCache, Sampler
+        from .generation import GenerateOutput, GenerationState, KVCache, Sampler
         sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
         if do_sample or sampling:
             raise NotImplementedError(f"SetokimLlamaPrefill.generate: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "
@@ -483,30 +556,88 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8'")
         if sampler is not None and not isinstance(sampler, Sampler):
             raise TypeError(f"SetokimLlamaPrefill.generate: sampler must be a generation.Sampler or None, got {type(sampler).__name__}")
+        for name, v in (("prefill_chunk", prefill_chunk), ("cache_capacity", cache_capacity)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+                raise ValueError(f"SetokimLlamaPrefill.generate: {name}={v!r} must be an integer >= 1 (or None)")
+        if return_past and not return_dict_in_generate:
+            raise ValueError("SetokimLlamaPrefill.generate: return_past=True needs return_dict_in_generate=True (the state is GenerateOutput.past)")
+        if past is not None:
+            if not isinstance(past, GenerationState):
+                raise TypeError(f"SetokimLlamaPrefill.generate: past must be a generation.GenerationState (GenerateOutput.past), got {type(past).__name__}")
+            if position_ids is not None:
+                raise ValueError("SetokimLlamaPrefill.generate: with past= the new turn's positions continue from the cache; position_ids must be None")
+            if past.cache.kv_format == "fp8":
+                raise NotImplementedError("SetokimLlamaPrefill.generate: continuing from an fp8 KV cache is not implemented (the extend attention "
+                                          "over e4m3fn rows is a follow-up kernel); generate the first turn with kv_cache='native'")
+            if past.cache.dtype != self.model.norm.weight.dtype or past.cache.num_layers != len(self.model.layers):
+                raise ValueError(f"SetokimLlamaPrefill.generate: past holds a {past.cache.dtype} cache of {past.cache.num_layers} layers, the model "
+                                 f"runs {len(self.model.layers)} layers in {self.model.norm.weight.dtype}")
         embeds, am, pos, _ = self._embed(inputs, attention_mask, position_ids, inputs_embeds, None, comp_images)
         B, T, D = embeds.shape
         dev = self.lm_head.weight.device
+        w_lm = self.lm_head.weight.detach().contiguous()
+        w_e = self.model.embed_tokens.weight.detach().contiguous()
+        len0 = 0
+        if past is not None:
+            if past.cache.B != B or past.pending.shape != (B,):
+                raise ValueError(f"SetokimLlamaPrefill.generate: past holds {past.cache.B} sequences, the new turn {B}")
+            len0 = past.cache.len
+            pend = past.pending.to(dev)
+            front = ops.splice_rows(pend.clamp_min(0).to(torch.int32).reshape(B, 1), w_e, None)       # the pending tokens' embedding rows, one column
+            embeds = torch.cat([front, embeds.to(device=dev, dtype=front.dtype)], dim=1)
+            turn = torch.ones((B, T), dtype=torch.int64, device=dev) if am is None else am.to(dev).long()
+            am = torch.cat([(pend >= 0).long()[:, None], turn], dim=1)
+            T += 1
         sw = config_get(self.config, "sliding_window")
-        if sw is not None and int(sw) < T + max_new_tokens:
+        if sw is not None and int(sw) < len0 + T + max_new_tokens:
             raise NotImplementedError(f"SetokimLlamaPrefill.generate: sliding_window={sw} is shorter than prompt + max_new_tokens "
-                                      f"({T} + {max_new_tokens} positions): windowed attention is not implemented on the HIP path")
+                                      f"({len0 + T} + {max_new_tokens} positions): windowed attention is not implemented on the HIP path")
+        windows = prefill_chunk is not None and prefill_chunk < T             # the prompt is really cut (N >= T is the unchunked path)
+        if windows and pos is not None:
+            raise ValueError("SetokimLlamaPrefill.generate: prefill_chunk windows take their positions from the cache; position_ids must be None")
+        if windows and kv_cache == "fp8":
+            raise NotImplementedError("SetokimLlamaPrefill.generate: prefill_chunk with kv_cache='fp8' is not implemented (the extend attention over "
+                                      "e4m3fn rows is a follow-up kernel)")
         if am is not None:
             am = am.to(dev)
-            if pos is None:                                                        # HF generate's rule for a padded prompt without position_ids
+            if pos is None and past is None:                                       # HF generate's rule for a padded prompt without position_ids
                 pos = (am.long().cumsum(-1) - 1).masked_fill(am == 0, 1)
         eos = None
         if eos_token_id is not None:
             eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), dtype=torch.int64, device=dev)
             pad = int(eos[0]) if pad_token_id is None else int(pad_token_id)
-        cache = KVCache.for_model(self.model, B, T + max_new_tokens, dev, kv_format=kv_cache)
-        hidden = self.model.prefill(embeds.to(dev), am, pos, cache)
-        if am is None:
-            h = hidden[:, -1].contiguous()
+        need = len0 + T + max_new_tokens
+        if past is None:
+            cache = KVCache.for_model(self.model, B, max(need, cache_capacity or 0), dev, kv_format=kv_cache)
         else:
-            last = (am.bool() * torch.arange(T, device=dev)[None]).max(dim=1).values
-            h = hidden[torch.arange(B, device=dev), last].contiguous()
-        w_lm = self.lm_head.weight.detach().contiguous()
-        w_e = self.model.embed_tokens.weight.detach().contiguous()
+            cache = past.cache if past.cache.cap >= need else past.cache.grown(max(need, cache_capacity or 0))
+        if past is None and not windows:
+            hidden = self.model.prefill(embeds.to(dev), am, pos, cache)
+            if am is None:
+                h = hidden[:, -1].contiguous()
+            else:
+                last = (am.bool() * torch.arange(T, device=dev)[None]).max(dim=1).values
+                h = hidden[torch.arange(B, device=dev), last].contiguous()
+        else:
+            # windows of the prompt (or the whole new turn): the first window of a fresh prompt is a prefill, everything else extends the cache;
+            # each sequence's last attended row is looked up in the window that holds it
+            N = prefill_chunk if windows else T
+            embeds = embeds.to(dev)
+            h = None
+            for c0 in range(0, T, N):
+                c1 = min(c0 + N, T)
+                amw = None if am is None else am[:, c0:c1]
+                if past is None and c0 == 0:
+                    hidden = self.model.prefill(embeds[:, c0:c1], amw, None if pos is None else pos[:, c0:c1], cache)
+                else:
+                    hidden = self.model.extend(embeds[:, c0:c1], cache, amw)
+                if amw is None:
+                    h = hidden[:, -1].contiguous()
+                    continue
+                last = (amw.bool() * torch.arange(c1 - c0, device=dev)[None]).max(dim=1).values
+                hw = hidden[torch.arange(B, device=dev), last]
+                h = hw.contiguous() if h is None else torch.where(amw.bool().any(dim=1)[:, None], hw, h)
+        fed0 = cache.len                                                           # the first slot a decode step of this call fills
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         toks, hids, lgs = [], [], []
         raws = []                                                                  # sampler only: the tokens as drawn, -1 where a row could not be drawn from
@@ -539,8 +670,22 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         seq = torch.stack(toks, dim=1)
         if not return_dict_in_generate:
             return seq
+        state = None
+        if return_past:
+            # Of the n emitted tokens the stack has consumed the first n - 1 (slots fed0 .. fed0 + n - 2).  A sequence's real tokens end with its first
+            # eos: the pads behind it that were fed are masked out and its next position is set back by their number; its last real token is pending
+            # iff it was never fed (the sequence did not finish before the last step).
+            n = seq.shape[1]
+            real = torch.full((B,), n, dtype=torch.int64, device=dev)
+            if eos is not None:
+                hit = torch.isin(seq, eos)
+                real = torch.where(hit.any(dim=1), hit.long().argmax(dim=1) + 1, real)
+            j = torch.arange(n - 1, device=dev)[None]
+            cache.key_mask[:, fed0:fed0 + n - 1] = (j < real[:, None]).to(torch.uint8)
+            cache.next_pos = cache.next_pos - (n - 1 - real).clamp_min(0)
+            state = GenerationState(cache=cache, pending=torch.where(real == n, seq[:, -1], torch.full_like(real, -1)))
         return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if output_hidden_states else None,
-                              logits=torch.stack(lgs, dim=1) if output_logits else None)
+                              logits=torch.stack(lgs, dim=1) if output_logits else None, past=state)
 
     def _head(self, inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss):
         hidden = self.model._forward(inputs_embeds, attention_mask, position_ids)  # setokim_llama.py:130-140

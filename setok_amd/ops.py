@@ -776,6 +776,40 @@ def attention_decode_fp8kv(q: Tensor, k_q: Tensor, k_e: Tensor, v_q: Tensor, v_e
     return out
 
 
+# ---- extending a cache by Tn tokens (csrc/attn_extend.hip) ---------------------------------------------------------------------------------------
+EXTEND_CHUNK = 256                                # SETOK_EXTEND_CHUNK of include/setok_hip.h
+
+
+def attention_extend_workspace(B: int, Tn: int, H: int, Dh: int, len0: int, Hkv: Optional[int] = None, dtype: torch.dtype = torch.float32) -> int:
+    """Floats of workspace setok_attention_extend_gqa needs for Tn new rows per sequence behind len0 cached slots, as the library states it
+    (setok_attention_extend_workspace: the rule lives there).  Without Hkv and dtype: B * Tn * H * ceil((len0 + Tn) / EXTEND_CHUNK) * (Dh + 2),
+    which suffices for every call; with them, what the kernel that call runs needs (the MFMA kernel with many rows leaves fewer partials)."""
+    code = _code(dtype)
+    return int(_lib.load(_lib.is_half(code)).setok_attention_extend_workspace(code, B, Tn, H, H if Hkv is None else Hkv, Dh, len0))
+
+
+def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tensor, H: int, Tn: int, len0: int, scale: float,
+                     ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Tn query rows per (sequence, query head) against the caches (B, Hkv, cap, Dh), which already hold the new rows' keys / values in slots
+    [len0, len0 + Tn): query i of sequence b counts slot j iff j <= len0 + i and key_mask[b, j] != 0.  q: (B * Tn, >= H*Dh) rows, row stride
+    q.stride(0) (the step's fused qkv buffer is read in place); key_mask (B, cap) uint8.  Returns (B * Tn, H*Dh)."""
+    B, Hkv, cap, Dh = k_cache.shape
+    assert v_cache.shape == k_cache.shape and k_cache.dtype == v_cache.dtype == q.dtype
+    assert Tn >= 1 and len0 >= 0 and len0 + Tn <= cap, f"attention_extend: slots [{len0}, {len0} + {Tn}) exceed the cache (cap = {cap})"
+    assert q.shape[0] == B * Tn and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, cap)
+    need = attention_extend_workspace(B, Tn, H, Dh, len0, Hkv, q.dtype)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B * Tn, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B * Tn, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_extend_gqa", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_cache), _p(v_cache), _p(key_mask), _p(out),
+              B, Tn, H, Hkv, Dh, cap, len0, scale, _p(ws), ws.numel())
+    return out
+
+
 def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """int64 (rows,): the lowest index of each row's maximum; x (rows, V) with any row stride."""
     rows, V = x.shape
