@@ -599,6 +599,50 @@ int setok_attention_extend_gqa(void* stream, int dtype, const void* q, int64_t l
 int setok_sample_rows(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u, float temperature, int top_k,
                       float top_p, int64_t* out, float* probs, int64_t ld_probs);
 
+/* ---- Speculative decoding (csrc/speculate.hip): draft-and-verify on top of the extend above.  A round feeds K + 1 rows per sequence - the pending
+ * token and K drafted ones - through one `extend`, selects a token from every row's logits (setok_argmax_rows or setok_sample_rows) and then keeps
+ * the longest prefix of the drafts that the model itself would have produced, plus one more token: what the plain loop emits, in fewer passes
+ * over the weights.  Both entries are integer-only, use no atomics, and are pure functions of their inputs.  Pure addition: the ABI stays 9.
+ *
+ * setok_spec_accept - one launch of one workgroup, a thread per sequence (looping for B above the block size).
+ *   draft (B, K) int64, -1 = no proposal (everything behind a sequence's first negative entry counts as negative); sel (B, K + 1) int64: sel[b][i]
+ *   is the token selected from the state that consumed the pending token and drafts 0 .. i - 1; eos (n_eos) int64 (NULL with n_eos == 0).
+ *   Loop state, updated in place: seq (B, max_new) int64, count (B) int32, finished (B) uint8, pending (B) int64; the cache's key_mask (B, cap)
+ *   uint8 and next_pos (B) int64; len0 = the first slot the round's extend filled.  Outputs: emitted (B, K + 1) int64, m_out (B) int32,
+ *   summary (3) int32.
+ *   For an unfinished sequence b (finished[b] == 0 and 0 <= count[b] < max_new):
+ *     n  = the number of leading i < K with draft[b][i] >= 0 && draft[b][i] == sel[b][i];  the candidates are e_i = sel[b][i], i <= n;
+ *     m  = min(n + 1, max_new - count[b]);  if some e_i with i < m is an eos id, m = (the first such i) + 1 and the sequence finishes;  it also
+ *          finishes when count[b] + m == max_new;
+ *     seq[b][count .. count + m) = e_0 .. e_{m-1};  count[b] += m;  emitted[b][i] = e_i for i < m, else -1;  m_out[b] = m;  pending[b] = e_{m-1};
+ *     key_mask[b][len0 + i] = 1 for i < m and 0 for m <= i <= K  (slot len0 holds the old pending token, slot len0 + i draft i - 1: the accepted
+ *          drafts ARE the emitted tokens e_0 .. e_{m-2}, and e_{m-1} is the new pending token, not yet in the cache);
+ *     next_pos[b] = next_pos[b] - (1 + the number of leading non-negative drafts) + m: `extend` advanced it by the rows it attended, so this is its
+ *          value before the round plus m.  With K == 0 and no extend before it (the loop's first token) the position is unchanged.
+ *   A finished sequence: m = 0, emitted all -1, key_mask[b][len0 .. len0 + K] = 0, nothing else touched.
+ *   summary = { max_b m, the number of sequences still unfinished after the round, 1 iff an emitted token is negative }.
+ *   Refused on the host before any launch (-1, setok_last_error): a null operand (draft may be NULL with K == 0), B < 0, K outside [0, 63],
+ *   max_new < 1, n_eos < 0, len0 + K + 1 > cap.  B == 0 launches nothing.
+ *
+ * setok_ngram_propose - the built-in drafter's one launch per round; one workgroup of 256 threads per sequence.
+ *   hist (B, cap_h) int64 with hist_len (B) int32 valid entries per row, both updated in place; emitted (B, n_emit) int64 and m (B) int32 (NULL
+ *   with n_emit == 0: propose only); out (B, K) int64.
+ *   1. Append: hist[b][hist_len[b] ..] = emitted[b][0 .. m[b]) and hist_len[b] += m[b]  (m[b] is clamped to [0, n_emit]).  L = the new length.
+ *   2. For n = max_ngram down to min_ngram: skip n when L <= n or when any of the last n entries is negative; find the LARGEST j <= L - n - 1 with
+ *      hist[b][j .. j + n) == hist[b][L - n .. L)  (the match may overlap the suffix);  at the first n with a match
+ *      out[b][i] = hist[b][j + n + i] if j + n + i < L, else -1, and the search ends.  With no match at any n, out[b] is all -1.
+ *      A negative history entry (an image placeholder) matches nothing; one inside a continuation is copied and ends the proposal there.
+ *   len_max is the caller's host-side bound on max_b (hist_len[b] + m[b]), the lengths themselves being on the device: the call is refused when
+ *   len_max > cap_h ("hist_len + m > cap_h"), and the kernel never writes at or behind cap_h whatever the device values say.
+ *   Refused as well: a null operand, B < 0, cap_h < 1, K outside [1, 63], n_emit outside [0, 64], 1 <= min_ngram <= max_ngram <= 8 violated.
+ *   Threads test strided j and keep their largest match; the largest of all meets by a wave max and an LDS max over the waves; one wave writes the
+ *   continuation. */
+int setok_spec_accept(void* stream, const int64_t* draft, const int64_t* sel, int B, int K, const int64_t* eos, int n_eos, int max_new,
+                      int64_t* seq, int32_t* count, uint8_t* finished, int64_t* pending, uint8_t* key_mask, int64_t* next_pos, int cap, int len0,
+                      int64_t* emitted, int32_t* m_out, int32_t* summary);
+int setok_ngram_propose(void* stream, int64_t* hist, int32_t* hist_len, int B, int cap_h, int len_max, const int64_t* emitted, const int32_t* m,
+                        int n_emit, int K, int max_ngram, int min_ngram, int64_t* out);
+
 /* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip): the decode step streams every projection weight once per token, so the stack's Linear
  * weights may be STORED as OCP e4m3fn bytes with one power-of-two scale per output row.  A matrix W (N, K) becomes q (N, K) uint8 + e (N,) int8 and
  * means exactly

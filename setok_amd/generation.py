@@ -3,7 +3,8 @@ keeps between steps as HF's `past_key_values` (:99,133,189), and what it returns
 
 `KVCache` is allocated once per `generate` call; `LlamaModel.prefill` fills slots [0, T') of every layer, every `LlamaModel.decode_step` appends
 one slot for all sequences, `LlamaModel.extend` appends Tn >= 1 slots (chunked prefill, the next turn of a conversation).  The loop itself is
-`SetokimLlamaPrefill.generate` (llama.py); `GenerationState` is what it hands back so that a later call can continue from the same cache."""
+`SetokimLlamaPrefill.generate` (llama.py); `GenerationState` is what it hands back so that a later call can continue from the same cache.
+`Drafter` / `LookupDrafter` are the sources of proposals for `generate(draft=...)`, which verifies K drafted tokens per `extend`."""
 from __future__ import annotations
 
 import math
@@ -91,6 +92,15 @@ class KVCache:
         new.len = n
         return new
 
+    def truncate(self, n: int) -> None:
+        """Give slots [n, len) back: `len = n` and their mask bytes are cleared (the rows themselves stay, unread).  What a draft-and-verify round does
+        with the slots of its rejected drafts.  ValueError for n outside [0, len]; positions are the caller's business."""
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= self.len:
+            raise ValueError(f"KVCache.truncate: n={n!r} is outside [0, len] = [0, {self.len}]")
+        if n < self.len:
+            self.key_mask[:, n:self.len] = 0
+        self.len = n
+
     def nbytes(self) -> int:
         if self.kv_format == "fp8":                                    # codes + exponents
             return sum(t.numel() * t.element_size() for t in self.k_q + self.k_e + self.v_q + self.v_e)
@@ -146,6 +156,18 @@ class Sampler:
             return self.u[step]
         return torch.rand(B, generator=self.generator, device=device, dtype=torch.float32)
 
+    def uniform_matrix(self, steps: int, B: int, device) -> torch.Tensor:
+        """All (steps, B) float32 uniforms of a call at once — what `generate(draft=...)` needs, since a round selects tokens for several steps.  With
+        `u` these are the plain loop's (row j is step j's); with a generator it is ONE `torch.rand(steps, B)` draw, which is not the stream the
+        plain loop's per-step draws consume."""
+        if self.u is not None:
+            if self.u.shape[0] < steps or self.u.shape[1] != B:
+                raise ValueError(f"Sampler: u has shape {tuple(self.u.shape)}, {steps} steps of a batch of {B} with a draft need (at least {steps}, {B})")
+            if self.u.device != torch.device(device):
+                self.u = self.u.to(device)
+            return self.u[:steps]
+        return torch.rand((steps, B), generator=self.generator, device=device, dtype=torch.float32)
+
     def select(self, logits: torch.Tensor, step: int) -> torch.Tensor:
         """int64 (B,): the step's tokens, -1 for a row whose logits hold a NaN or +inf or no finite entry."""
         return ops.sample_rows(logits, self.uniforms(step, logits.shape[0], logits.device), self.temperature, self.top_k, self.top_p)
@@ -171,3 +193,95 @@ class GenerateOutput:
     hidden_states: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
     past: Optional[GenerationState] = None
+
+
+class Drafter:
+    """What `SetokimLlamaPrefill.generate(draft=...)` drives: a source of K proposed tokens per sequence per round.  `generate` calls
+
+      begin(B, device, prompt_ids, prompt_mask, max_new_tokens)   once: prompt_ids (B, T) int64 as the caller passed them (image placeholders and
+                                                                   other specials are negative) or None with `inputs_embeds`; prompt_mask (B, T) or None
+      update(emitted, m)     after the first token and after every round: emitted (B, n) int64, the first m[b] (int32) entries of row b are the tokens
+                             sequence b just emitted, the rest is -1
+      propose(pending)       before every round: pending (B,) int64 is each sequence's last emitted token; returns (B, K) int64, -1 = no proposal
+                             (everything behind a row's first -1 is ignored)
+
+    all on the device.  A proposal costs nothing but its slots when it is wrong: the verify pass keeps the tokens the model itself selects.  `K`
+    (an int in [1, 63]) is fixed for a call.  A model-backed drafter would subclass this; `LookupDrafter` is the one that is built."""
+    K: int = 0
+
+    def begin(self, B: int, device, prompt_ids: Optional[torch.Tensor], prompt_mask: Optional[torch.Tensor], max_new_tokens: Optional[int] = None) -> None:
+        pass
+
+    def propose(self, pending: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError
+
+    def update(self, emitted: torch.Tensor, m: torch.Tensor) -> None:
+        pass
+
+
+class LookupDrafter(Drafter):
+    """Prompt-lookup drafting, no second model: propose the continuation of the most recent earlier occurrence of the sequence's trailing n-gram,
+    n = max_ngram down to min_ngram (include/setok_hip.h, "Speculative decoding", states the rule).  The history `hist` (B, cap_h) int64 with
+    `hist_len` (B,) int32 lives on the device: `begin` stores each sequence's attended prompt ids in order (negative ids stay and match nothing;
+    with `inputs_embeds` alone the history starts empty, and every call starts a new history), `update` followed by `propose` is ONE launch of
+    `setok_ngram_propose`.  What it accepts depends on how repetitive the text is."""
+
+    def __init__(self, K: int, max_ngram: int = 3, min_ngram: int = 1):
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPEC_MAX_K:
+            raise ValueError(f"LookupDrafter: K={K!r} must be an int in [1, {ops.SPEC_MAX_K}]")
+        for v in (max_ngram, min_ngram):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"LookupDrafter: the n-gram lengths must be ints, got {v!r}")
+        if not 1 <= min_ngram <= max_ngram <= ops.NGRAM_MAX_N:
+            raise ValueError(f"LookupDrafter: the n-gram range [{min_ngram}, {max_ngram}] must satisfy 1 <= min_ngram <= max_ngram <= {ops.NGRAM_MAX_N}")
+        self.K, self.max_ngram, self.min_ngram = K, max_ngram, min_ngram
+        self.hist: Optional[torch.Tensor] = None
+        self.hist_len: Optional[torch.Tensor] = None
+        self._queued = None                                                        # (emitted, m) of an update that no launch has appended yet
+        self._hi = 0                                                               # host bound on every hist_len, queued update included
+        self._limit: Optional[int] = None                                          # prompt + max_new_tokens when the call said so
+
+    def begin(self, B, device, prompt_ids, prompt_mask, max_new_tokens=None):
+        T = 0 if prompt_ids is None else prompt_ids.shape[1]
+        self._limit = None if max_new_tokens is None else T + int(max_new_tokens)
+        cap_h = T + (int(max_new_tokens) if max_new_tokens is not None else 64) + self.K + 1
+        self.hist = torch.full((B, cap_h), -1, dtype=torch.int64, device=device)
+        self.hist_len = torch.zeros(B, dtype=torch.int32, device=device)
+        self._queued, self._hi = None, T
+        if T:
+            ids = prompt_ids.to(device=device, dtype=torch.int64)
+            if prompt_mask is None:
+                self.hist[:, :T] = ids
+                self.hist_len.fill_(T)
+            else:
+                am = prompt_mask.to(device).bool()
+                order = torch.argsort((~am).to(torch.int8), dim=1, stable=True)   # the attended columns first, in their order
+                self.hist[:, :T] = ids.gather(1, order)
+                self.hist_len.copy_(am.sum(1))
+
+    def _room(self, n: int) -> int:
+        """The bound on hist_len after `n` more entries per row; the history is regrown when a row could not take them."""
+        self._hi += n
+        if self._limit is not None:
+            self._hi = min(self._hi, self._limit)                                   # a call emits max_new_tokens per sequence at the most
+        if self._hi > self.hist.shape[1]:
+            grown = torch.full((self.hist.shape[0], max(2 * self.hist.shape[1], self._hi)), -1, dtype=torch.int64, device=self.hist.device)
+            grown[:, :self.hist.shape[1]] = self.hist
+            self.hist = grown
+        return self._hi
+
+    def _launch(self) -> torch.Tensor:
+        if self.hist is None:
+            raise RuntimeError("LookupDrafter: begin() has not been called")
+        e, m = self._queued if self._queued is not None else (None, None)
+        self._queued = None
+        return ops.ngram_propose(self.hist, self.hist_len, self.K, self._hi, e, m, self.max_ngram, self.min_ngram)
+
+    def update(self, emitted, m):
+        if self._queued is not None:
+            self._launch()                                                         # two updates in a row: append the first now
+        self._room(emitted.shape[1])
+        self._queued = (emitted.contiguous(), m.to(torch.int32).contiguous())
+
+    def propose(self, pending):
+        return self._launch()

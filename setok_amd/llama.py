@@ -500,7 +500,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
                  eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
                  output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", sampler=None, prefill_chunk: Optional[int] = None,
-                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, **unsupported):
+                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, draft=None, **unsupported):
         """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
         the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
         embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
@@ -534,11 +534,22 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         (NotImplementedError: the extend attention over e4m3fn rows is a follow-up) is refused without being touched.  `kv_cache="fp8"` with a
         `prefill_chunk` that cuts the prompt is refused the same way.
 
+        `draft=` (a generation.Drafter, e.g. generation.LookupDrafter(K)) decodes by draft and verify: a round feeds every sequence's pending token and
+        K proposed ones through ONE `LlamaModel.extend`, selects a token from each of the K + 1 states (the same argmax or sampler launch) and
+        `setok_spec_accept` keeps the longest prefix of the proposals that the model itself selected plus one more token.  Selection is a pure function
+        of (logits, u), so the tokens are the plain loop's, greedy and with `Sampler(u=...)` (row j of `u` draws emitted token j; `u` needs
+        max_new_tokens rows); a `Sampler(generator=...)` draws `torch.rand(max_new_tokens, B)` once at the start, which is NOT the plain loop's
+        stream.  One host read per round (the kernel's 3-int summary).  The cache gets K more slots than the plain loop's and all sequences share
+        `len`, so at B > 1 a sequence that accepts fewer tokens than the round's best keeps masked holes; a round that lacks K + 1 free slots
+        first replaces the cache by one of twice the capacity.  Outputs, pad rule and `return_past` are the plain loop's (the state's pending token is
+        each sequence's last emitted one, an eos included).  Refused before any device call: a `draft` that is no Drafter (TypeError), a `draft.K`
+        outside [1, 63] (ValueError), `kv_cache="fp8"` with a draft (NotImplementedError: `extend` refuses that cache).  `draft=None` is the plain loop.
+
         HF's own spelling stays refused: `do_sample=True`, temperature= / top_p= / top_k= or beams raise NotImplementedError (the reference's
         defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here: pass a
         `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
-        from .generation import GenerateOutput, GenerationState, KVCache, Sampler
+        from .generation import Drafter, GenerateOutput, GenerationState, KVCache, Sampler
         sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
         if do_sample or sampling:
             raise NotImplementedError(f"SetokimLlamaPrefill.generate: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "
@@ -556,6 +567,16 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8'")
         if sampler is not None and not isinstance(sampler, Sampler):
             raise TypeError(f"SetokimLlamaPrefill.generate: sampler must be a generation.Sampler or None, got {type(sampler).__name__}")
+        K = 0
+        if draft is not None:
+            if not isinstance(draft, Drafter):
+                raise TypeError(f"SetokimLlamaPrefill.generate: draft must be a generation.Drafter or None, got {type(draft).__name__}")
+            K = draft.K
+            if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPEC_MAX_K:
+                raise ValueError(f"SetokimLlamaPrefill.generate: draft.K={K!r} must be an int in [1, {ops.SPEC_MAX_K}]")
+            if kv_cache == "fp8":
+                raise NotImplementedError("SetokimLlamaPrefill.generate: draft= with kv_cache='fp8' is not implemented (a round extends the cache by "
+                                          "K + 1 tokens, and the extend attention over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
         for name, v in (("prefill_chunk", prefill_chunk), ("cache_capacity", cache_capacity)):
             if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
                 raise ValueError(f"SetokimLlamaPrefill.generate: {name}={v!r} must be an integer >= 1 (or None)")
@@ -606,7 +627,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         if eos_token_id is not None:
             eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), dtype=torch.int64, device=dev)
             pad = int(eos[0]) if pad_token_id is None else int(pad_token_id)
-        need = len0 + T + max_new_tokens
+        need = len0 + T + max_new_tokens + K                                       # (K = 0 without a draft: a round may fill K slots it gives back)
         if past is None:
             cache = KVCache.for_model(self.model, B, max(need, cache_capacity or 0), dev, kv_format=kv_cache)
         else:
@@ -637,6 +658,9 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                 last = (amw.bool() * torch.arange(c1 - c0, device=dev)[None]).max(dim=1).values
                 hw = hidden[torch.arange(B, device=dev), last]
                 h = hw.contiguous() if h is None else torch.where(amw.bool().any(dim=1)[:, None], hw, h)
+        if draft is not None:
+            return self._generate_speculative(draft, h, cache, inputs, attention_mask, max_new_tokens, eos, pad if eos is not None else 0, sampler,
+                                              return_dict_in_generate, output_hidden_states, output_logits, return_past)
         fed0 = cache.len                                                           # the first slot a decode step of this call fills
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         toks, hids, lgs = [], [], []
@@ -686,6 +710,93 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             state = GenerationState(cache=cache, pending=torch.where(real == n, seq[:, -1], torch.full_like(real, -1)))
         return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if output_hidden_states else None,
                               logits=torch.stack(lgs, dim=1) if output_logits else None, past=state)
+
+    def _generate_speculative(self, draft, h, cache, prompt_ids, prompt_mask, max_new, eos, pad, sampler, as_dict, want_hidden, want_logits, want_past):
+        """generate()'s loop with a drafter, from the last attended state `h` (B, D) on.  Between rounds the state lives on the device: pending
+        (B,) int64, count (B,) int32, finished (B,) uint8 and seq (B, max_new) int64; `setok_spec_accept` advances it, and the host reads the
+        kernel's 3-int summary once per round."""
+        from .generation import GenerateOutput, GenerationState
+        B, D = h.shape
+        K, dev = draft.K, h.device
+        w_lm = self.lm_head.weight.detach().contiguous()
+        w_e = self.model.embed_tokens.weight.detach().contiguous()
+        seq = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
+        count = torch.zeros(B, dtype=torch.int32, device=dev)
+        finished = torch.zeros(B, dtype=torch.uint8, device=dev)
+        pending = torch.zeros(B, dtype=torch.int64, device=dev)
+        summary = torch.zeros(3, dtype=torch.int32, device=dev)
+        u = None if sampler is None else sampler.uniform_matrix(max_new, B, dev)
+        steps = torch.arange(K + 1, device=dev, dtype=torch.int64)[None]
+        rows_b = torch.arange(B, device=dev)[:, None]
+        # outputs: column max_new takes the rows no sequence emitted and is cut off at the end
+        hid_out = torch.zeros((B, max_new + 1, D), dtype=h.dtype, device=dev) if want_hidden else None
+        lg_out = None
+
+        def select(logits, n):                                                     # logits (B * n, V) -> (B, n) int64
+            if sampler is None:
+                return ops.argmax_rows(logits).reshape(B, n)
+            ur = u[(count.long()[:, None] + steps[:, :n]).clamp_max(max_new - 1), rows_b].reshape(B * n).contiguous()
+            return ops.sample_rows(logits, ur, sampler.temperature, sampler.top_k, sampler.top_p).reshape(B, n)
+
+        def keep(hidden, logits, before, m, n):                                    # row i < m[b] of sequence b -> column before[b] + i
+            nonlocal lg_out
+            if not (want_hidden or want_logits):
+                return
+            cols = torch.where(steps[:, :n] < m.long()[:, None], before.long()[:, None] + steps[:, :n], torch.full_like(steps[:, :n], max_new))
+            if want_hidden:
+                hid_out[rows_b, cols] = hidden.reshape(B, n, D)
+            if want_logits:
+                if lg_out is None:
+                    lg_out = torch.zeros((B, max_new + 1, logits.shape[-1]), dtype=logits.dtype, device=dev)
+                lg_out[rows_b, cols] = logits.reshape(B, n, -1)
+
+        def after_round():
+            mx, live, bad = summary.tolist()                                       # the round's one host read
+            if bad:
+                n = int(count.max())
+                drawn = torch.where((seq[:, :n] < 0) & (torch.arange(n, device=dev)[None] < count[:, None]), -1, 0)
+                _raise_undrawable(list(drawn.unbind(dim=1)))
+            return mx, live
+
+        cache.next_pos = cache.next_pos.contiguous()
+        draft.begin(B, dev, prompt_ids, prompt_mask, max_new)
+        # step 0: the token selected from the last attended state, put into the loop state by the accept rule with no drafts
+        logits = ops.linear(h, w_lm)
+        sel = select(logits, 1)
+        before = count.clone()
+        emitted, m, _ = ops.spec_accept(sel[:, :0].contiguous(), sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, cache.len,
+                                        summary=summary)
+        cache.key_mask[:, cache.len] = 0                                           # (nothing was fed: the slot the rule marked is not filled yet)
+        keep(h, logits, before, m, 1)
+        draft.update(emitted, m)
+        _, live = after_round()
+        while live > 0:
+            if cache.len + K + 1 > cache.cap:
+                cache = cache.grown(2 * cache.cap)
+            d = draft.propose(pending)
+            if not (isinstance(d, torch.Tensor) and d.dtype == torch.int64 and tuple(d.shape) == (B, K)):
+                raise TypeError(f"SetokimLlamaPrefill.generate: draft.propose must return a (B, K) = ({B}, {K}) int64 tensor")
+            d = d.to(dev).contiguous()
+            live_b = finished == 0
+            am = torch.cat([live_b[:, None], ((d >= 0).long().cummin(dim=1).values > 0) & live_b[:, None]], dim=1)
+            ids = torch.cat([pending[:, None], d], dim=1).clamp_min(0).to(torch.int32)
+            len0 = cache.len
+            hidden = self.model.extend(ops.splice_rows(ids, w_e, None), cache, am)         # (B, K + 1, D): one pass over the weights
+            logits = ops.linear(hidden.reshape(B * (K + 1), D), w_lm)
+            sel = select(logits, K + 1)
+            before = count.clone()
+            emitted, m, _ = ops.spec_accept(d, sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, len0, summary=summary)
+            keep(hidden, logits, before, m, K + 1)
+            draft.update(emitted, m)
+            mx, live = after_round()
+            cache.truncate(len0 + mx)
+        n = int(count.max())
+        out = seq[:, :n].contiguous()
+        if not as_dict:
+            return out
+        state = GenerationState(cache=cache, pending=pending) if want_past else None
+        return GenerateOutput(sequences=out, hidden_states=hid_out[:, :n].contiguous() if want_hidden else None,
+                              logits=lg_out[:, :n].contiguous() if want_logits else None, past=state)
 
     def _head(self, inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss):
         hidden = self.model._forward(inputs_embeds, attention_mask, position_ids)  # setokim_llama.py:130-140

@@ -841,6 +841,82 @@ def sample_rows(logits: Tensor, u: Tensor, temperature: float = 1.0, top_k: int 
     return out
 
 
+# ---- speculative decoding (csrc/speculate.hip) ---------------------------------------------------------------------------------------------------
+SPEC_MAX_K = 63                                   # drafted tokens per round: K + 1 <= 64 rows per sequence
+NGRAM_MAX_N = 8
+
+
+def _i(t: Tensor, dtype: torch.dtype, shape, what: str) -> Tensor:
+    if not (isinstance(t, Tensor) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_cuda and t.is_contiguous()):
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, Tensor) else type(t).__name__
+        raise ValueError(f"{what} must be a contiguous device {dtype} tensor of shape {tuple(shape)}, got {got}")
+    return t
+
+
+def spec_accept(draft: Tensor, sel: Tensor, eos: Optional[Tensor], seq: Tensor, count: Tensor, finished: Tensor, pending: Tensor, key_mask: Tensor,
+                next_pos: Tensor, len0: int, emitted: Optional[Tensor] = None, m_out: Optional[Tensor] = None,
+                summary: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The accept rule of a draft-and-verify round (include/setok_hip.h, "Speculative decoding"), one launch: draft (B, K) int64 and the selected
+    tokens sel (B, K + 1) int64 -> what every sequence emits.  Updated in place: seq (B, max_new) int64, count (B,) int32, finished (B,) uint8,
+    pending (B,) int64, key_mask (B, cap) uint8 (slots [len0, len0 + K]) and next_pos (B,) int64.  eos: (n_eos,) int64 or None.  Returns
+    (emitted (B, K + 1) int64, m (B,) int32, summary (3,) int32 = {max m, unfinished sequences, 1 iff a negative token was emitted})."""
+    if sel.dim() != 2 or draft.dim() != 2:
+        raise ValueError(f"spec_accept: draft and sel must be (B, K) and (B, K + 1), got {tuple(draft.shape)} and {tuple(sel.shape)}")
+    B, K = sel.shape[0], sel.shape[1] - 1
+    if not 0 <= K <= SPEC_MAX_K:
+        raise ValueError(f"spec_accept: K={K} is outside [0, {SPEC_MAX_K}]")
+    if seq.dim() != 2 or seq.shape[1] < 1 or key_mask.dim() != 2:
+        raise ValueError(f"spec_accept: seq must be (B, max_new >= 1) and key_mask (B, cap), got {tuple(seq.shape)} and {tuple(key_mask.shape)}")
+    max_new, cap = seq.shape[1], key_mask.shape[1]
+    if len0 < 0 or len0 + K + 1 > cap:
+        raise ValueError(f"spec_accept: slots [{len0}, {len0} + {K}] exceed the cache (cap = {cap})")
+    i64, i32, u8 = torch.int64, torch.int32, torch.uint8
+    _i(draft, i64, (B, K), "spec_accept: draft"); _i(sel, i64, (B, K + 1), "spec_accept: sel"); _i(seq, i64, (B, max_new), "spec_accept: seq")
+    _i(count, i32, (B,), "spec_accept: count"); _i(finished, u8, (B,), "spec_accept: finished"); _i(pending, i64, (B,), "spec_accept: pending")
+    _i(key_mask, u8, (B, cap), "spec_accept: key_mask"); _i(next_pos, i64, (B,), "spec_accept: next_pos")
+    n_eos = 0
+    if eos is not None:
+        n_eos = eos.numel()
+        _i(eos, i64, (n_eos,), "spec_accept: eos")
+    dev = sel.device
+    emitted = torch.empty((B, K + 1), dtype=i64, device=dev) if emitted is None else _i(emitted, i64, (B, K + 1), "spec_accept: emitted")
+    m_out = torch.empty(B, dtype=i32, device=dev) if m_out is None else _i(m_out, i32, (B,), "spec_accept: m_out")
+    summary = torch.zeros(3, dtype=i32, device=dev) if summary is None else _i(summary, i32, (3,), "spec_accept: summary")
+    _lib.call("setok_spec_accept", _stream(), draft.data_ptr() if K else None, sel.data_ptr(), B, K, eos.data_ptr() if n_eos else None, n_eos, max_new,
+              seq.data_ptr(), count.data_ptr(), finished.data_ptr(), pending.data_ptr(), key_mask.data_ptr(), next_pos.data_ptr(), cap, len0,
+              emitted.data_ptr(), m_out.data_ptr(), summary.data_ptr())
+    return emitted, m_out, summary
+
+
+def ngram_propose(hist: Tensor, hist_len: Tensor, K: int, len_max: int, emitted: Optional[Tensor] = None, m: Optional[Tensor] = None,
+                  max_ngram: int = 3, min_ngram: int = 1, out: Optional[Tensor] = None) -> Tensor:
+    """The lookup drafter's launch (include/setok_hip.h, "Speculative decoding"): append emitted[b, :m[b]] to the history hist (B, cap_h) int64 /
+    hist_len (B,) int32 (in place; both None: propose only), then out (B, K) int64 = the continuation of the most recent earlier occurrence of the
+    longest trailing n-gram, max_ngram down to min_ngram, -1 where there is none.  len_max: the caller's bound on max_b (hist_len[b] + m[b])."""
+    if hist.dim() != 2:
+        raise ValueError(f"ngram_propose: hist must be (B, cap_h), got {tuple(hist.shape)}")
+    B, cap_h = hist.shape
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= SPEC_MAX_K:
+        raise ValueError(f"ngram_propose: K={K!r} must be an int in [1, {SPEC_MAX_K}]")
+    if not 1 <= min_ngram <= max_ngram <= NGRAM_MAX_N:
+        raise ValueError(f"ngram_propose: the n-gram range [{min_ngram}, {max_ngram}] must satisfy 1 <= min_ngram <= max_ngram <= {NGRAM_MAX_N}")
+    if cap_h < 1 or not 0 <= len_max <= cap_h:
+        raise ValueError(f"ngram_propose: hist_len + m > cap_h (the history may reach {len_max} entries, a row holds {cap_h})")
+    _i(hist, torch.int64, (B, cap_h), "ngram_propose: hist"); _i(hist_len, torch.int32, (B,), "ngram_propose: hist_len")
+    n_emit = 0
+    if (emitted is None) != (m is None):
+        raise ValueError("ngram_propose: pass emitted and m together, or neither")
+    if emitted is not None:
+        if emitted.dim() != 2 or not 1 <= emitted.shape[1] <= SPEC_MAX_K + 1:
+            raise ValueError(f"ngram_propose: emitted must be (B, 1 .. {SPEC_MAX_K + 1}), got {tuple(emitted.shape)}")
+        n_emit = emitted.shape[1]
+        _i(emitted, torch.int64, (B, n_emit), "ngram_propose: emitted"); _i(m, torch.int32, (B,), "ngram_propose: m")
+    out = torch.empty((B, K), dtype=torch.int64, device=hist.device) if out is None else _i(out, torch.int64, (B, K), "ngram_propose: out")
+    _lib.call("setok_ngram_propose", _stream(), hist.data_ptr(), hist_len.data_ptr(), B, cap_h, int(len_max), emitted.data_ptr() if n_emit else None,
+              m.data_ptr() if n_emit else None, n_emit, K, int(max_ngram), int(min_ngram), out.data_ptr())
+    return out
+
+
 # ---- fp8 weight-only storage (csrc/gemm_fp8w.hip) -----------------------------------------------------------------------------------------------
 FP8W_MAX_M = 64                                   # rows setok_linear_fp8w takes; more rows dequantise and go through `linear`
 
