@@ -755,6 +755,33 @@ int setok_ddpm_step(void* stream, int dtype, int out_dtype, const void* out, int
                     int rows, int C, int half, float cfg_scale, float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, float min_log,
                     float max_log, float nonzero, float temperature);
 
+/* ---- The skinny GEMM of a LoRA adapter (csrc/gemm_skinny.hip).  Every adapter GEMM has one dimension equal to the rank r; with r as the
+ * OUTPUT width the tiled kernels of setok_linear get cdiv(M, 128) workgroups that each walk the whole K.  Pure additions: the ABI version stays 9. */
+
+/* Widest output setok_linear_skinny takes, and the columns of one K slice (counted from column 0; a multiple of 64). */
+#define SETOK_SKINNY_MAX_N 256
+#ifndef SETOK_SKINNY_KSLICE
+#define SETOK_SKINNY_KSLICE 512
+#endif
+
+/* Floats of workspace setok_linear_skinny needs: ceil(K / SETOK_SKINNY_KSLICE) * M * N (0 for an empty problem). */
+int64_t setok_linear_skinny_workspace(int M, int N, int K);
+
+/* C[M, N] = alpha * A[M, K] · W[N, K]^T   for 1 <= N <= SETOK_SKINNY_MAX_N, N % 16 == 0, any M >= 0.  A, W in `dtype` (the build's 16-bit type
+ * or SETOK_F32), C in out_dtype = `dtype` or SETOK_F32.  K % 64 == 0 (16-bit) or K % 16 == 0 (fp32).  Strides as in setok_linear, in elements:
+ * lda >= K, ldw >= K (multiples of 8 / 4: 16-byte pieces), ldc >= N (a multiple of 8 for a 16-bit C, of 4 for fp32); A, W, C and ws 16-byte
+ * aligned; a stride changes addresses only.  No element outside A's [0, M) x [0, K) or W's [0, N) x [0, K) is read, none outside C's
+ * [0, M) x [0, N) is written.
+ * Split-K by a rule in K alone: grid (blocks of 128 rows, slices of SETOK_SKINNY_KSLICE columns); every workgroup writes the fp32 partial of its
+ * rows over its slice to ws[slice][M][N], and a second launch sums a row's partials in slice order, multiplies by alpha once in fp32 and rounds
+ * once.  No atomics, no hand-off between workgroups.  A row's bits depend on that row of A, W, K and alpha alone — not on M, the strides or the
+ * rows around it.  It is NOT setok_linear's summation order.  16-bit: v_mfma_f32_32x32x16, W's slice tile through LDS (N x 64 columns per K
+ * step), A's rows streamed.  SETOK_F32 is the parity mode: a plain k-ordered fmaf chain per slice.
+ * ws: ws_floats >= setok_linear_skinny_workspace(M, N, K) floats, the caller's.  A shorter workspace, and every other bad argument, is
+ * SETOK_EINVAL with a message naming it, before any launch. */
+int setok_linear_skinny(void* stream, int dtype, int out_dtype, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
+                        int M, int N, int K, float alpha, float* ws, int64_t ws_floats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ class SetokConfig(C.Structure):
 
 
 RESTYPES = {"setok_last_error": C.c_char_p, "setok_ctx_error": C.c_char_p, "setok_encode_workspace_bytes": _i64, "setok_destroy": None,
-            "setok_attention_extend_workspace": _i64}
+            "setok_attention_extend_workspace": _i64, "setok_linear_skinny_workspace": _i64}
 
 # name -> argtypes; mirrors include/setok_hip.h declaration by declaration
 SIGNATURES = {
@@ -117,6 +117,8 @@ SIGNATURES = {
     "setok_linear_fp8w_wgs": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i],
     "setok_kv_append_fp8": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa_fp8kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_linear_skinny_workspace": [_i, _i, _i],
+    "setok_linear_skinny": [_vp, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _f, _vp, _i64],
     "setok_timestep_embedding": [_vp, _i, _vp, _vp, _i, _i, _f],
     "setok_add_silu": [_vp, _i, _vp, _vp, _i64, _vp, _i, _i],
     "setok_adaln_modulate": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _f],

@@ -15,6 +15,8 @@ inside the transposes for db, setok_gelu_bwd, setok_layernorm_bwd, setok_splice_
                   reconstruction_loss
     LlamaFn       LlamaModel.forward with the decoder stack frozen  d loss / d inputs_embeds across the decoder layers (llama_train.py;
     LlamaLMFn     SetokimLlamaPrefill.forward (logits, LM loss)     the LLM's own weights get no gradient: stage 2 freezes them)
+    LlamaLoraFn   the same two with LoRA adapters attached (lora.py)  d loss / d inputs_embeds and every adapter's dA, dB: the reference's
+    LlamaLoraLMFn                                                   finetune stage (llama_train.llama_lora_backward)
 
 With them `loss.backward()` on SetokimLlamaPrefill's language-model loss reaches the projector: stage 2 end to end.
 Everything else on the path is inference-only and says so (round 4): the forward always runs — reference-style inference callers
@@ -384,3 +386,82 @@ class LlamaLMFn(torch.autograd.Function):
         del dl
         dx = llama_backward(ctx.prefill.model, saved, dhidden.reshape(B, T, -1))
         return None, _grad_as(dx, like), None, None, None
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the frozen LLM with LoRA adapters (lora.py): the reference's finetune stage trains the adapters (and the projector) through the same loss
+# ----------------------------------------------------------------------------------------------------------------------------
+def _adapter_grads(model, grads: Dict[str, torch.Tensor], params: Sequence[torch.Tensor], needs: Sequence[bool]):
+    """The fp32 gradients of llama_lora_backward in the order of LoraAdapters.flat(), each in its adapter's dtype; None where none is wanted."""
+    names, _ = model.lora.flat()
+    return tuple(_grad_as(grads[n], p) if need else None for n, p, need in zip(names, params, needs))
+
+
+class LlamaLoraFn(torch.autograd.Function):
+    """hidden = LlamaModel(inputs_embeds) with adapters attached and the stack frozen: d / d inputs_embeds and every dA, dB.
+    `params`: LoraAdapters.flat()'s tensors, passed so that autograd routes their gradients."""
+
+    @staticmethod
+    def forward(ctx, model, inputs_embeds: torch.Tensor, attention_mask, position_ids, *params: torch.Tensor):
+        from .llama_train import llama_lora_forward_train
+        hidden, saved = llama_lora_forward_train(model, inputs_embeds.detach(), attention_mask, position_ids)
+        ctx.model, ctx.saved, ctx.like, ctx.params = model, saved, inputs_embeds, params
+        return hidden
+
+    @staticmethod
+    def backward(ctx, dhidden: torch.Tensor):
+        from .llama_train import llama_lora_backward
+        if ctx.saved is None:
+            raise _spent("LlamaModel.forward")
+        saved, ctx.saved = ctx.saved, None
+        like, ctx.like = ctx.like, None
+        dx, grads = llama_lora_backward(ctx.model, saved, dhidden)
+        out = _adapter_grads(ctx.model, grads, ctx.params, ctx.needs_input_grad[4:])
+        return (None, _grad_as(dx, like) if ctx.needs_input_grad[1] else None, None, None) + out
+
+
+class LlamaLoraLMFn(torch.autograd.Function):
+    """LlamaLMFn with adapters attached: (logits, loss) and, backward, d / d inputs_embeds plus every dA, dB."""
+
+    @staticmethod
+    def forward(ctx, prefill, inputs_embeds: torch.Tensor, attention_mask, position_ids, labels, *params: torch.Tensor):
+        from .llama_train import llama_lora_forward_train
+        hidden, saved = llama_lora_forward_train(prefill.model, inputs_embeds.detach(), attention_mask, position_ids)
+        B, T, D = hidden.shape
+        w = prefill.lm_head.weight.detach().contiguous()
+        logits = ops.linear(hidden.reshape(B * T, D), w).reshape(B, T, -1)
+        loss_out = ops.lm_loss(logits, labels, attention_mask) if labels is not None else None
+        ctx.prefill, ctx.saved, ctx.like, ctx.params = prefill, saved, inputs_embeds, params
+        ctx.lm = (logits, labels, attention_mask, loss_out)
+        ctx.set_materialize_grads(False)
+        return logits, (loss_out[0].clone() if loss_out is not None else logits.new_zeros((), dtype=torch.float32))
+
+    @staticmethod
+    def backward(ctx, dlogits: Optional[torch.Tensor], dloss: Optional[torch.Tensor]):
+        from .llama_train import llama_lora_backward
+        if ctx.saved is None:
+            raise _spent("SetokimLlamaPrefill.forward")
+        saved, ctx.saved = ctx.saved, None
+        (logits, labels, attention_mask, loss_out), ctx.lm = ctx.lm, None
+        like, ctx.like = ctx.like, None
+        none = (None,) * (5 + len(ctx.params))
+        if dlogits is None and (dloss is None or loss_out is None):
+            return none
+        B, T, V = logits.shape
+        w = ctx.prefill.lm_head.weight.detach().contiguous()
+        gran = ops.k_align(logits.dtype)
+        Vp = ops.round_up(V, gran)                                    # (as LlamaLMFn: the dX GEMM contracts over the vocabulary)
+        dl = (torch.zeros if Vp != V else torch.empty)((B * T, Vp), dtype=logits.dtype, device=logits.device)
+        view = dl[:, :V].view(B, T, V) if Vp == V else dl.view(B, T, Vp)[:, :, :V]
+        if dloss is not None and loss_out is not None:
+            ops.lm_loss_bwd(logits, labels, attention_mask, loss_out, upstream=dloss, out=view)
+            if dlogits is not None:
+                view += dlogits.to(logits.dtype)
+        else:
+            view.copy_(dlogits.to(logits.dtype))
+        del logits
+        dhidden = ops.linear(dl, ops.transpose(w, pad_to=gran))       # lm_head dX
+        del dl
+        dx, grads = llama_lora_backward(ctx.prefill.model, saved, dhidden.reshape(B, T, -1))
+        out = _adapter_grads(ctx.prefill.model, grads, ctx.params, ctx.needs_input_grad[5:])
+        return (None, _grad_as(dx, like) if ctx.needs_input_grad[1] else None, None, None, None) + out

@@ -21,6 +21,10 @@ prefill that also fills a `generation.KVCache`, `LlamaModel.decode_step` runs on
 `SetokimLlamaPrefill.generate` is the loop.  `LlamaModel.extend` adds Tn >= 1 tokens per sequence to a cache that already holds
 some (csrc/attn_extend.hip): `generate(prefill_chunk=)` feeds a prompt in windows through it and `generate(past=)` continues a conversation from the
 state an earlier call returned.
+
+Fine-tuning (the reference's scripts/finetune.sh: LoRA on every decoder Linear): `add_lora_` attaches adapters (lora.py) and freezes the stack; with
+them `forward` is differentiable with respect to `inputs_embeds` AND the adapters (autograd.LlamaLoraFn / LlamaLoraLMFn), `merge_lora_` folds them
+into the weights, and the KV-cached entry points refuse unmerged adapters.
 """
 from __future__ import annotations
 
@@ -29,9 +33,10 @@ from typing import Any, Dict, Optional
 import torch
 import torch.nn as nn
 
-from . import autograd, ops
+from . import autograd, lora, ops
 from ._packcache import PackCacheMixin
 from .arch import SetokimVisionMixin, config_get
+from .lora import ALL_SEVEN
 
 
 class _RMSNorm(nn.Module):
@@ -84,6 +89,52 @@ class LlamaModel(PackCacheMixin, nn.Module):
         self.norm = _RMSNorm(hidden_size, rms_norm_eps)
         self._init_pack_cache()
         self._fp8 = None                                                        # quantize_fp8_(): the packed stack in fp8 storage
+        self.lora = None                                                        # add_lora_(): a lora.LoraAdapters, outside self.layers
+
+    # ---- LoRA adapters (lora.py; the arithmetic is llama_train.llama_lora_forward_train / llama_lora_backward) ---------------------------------
+    def add_lora_(self, r: int, lora_alpha: float, target_modules=ALL_SEVEN, lora_dropout: float = 0.0):
+        """Attach LoRA adapters to the targeted projections of every decoder layer (the reference's finetune stage: peft's LoraConfig over all
+        seven Linears, r = 128, lora_alpha = 256, dropout 0.05): per projection `lora_A` (r, in), Kaiming-uniform with a = sqrt(5), and `lora_B`
+        (out, r), zero, in the model's element type and on its device, kept in `self.lora`; the scaling is lora_alpha / r.  `layers.*` and `norm`
+        are frozen.  A fresh adapter changes no bit of the forward.  Refused by name: r off the GEMM's K granule (64 in the 16-bit types, 16 in
+        fp32) or above 128, an unknown target, a second call, a stack in fp8 storage.  Call it on the device and in the dtype the model trains in."""
+        targets = lora.check_request(self, r, lora_alpha, target_modules, lora_dropout)
+        self.lora = lora.LoraAdapters(self, r, lora_alpha, targets, lora_dropout)
+        self.layers.requires_grad_(False)
+        self.norm.requires_grad_(False)
+        return self
+
+    def _need_lora(self, what: str):
+        if self.lora is None:
+            raise ValueError(f"LlamaModel.{what}: no adapters are attached (add_lora_ first)")
+        return self.lora
+
+    def _refuse_unmerged(self, what: str) -> None:
+        if self.lora is not None:
+            raise NotImplementedError(f"{what}: LoRA adapters are attached and the inference kernels read the base weights only; call merge_lora_() "
+                                      "first (forward() applies unmerged adapters)")
+
+    def lora_state_dict(self):
+        """The adapters under peft's adapter-file keys (lora.state_dict_of: `base_model.model.model.layers.{i}.self_attn.q_proj.lora_A.weight`, ...).
+        The format follows the reference's save and load code and is not checked against a peft-written file."""
+        return lora.state_dict_of(self._need_lora("lora_state_dict"))
+
+    def load_lora_state_dict(self, sd) -> None:
+        """Load what lora_state_dict wrote; the `.lora_A.default.weight` spelling of an in-memory PeftModel is accepted too."""
+        lora.load_state_dict_into(self._need_lora("load_lora_state_dict"), sd)
+
+    @torch.no_grad()
+    def merge_lora_(self):
+        """W <- W + (lora_alpha / r) B A for every adapted projection, formed in fp32 and rounded once; the adapters are then removed (peft's
+        merge_and_unload).  The packed copies rebuild through their version key."""
+        self._need_lora("merge_lora_")
+        lora.merge_into(self)
+        self.lora = None
+        return self
+
+    def _stack_and_embed_parameters(self):
+        """Every parameter but the adapters': what the packed copies are built from."""
+        return [p for n, p in self.named_parameters() if not n.startswith("lora.")]
 
     @property
     def weight_format(self) -> str:
@@ -100,6 +151,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         `decode_step` streams the bytes through `ops.linear_fp8w`.  With `free_master` the Linear parameters release their storage (N * K + N
         bytes per matrix remain) and `state_dict()` is refused; without it the masters stay for `state_dict()` only — the fp8 copy computes, and an
         in-place update of any stack parameter afterwards is refused at the next forward instead of being silently ignored.  Call it on the device and in the dtype the model will run in.  Inference only."""
+        self._refuse_unmerged("LlamaModel.quantize_fp8_")
         if self._fp8 is not None:
             raise NotImplementedError("LlamaModel.quantize_fp8_: the stack is already in fp8 storage (a second quantisation would re-round it)")
         f32 = lambda t: t.detach().float().contiguous()
@@ -122,7 +174,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
                     lin.weight.requires_grad_(False)
                     lin.weight.data = torch.empty(0, dtype=w0.dtype, device=w0.device)
         self._fp8 = dict(key=(w0.dtype, str(w0.device)), layers=layers, norm=f32(self.norm.weight), largest=largest, scratch=None,
-                         freed=bool(free_master), versions=self._versions(self.parameters()))
+                         freed=bool(free_master), versions=self._versions(self._stack_and_embed_parameters()))
         self._packed = {}
         return self
 
@@ -151,12 +203,12 @@ class LlamaModel(PackCacheMixin, nn.Module):
             if self._fp8["key"] != (w.dtype, str(w.device)):
                 raise NotImplementedError(f"LlamaModel: the stack was quantised to fp8 as {self._fp8['key']} and cannot follow a move to "
                                           f"{(w.dtype, str(w.device))}")
-            if self._versions(self.parameters()) != self._fp8["versions"]:
+            if self._versions(self._stack_and_embed_parameters()) != self._fp8["versions"]:
                 # (free_master=False keeps the masters for state_dict(); the fp8 copy is what computes, and it cannot follow them)
                 raise NotImplementedError("LlamaModel: a parameter of the stack was modified in place after quantize_fp8_ (a LoRA merge, an optimiser "
                                           "step): the fp8 copy is stale and re-quantising is not implemented; quantise after the last update")
             return self._fp8
-        key = (w.dtype, str(w.device), self._versions(self.parameters()))      # every tensor: a LoRA merge into q_proj / v_proj alone must rebuild the fused copies
+        key = (w.dtype, str(w.device), self._versions(self._stack_and_embed_parameters()))      # every tensor: a LoRA merge into q_proj / v_proj alone must rebuild the fused copies
         if self._packed.get("key") == key:
             return self._packed
         f32 = lambda t: t.detach().float().contiguous()
@@ -178,10 +230,18 @@ class LlamaModel(PackCacheMixin, nn.Module):
           a decoder-stack parameter (layers.*, norm) requires one   the prefill runs and the result's backward raises — training the LLM's own
                                                                  weights is the reference's HF-Trainer side (SURVEY.md §2 "OUT")
           the stack is frozen and inputs_embeds requires one     the same values with a grad_fn (autograd.LlamaFn): backward() delivers
-                                                                 d loss / d inputs_embeds"""
+                                                                 d loss / d inputs_embeds
+          adapters attached (add_lora_), the stack frozen, an    the adapted forward with a grad_fn (autograd.LlamaLoraFn): backward() delivers
+          adapter or inputs_embeds requires one                  d loss / d inputs_embeds and every dA, dB
+        With adapters attached the no-graph rows apply them too (the same calls, nothing kept)."""
         if self._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
             raise NotImplementedError("LlamaModel.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 weights)")
-        if torch.is_grad_enabled() and inputs_embeds.requires_grad and not self.stack_requires_grad():
+        if self.lora is not None and torch.is_grad_enabled() and not self.stack_requires_grad():
+            # adapters attached, the stack frozen, an adapter or inputs_embeds requires a gradient: d / d inputs_embeds and every dA, dB
+            names, params = self.lora.flat()
+            if inputs_embeds.requires_grad or any(p.requires_grad for p in params):
+                return autograd.LlamaLoraFn.apply(self, inputs_embeds, attention_mask, position_ids, *params)
+        elif torch.is_grad_enabled() and inputs_embeds.requires_grad and not self.stack_requires_grad():
             return autograd.LlamaFn.apply(self, inputs_embeds, attention_mask, position_ids)
         with torch.no_grad():
             out = self._forward(inputs_embeds, attention_mask, position_ids)
@@ -195,6 +255,11 @@ class LlamaModel(PackCacheMixin, nn.Module):
     def _forward(self, inputs_embeds, attention_mask=None, position_ids=None, cache=None):
         """The prefill.  With `cache` (a generation.KVCache, empty) every layer's post-rotary keys / values are also copied to its slots [0, T):
         one more launch per layer, nothing else changes."""
+        if self.lora is not None:                                               # unmerged adapters: the training forward's calls (its bits), nothing kept
+            if cache is not None:
+                self._refuse_unmerged("LlamaModel.prefill")
+            from .llama_train import llama_lora_forward_train
+            return llama_lora_forward_train(self, inputs_embeds, attention_mask, position_ids, keep=False)[0]
         B, T, D = inputs_embeds.shape
         pk = self._pack()
         H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
@@ -234,6 +299,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
     def prefill(self, inputs_embeds, attention_mask=None, position_ids=None, cache=None):
         """`_forward` (the same calls in the same order: the same bits) that also fills `cache` — the first call of HF's generate, which returns
         `past_key_values` next to the hidden states (setokim_llama.py:133,189).  Returns the final-norm hidden states (B, T, D)."""
+        self._refuse_unmerged("LlamaModel.prefill")
         if cache is None:
             raise ValueError("LlamaModel.prefill needs a generation.KVCache to fill (forward() is the prefill without one)")
         B, T, _ = inputs_embeds.shape
@@ -248,6 +314,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         `cache.len` of every sequence and rotated to the sequence's own next position (`cache.next_pos`: the position of its last attended token
         + 1), so left- and right-padded prompts both work — with right padding the masked slots simply stay masked.  HF LlamaDecoderLayer.forward with
         `past_key_values` on a one-token input; the GEMMs are the prefill's, at M = B."""
+        self._refuse_unmerged("LlamaModel.decode_step")
         B, D = inputs_embeds.shape
         slot = cache.len
         if slot < 1 or slot >= cache.cap or B != cache.B:
@@ -291,6 +358,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         stays masked and its hidden state means nothing.  HF LlamaDecoderLayer.forward with `past_key_values` on a Tn-token input; the GEMMs are the
         prefill's at M = B * Tn (fp8 weights: `decode_step`'s streaming GEMM up to FP8W_MAX_M rows, the dequantise scratch above).
         Refused with the cache untouched: an fp8 KV cache (NotImplementedError), a wrong B, Tn == 0 on an empty cache, len + Tn > cap (ValueError)."""
+        self._refuse_unmerged("LlamaModel.extend")
         B, Tn, D = inputs_embeds.shape
         len0 = cache.len
         if cache.kv_format == "fp8":
@@ -425,6 +493,22 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     def weight_format(self) -> str:
         return self.model.weight_format
 
+    def add_lora_(self, r: int, lora_alpha: float, target_modules=ALL_SEVEN, lora_dropout: float = 0.0):
+        """`LlamaModel.add_lora_` on the decoder stack; lm_head is frozen with it (the reference excludes it from the adapted Linears)."""
+        self.model.add_lora_(r, lora_alpha, target_modules, lora_dropout)
+        self.lm_head.requires_grad_(False)
+        return self
+
+    def lora_state_dict(self):
+        return self.model.lora_state_dict()
+
+    def load_lora_state_dict(self, sd) -> None:
+        self.model.load_lora_state_dict(sd)
+
+    def merge_lora_(self):
+        self.model.merge_lora_()
+        return self
+
     def quantize_fp8_(self, free_master: bool = True):
         """`LlamaModel.quantize_fp8_`: the decoder stack's projection weights into fp8 storage (embed_tokens, the norms and lm_head stay)."""
         self.model.quantize_fp8_(free_master)
@@ -451,13 +535,18 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         if self.model._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
             raise NotImplementedError("SetokimLlamaPrefill.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 "
                                       "weights); run it under torch.no_grad() or detach inputs_embeds")
-        if may_train and inputs_embeds.requires_grad:
+        adapters = self.model.lora.flat()[1] if self.model.lora is not None else []
+        if may_train and (inputs_embeds.requires_grad or any(p.requires_grad for p in adapters)):
             if last_token_only:
                 what = "SetokimLlamaPrefill.forward with last_token_only=True (a generation step: inference-only)"
             else:
                 if return_loss and new_labels is None:
                     raise ValueError("return_loss needs labels")
-                logits, loss = autograd.LlamaLMFn.apply(self, inputs_embeds, attention_mask, position_ids, new_labels if return_loss else None)
+                if adapters:
+                    logits, loss = autograd.LlamaLoraLMFn.apply(self, inputs_embeds, attention_mask, position_ids, new_labels if return_loss else None,
+                                                                *adapters)
+                else:
+                    logits, loss = autograd.LlamaLMFn.apply(self, inputs_embeds, attention_mask, position_ids, new_labels if return_loss else None)
                 return (logits, new_labels, attention_mask, loss) if return_loss else (logits, new_labels, attention_mask)
         with torch.no_grad():
             out = self._head(inputs_embeds.detach(), attention_mask, position_ids, new_labels, last_token_only, return_loss)
@@ -550,6 +639,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
         from .generation import Drafter, GenerateOutput, GenerationState, KVCache, Sampler
+        self.model._refuse_unmerged("SetokimLlamaPrefill.generate")
         sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
         if do_sample or sampling:
             raise NotImplementedError(f"SetokimLlamaPrefill.generate: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "

@@ -119,8 +119,63 @@ def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, residual: Option
     assert out.shape == (M, N) and out.dtype == od
     if residual is not None:
         assert residual.shape == (M, N) and residual.dtype == od
+    if not (a.is_contiguous() and out.is_contiguous() and (residual is None or residual.is_contiguous())):
+        return _linear_windows(a, w, bias, residual, act, out)
     _lib.call("setok_linear", _stream(), _code(a.dtype), _code(od), _p(a), K, _p(w), _p(_f32(bias)), _p(residual),
               _p(out), N, M, N, K, act, 1, 0, 0, 0)
+    return out
+
+
+def _linear_windows(a: Tensor, w: Tensor, bias, residual, act: int, out: Tensor) -> Tensor:
+    """`linear` on column windows of wider buffers: `a` and `out` with dense rows and their buffers' row strides (a stride changes addresses
+    only); a residual shares out's stride, as setok_linear reads it (the LoRA update of a window of the fused q|k|v output, in place)."""
+    M, K = a.shape
+    N = w.shape[0]
+    ldc = _rows_ld(out)
+    assert w.is_contiguous() and (residual is None or M <= 1 or _rows_ld(residual) == ldc), "residual shares out's row stride"
+    _lib.call("setok_linear", _stream(), _code(a.dtype), _code(out.dtype), a.data_ptr(), _rows_ld(a), _p(w), _p(_f32(bias)),
+              None if residual is None else residual.data_ptr(), out.data_ptr(), ldc, M, N, K, act, 1, 0, 0, 0)
+    return out
+
+
+# ---- the skinny GEMM of a LoRA adapter (csrc/gemm_skinny.hip) -------------------------------------------------------------------------------
+SKINNY_MAX_N = 256                                # SETOK_SKINNY_MAX_N of include/setok_hip.h
+
+
+def linear_skinny_workspace(M: int, N: int, K: int, half: bool = False) -> int:
+    """Floats of workspace `setok_linear_skinny` needs for an (M, K) x (N, K) problem: ceil(K / SETOK_SKINNY_KSLICE) * M * N."""
+    return int(_lib.load(half).setok_linear_skinny_workspace(M, N, K))
+
+
+def skinny_kslice(half: bool = False) -> int:
+    """SETOK_SKINNY_KSLICE of the loaded library, read off its workspace rule: the largest K that is still one slice."""
+    K = 64
+    while linear_skinny_workspace(1, 16, K + 64, half) == 16:
+        K += 64
+    return K
+
+
+def linear_skinny(a: Tensor, w: Tensor, alpha: float = 1.0, out: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+                  ws: Optional[Tensor] = None) -> Tensor:
+    """out = alpha * a @ w.T for a narrow output: a (M, K), w (N, K) with N <= SKINNY_MAX_N, N % 16 == 0; out in a.dtype or fp32.  Split-K by a
+    rule in K alone with a fixed-order sum (include/setok_hip.h: setok_linear_skinny): a row's bits do not depend on M or the strides.  a, w and
+    out may be column windows of wider buffers.  `ws`: fp32 scratch of at least linear_skinny_workspace(M, N, K) floats (default: the
+    stream-ordered scratch `linear_tn` uses)."""
+    M, K = a.shape
+    N, K2 = w.shape
+    assert K == K2 and a.dtype == w.dtype
+    od = out_dtype or a.dtype
+    if out is None:
+        out = torch.empty((M, N), dtype=od, device=a.device)
+    assert out.shape == (M, N) and out.dtype == od
+    if M == 0:                                        # nothing to compute (an empty tensor has no address to pass)
+        return out
+    need = linear_skinny_workspace(M, N, K, a.dtype == torch.float16)
+    if ws is None:
+        ws = _ws(a.device, need)
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.is_cuda
+    _lib.call("setok_linear_skinny", _stream(), _code(a.dtype), _code(od), a.data_ptr(), _rows_ld(a), w.data_ptr(), _rows_ld(w), out.data_ptr(),
+              _rows_ld(out), M, N, K, float(alpha), ws.data_ptr(), ws.numel())
     return out
 
 
