@@ -685,6 +685,53 @@ int setok_linear_fp8w(void* stream, int dtype, const void* A, int64_t lda, const
 int setok_linear_fp8w_wgs(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const int8_t* e,
                           const void* residual, void* C, int64_t ldc, int M, int N, int K, int min_wgs);
 
+/* ---- MXFP4 weight-only decode (csrc/gemm_mxfp4w.hip): the same idea at half the bytes again, in the OCP Microscaling format gfx950 converts in
+ * hardware.  A matrix W (N, K), K % 32 == 0, is stored in two arrays:
+ *     q (N, K/2) uint8     byte j of a row holds element 2j in its low nibble and element 2j+1 in its high nibble (torch's float4_e2m1fn_x2 order)
+ *     s (N, K/32) uint8    e8m0 scale bytes, plain row-major: block b of a row covers k in [32 b, 32 b + 32)
+ * and means exactly
+ *     W'[n, k] = value_e2m1(nibble[n, k]) * 2^(s[n, k / 32] - 127);     a block whose scale byte is 0xFF is 32 NaNs.
+ * A nibble's bit 3 is the sign; magnitude codes 0..7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6.  The quantiser emits scale bytes in [114, 140] (and 0xFF), so
+ * that 0.5 * 2^e and 6 * 2^e are normal numbers in fp16 as well: W' is exactly representable in bf16, fp16 and fp32, a quantised model is an ordinary
+ * model whose weights lie on a grid, and setok_linear on the dequantised W' computes the same function.
+ * Scale bytes the quantiser never emits are still accepted by the dequantiser and the GEMM: the byte is the exponent field of the hardware
+ * converter's fp32 scale operand, the value is value_e2m1 * 2^(s - 127) formed in fp32 and rounded once to the element type (exact in fp32 and bf16
+ * wherever the product is a normal number there; fp16 overflows and underflows as its range dictates).
+ * Pure additions: the ABI version stays 9. */
+
+/* The quantiser, per block of 32 elements of a row:  any non-finite entry -> scale byte 0xFF and nibbles 0 (a non-finite weight stays visible);
+ * otherwise amax = max |W|;  a block of zeros gets scale byte 127;  any other block e = floor(log2(amax)) - 2 (the OCP MX v1.0 rule, by exponent
+ * arithmetic, no log2), clamped to [-13, 13], scale byte e + 127;  nibble = round-to-nearest(W * 2^-e) saturating at +-6 (reachable where amax is
+ * in (6, 8) * 2^e or the clamp at 13 binds), ties to the even code: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4;  the sign bit
+ * is W's own sign bit, so -0.0 and a negative that rounds to zero store 0x8.
+ * W: (N, K) in `dtype`, row stride ldw >= K elements;  q: row stride ldq >= K/2 bytes;  s: row stride lds >= K/32 bytes;  any alignment.  Each of
+ * W, q, s may be a window of a wider buffer; nothing outside them is written.  One thread per block, no atomics. */
+int setok_quantize_mxfp4_rows(void* stream, int dtype, const void* W, int64_t ldw, uint8_t* q, int64_t ldq, uint8_t* s, int64_t lds, int N, int K);
+
+/* The exact inverse: W[n, k] = W'[n, k] in `dtype`.  Same strides.  Rows of q in 4-byte pieces and rows of W in 16-byte pieces take a packed path
+ * (8 elements per lane), anything else a byte-wise one; both give the same bits. */
+int setok_dequantize_mxfp4_rows(void* stream, int dtype, const uint8_t* q, int64_t ldq, const uint8_t* s, int64_t lds, void* W, int64_t ldw, int N, int K);
+
+/* C[M, N] = A[M, K] · W'^T + residual[M, N]   (residual optional; C may alias it) for 1 <= M <= 64: the weight-streaming GEMM of a decode step on
+ * the nibbles.  A, residual and C have element type `dtype`; products of the exact element-type values of A and W' (the block scale is applied
+ * when the block is converted, by the hardware converter), fp32 accumulation, one rounding to `dtype`.  K % 128 == 0 (16-bit) or K % 32 == 0
+ * (fp32), any N >= 1.
+ * Strides: lda >= K (elements, a multiple of 8 / 4: 16-byte pieces, A 16-byte aligned), ldc >= N (C AND residual, any value), ldq >= K/2 (bytes, a
+ * multiple of 16, q 16-byte aligned: a lane's 16-byte load is one block), lds >= K/32 (bytes, any value).  Anything else — M > 64 included:
+ * dequantise and call setok_linear — is SETOK_EINVAL with a message naming the argument, before any launch.
+ * No element outside A's [0, M) x [0, K), q's [0, N) x [0, K/2) or s's [0, N) x [0, K/32) is read and none outside C's [0, M) x [0, N) is written.
+ * A row's bits depend on that row of A (and of residual), q and s alone — not on M, the strides, the band or the rows around it: there is one
+ * summation order, fixed by K.  It is NOT setok_linear's order.  No atomics, no hand-off between workgroups.
+ * SETOK_F32 is the parity mode, as in setok_linear_fp8w: compensated fp32 arithmetic, a different algorithm from the 16-bit MFMA path. */
+int setok_linear_mxfp4w(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const uint8_t* s, int64_t lds,
+                        const void* residual, void* C, int64_t ldc, int M, int N, int K);
+
+/* setok_linear_mxfp4w with the floor of its band rule as an argument (setok_linear_fp8w_wgs's rule: the widest band of 64 / 32 / 16 columns — 64 from
+ * three row tiles, 32 at two, 16 at one — that leaves ceil(N / band) >= min_wgs workgroups; setok_linear_mxfp4w passes 256).  The band decides
+ * which workgroup computes a column and never a bit of C.  SETOK_F32 ignores it. */
+int setok_linear_mxfp4w_wgs(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const uint8_t* s, int64_t lds,
+                            const void* residual, void* C, int64_t ldc, int M, int N, int K, int min_wgs);
+
 /* ---- FP8 KV cache (csrc/attn_decode.hip): the decode attention is bound by the K / V bytes it reads, so the cache may be STORED by the rule
  * above, one cache row — the Dh post-rotary elements of one (sequence, key / value head, slot), of K or of V — taking the place of a weight row:
  * Dh e4m3fn bytes and one int8 exponent, meaning exactly value(q[d]) * 2^e with e in [-15, 7]; amax over the finite entries, e the smallest

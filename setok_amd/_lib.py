@@ -115,6 +115,10 @@ SIGNATURES = {
     "setok_dequantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _i],
     "setok_linear_fp8w": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i],
     "setok_linear_fp8w_wgs": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i],
+    "setok_quantize_mxfp4_rows": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i],
+    "setok_dequantize_mxfp4_rows": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i],
+    "setok_linear_mxfp4w": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i],
+    "setok_linear_mxfp4w_wgs": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i],
     "setok_kv_append_fp8": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa_fp8kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_linear_skinny_workspace": [_i, _i, _i],

@@ -89,6 +89,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         self.norm = _RMSNorm(hidden_size, rms_norm_eps)
         self._init_pack_cache()
         self._fp8 = None                                                        # quantize_fp8_(): the packed stack in fp8 storage
+        self._mxfp4 = None                                                      # quantize_mxfp4_(): the packed stack in MXFP4 storage (never both)
         self.lora = None                                                        # add_lora_(): a lora.LoraAdapters, outside self.layers
 
     # ---- LoRA adapters (lora.py; the arithmetic is llama_train.llama_lora_forward_train / llama_lora_backward) ---------------------------------
@@ -138,7 +139,9 @@ class LlamaModel(PackCacheMixin, nn.Module):
 
     @property
     def weight_format(self) -> str:
-        """"native" (the Linear weights in the model's element type) or "fp8_e4m3" after quantize_fp8_()."""
+        """"native" (the Linear weights in the model's element type), "fp8_e4m3" after quantize_fp8_() or "mxfp4_e2m1" after quantize_mxfp4_()."""
+        if self._mxfp4 is not None:
+            return "mxfp4_e2m1"
         return "native" if self._fp8 is None else "fp8_e4m3"
 
     @torch.no_grad()
@@ -152,6 +155,8 @@ class LlamaModel(PackCacheMixin, nn.Module):
         bytes per matrix remain) and `state_dict()` is refused; without it the masters stay for `state_dict()` only — the fp8 copy computes, and an
         in-place update of any stack parameter afterwards is refused at the next forward instead of being silently ignored.  Call it on the device and in the dtype the model will run in.  Inference only."""
         self._refuse_unmerged("LlamaModel.quantize_fp8_")
+        if self._mxfp4 is not None:
+            raise NotImplementedError("LlamaModel.quantize_fp8_: the stack is already in mxfp4 storage (a second quantisation would re-round it)")
         if self._fp8 is not None:
             raise NotImplementedError("LlamaModel.quantize_fp8_: the stack is already in fp8 storage (a second quantisation would re-round it)")
         f32 = lambda t: t.detach().float().contiguous()
@@ -178,27 +183,90 @@ class LlamaModel(PackCacheMixin, nn.Module):
         self._packed = {}
         return self
 
+    @torch.no_grad()
+    def quantize_mxfp4_(self, free_master: bool = True):
+        """Store the stack's projection weights in OCP MXFP4 (include/setok_hip.h, "MXFP4 weight-only decode"): e2m1 nibbles with one e8m0
+        power-of-two scale per 32 elements of a row, for the same four fused operands per layer as `quantize_fp8_`, quantised on the device one layer
+        at a time.  Blocks lie along K inside a row, so fused rows stay independent.  embed_tokens, the norms and lm_head stay.  The model then
+        IS the Llama whose weights are W' = value(nibble) * 2^(s - 127), exactly representable in the element type: `_forward` / `prefill`
+        dequantise each matrix into one reusable scratch buffer and run the existing kernels, `decode_step` and `extend` stream the nibbles through
+        `ops.linear_mxfp4w` up to 64 rows.  With `free_master` the Linear parameters release their storage (N * K / 2 + N * K / 32 bytes per matrix
+        remain) and `state_dict()` is refused.  Refused before anything is freed: a hidden or intermediate size off the streaming GEMM's K granule
+        (128 in the 16-bit types, 32 in fp32; ValueError naming the matrix), a stack already quantised, unmerged adapters.  Inference only."""
+        self._refuse_unmerged("LlamaModel.quantize_mxfp4_")
+        if self._mxfp4 is not None:
+            raise NotImplementedError("LlamaModel.quantize_mxfp4_: the stack is already in mxfp4 storage (a second quantisation would re-round it)")
+        if self._fp8 is not None:
+            raise NotImplementedError("LlamaModel.quantize_mxfp4_: the stack is already in fp8 storage and its masters may be gone; mxfp4 "
+                                      "quantises the native weights")
+        f32 = lambda t: t.detach().float().contiguous()
+        w0 = self.norm.weight
+        gran = 32 if w0.dtype == torch.float32 else 128
+        for li, l in enumerate(self.layers):
+            a, m = l.self_attn, l.mlp
+            for name, lin in (("self_attn.q_proj", a.q_proj), ("self_attn.k_proj", a.k_proj), ("self_attn.v_proj", a.v_proj),
+                              ("self_attn.o_proj", a.o_proj), ("mlp.gate_proj", m.gate_proj), ("mlp.up_proj", m.up_proj), ("mlp.down_proj", m.down_proj)):
+                K = lin.weight.shape[1]
+                if K % gran != 0:
+                    raise ValueError(f"LlamaModel.quantize_mxfp4_: layers.{li}.{name} has in_features={K}, not a multiple of {gran} (the K granule of "
+                                     f"the mxfp4 streaming GEMM in {w0.dtype}); nothing was quantised")
+        if not w0.is_cuda:
+            raise NotImplementedError("LlamaModel.quantize_mxfp4_: the mxfp4 quantiser runs on the device; move the model there first")
+        layers, largest = [], 0
+        for l in self.layers:
+            a, m = l.self_attn, l.mlp
+            fused = dict(wqkv=torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), wo=a.o_proj.weight.contiguous(),
+                         wgu=ops.interleave_gate_up(m.gate_proj.weight, m.up_proj.weight), wd=m.down_proj.weight.contiguous())
+            L = dict(n1=f32(l.input_layernorm.weight), n2=f32(l.post_attention_layernorm.weight))
+            for k, w in fused.items():
+                L[k] = ops.quantize_mxfp4_rows(w)
+                largest = max(largest, w.numel())
+            layers.append(L)
+            del fused
+            if free_master:
+                for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj):
+                    lin.weight.requires_grad_(False)
+                    lin.weight.data = torch.empty(0, dtype=w0.dtype, device=w0.device)
+        self._mxfp4 = dict(key=(w0.dtype, str(w0.device)), layers=layers, norm=f32(self.norm.weight), largest=largest, scratch=None,
+                           freed=bool(free_master), versions=self._versions(self._stack_and_embed_parameters()))
+        self._packed = {}
+        return self
+
     def state_dict(self, *args, **kwargs):
+        if self._mxfp4 is not None and self._mxfp4["freed"]:
+            raise NotImplementedError("LlamaModel.state_dict: the Linear weights were released by quantize_mxfp4_(free_master=True); saving an "
+                                      "mxfp4 stack is not implemented (quantise with free_master=False to keep the masters)")
         if self._fp8 is not None and self._fp8["freed"]:
             raise NotImplementedError("LlamaModel.state_dict: the Linear weights were released by quantize_fp8_(free_master=True); saving an fp8 "
                                       "stack is not implemented (quantise with free_master=False to keep the masters)")
         return super().state_dict(*args, **kwargs)
 
     def _w(self, w):
-        """A packed operand as `linear` takes it: itself, or — fp8 storage, a (q, e) pair — dequantised into the one scratch buffer (stream order
-        makes the reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
+        """A packed operand as `linear` takes it: itself, or — fp8 storage, a (q, e) pair; mxfp4 storage, a (q, s) pair — dequantised into the one
+        scratch buffer (stream order makes the reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
         if not isinstance(w, tuple):
             return w
+        if self._mxfp4 is not None:
+            N, K = w[0].shape[0], 2 * w[0].shape[1]
+            return ops.dequantize_mxfp4_rows(w[0], w[1], out=self._fp8_scratch()[:N * K].view(N, K))
         return ops.dequantize_fp8_rows(w[0], w[1], out=self._fp8_scratch()[:w[0].numel()].view(w[0].shape))
 
     def _fp8_scratch(self):
-        f = self._fp8
+        f = self._fp8 if self._mxfp4 is None else self._mxfp4                   # (one scratch buffer, whichever storage the stack is in)
         if f["scratch"] is None:
             f["scratch"] = torch.empty(f["largest"], dtype=f["key"][0], device=self.norm.weight.device)
         return f["scratch"]
 
     def _pack(self):
         w = self.norm.weight
+        if self._mxfp4 is not None:
+            if self._mxfp4["key"] != (w.dtype, str(w.device)):
+                raise NotImplementedError(f"LlamaModel: the stack was quantised to mxfp4 as {self._mxfp4['key']} and cannot follow a move to "
+                                          f"{(w.dtype, str(w.device))}")
+            if self._versions(self._stack_and_embed_parameters()) != self._mxfp4["versions"]:
+                raise NotImplementedError("LlamaModel: a parameter of the stack was modified in place after quantize_mxfp4_ (a LoRA merge, an "
+                                          "optimiser step): the mxfp4 copy is stale and re-quantising is not implemented; quantise after the last update")
+            return self._mxfp4
         if self._fp8 is not None:
             if self._fp8["key"] != (w.dtype, str(w.device)):
                 raise NotImplementedError(f"LlamaModel: the stack was quantised to fp8 as {self._fp8['key']} and cannot follow a move to "
@@ -234,6 +302,8 @@ class LlamaModel(PackCacheMixin, nn.Module):
           adapters attached (add_lora_), the stack frozen, an    the adapted forward with a grad_fn (autograd.LlamaLoraFn): backward() delivers
           adapter or inputs_embeds requires one                  d loss / d inputs_embeds and every dA, dB
         With adapters attached the no-graph rows apply them too (the same calls, nothing kept)."""
+        if self._mxfp4 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            raise NotImplementedError("LlamaModel.forward: a stack in mxfp4 storage is inference-only (no backward pass reads the mxfp4 weights)")
         if self._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
             raise NotImplementedError("LlamaModel.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 weights)")
         if self.lora is not None and torch.is_grad_enabled() and not self.stack_requires_grad():
@@ -327,19 +397,21 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.key_mask[:, slot] = 1
         ws = cache.workspace(H)
         y = o = None
-        fp8 = self._fp8 is not None
+        mx4 = self._mxfp4 is not None
+        fp8 = self._fp8 is not None or mx4                                          # quantised storage: (q, e) pairs, or mxfp4's (q, s) pairs
+        lin8 = ops.linear_mxfp4w if mx4 else ops.linear_fp8w                        # (MXFP4W_MAX_M == FP8W_MAX_M: the same row limit)
         big = self._fp8_scratch() if fp8 and B > ops.FP8W_MAX_M else None          # more rows than the streaming kernel takes: dequantise, then `linear`
         for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = ops.linear_fp8w(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
+            qkv = lin8(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
             cache.append(li, qkv, 1, H, slot)                                       # (native or fp8: the cache's format decides these two calls)
             o = cache.attend(li, qkv, H, slot + 1, dh ** -0.5, ws, o)
-            if fp8:                                                                 # the same step on the fp8 bytes: four weight-streaming GEMMs
-                ops.linear_fp8w(o, *L["wo"], residual=x, out=x, scratch=big)
+            if fp8:                                                                 # the same step on the fp8 bytes (mxfp4 nibbles): four weight-streaming GEMMs
+                lin8(o, *L["wo"], residual=x, out=x, scratch=big)
                 y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-                g = ops.swiglu_pairs(ops.linear_fp8w(y, *L["wgu"], scratch=big))
-                ops.linear_fp8w(g, *L["wd"], residual=x, out=x, scratch=big)
+                g = ops.swiglu_pairs(lin8(y, *L["wgu"], scratch=big))
+                lin8(g, *L["wd"], residual=x, out=x, scratch=big)
                 continue
             ops.linear(o, L["wo"], residual=x, out=x)
             y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
@@ -385,19 +457,21 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.key_mask[:, len0:len0 + Tn] = am.to(torch.uint8)
         ws = cache.workspace(H, Tn, len0)
         y = o = None
-        fp8 = self._fp8 is not None
-        stream8 = fp8 and M <= ops.FP8W_MAX_M                                   # few rows: the weight-streaming GEMM on the fp8 bytes, as in decode_step
+        mx4 = self._mxfp4 is not None
+        fp8 = self._fp8 is not None or mx4
+        lin8 = ops.linear_mxfp4w if mx4 else ops.linear_fp8w
+        stream8 = fp8 and M <= ops.FP8W_MAX_M                                   # few rows: the weight-streaming GEMM on the fp8 bytes (mxfp4 nibbles), as in decode_step
         for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = ops.linear_fp8w(y, *L["wqkv"]) if stream8 else ops.linear(y, self._w(L["wqkv"]))
+            qkv = lin8(y, *L["wqkv"]) if stream8 else ops.linear(y, self._w(L["wqkv"]))
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
             cache.append(li, qkv, Tn, H, len0)
             o = cache.extend_attend(li, qkv, H, Tn, len0, dh ** -0.5, ws, o)
             if stream8:
-                ops.linear_fp8w(o, *L["wo"], residual=x, out=x)
+                lin8(o, *L["wo"], residual=x, out=x)
                 y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-                g = ops.swiglu_pairs(ops.linear_fp8w(y, *L["wgu"]))
-                ops.linear_fp8w(g, *L["wd"], residual=x, out=x)
+                g = ops.swiglu_pairs(lin8(y, *L["wgu"]))
+                lin8(g, *L["wd"], residual=x, out=x)
                 continue
             ops.linear(o, self._w(L["wo"]), residual=x, out=x)
             y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
@@ -514,6 +588,11 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         self.model.quantize_fp8_(free_master)
         return self
 
+    def quantize_mxfp4_(self, free_master: bool = True):
+        """`LlamaModel.quantize_mxfp4_`: the decoder stack's projection weights into MXFP4 storage (embed_tokens, the norms and lm_head stay)."""
+        self.model.quantize_mxfp4_(free_master)
+        return self
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, inputs_embeds=None, labels=None, comp_images=None,
                 last_token_only: bool = False, return_loss: bool = False):
         """Returns (logits, new_labels, attention_mask): logits (B, T', vocab) — or (B, vocab) for every sequence's last token with
@@ -532,6 +611,9 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         given = inputs_embeds
         with torch.set_grad_enabled(may_train):
             inputs_embeds, attention_mask, position_ids, new_labels = self._embed(input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images)
+        if self.model._mxfp4 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            raise NotImplementedError("SetokimLlamaPrefill.forward: a stack in mxfp4 storage is inference-only (no backward pass reads the mxfp4 "
+                                      "weights); run it under torch.no_grad() or detach inputs_embeds")
         if self.model._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
             raise NotImplementedError("SetokimLlamaPrefill.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 "
                                       "weights); run it under torch.no_grad() or detach inputs_embeds")

@@ -77,6 +77,9 @@ def check_request(model, r, lora_alpha, target_modules: Iterable[str], lora_drop
     """add_lora_'s refusals, each by name.  Returns the targets in canonical order."""
     if getattr(model, "lora", None) is not None:
         raise NotImplementedError("LlamaModel.add_lora_: adapters are already attached (a second set is not implemented; merge_lora_() first)")
+    if getattr(model, "_mxfp4", None) is not None:
+        raise NotImplementedError("LlamaModel.add_lora_: the stack is in mxfp4 storage (quantize_mxfp4_), which is inference-only; attach "
+                                  "adapters to the native weights")
     if model._fp8 is not None:
         raise NotImplementedError("LlamaModel.add_lora_: the stack is in fp8 storage (quantize_fp8_), which is inference-only; attach adapters "
                                   "to the native weights")

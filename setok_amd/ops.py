@@ -1035,6 +1035,75 @@ def linear_fp8w(a: Tensor, q: Tensor, e: Tensor, residual: Optional[Tensor] = No
     return out
 
 
+# ---- MXFP4 weight-only storage (csrc/gemm_mxfp4w.hip) ---------------------------------------------------------------------------------------------
+MXFP4W_MAX_M = 64                                 # rows setok_linear_mxfp4w takes; more rows dequantise and go through `linear`
+MXFP4_BLOCK = 32                                  # elements per e8m0 scale byte
+
+
+def _mxfp4_check(q: Tensor, s: Tensor) -> Tuple[int, int]:
+    N, K2 = q.shape
+    K = 2 * K2
+    assert K % MXFP4_BLOCK == 0 and q.dtype == torch.uint8 and s.dtype == torch.uint8 and s.shape == (N, K // MXFP4_BLOCK), \
+        "q (N, K/2) uint8 and s (N, K/32) uint8 with K % 32 == 0 required"
+    return N, K
+
+
+def quantize_mxfp4_rows(w: Tensor, q: Optional[Tensor] = None, s: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """w (N, K) fp32 / bf16 / fp16, K % 32 == 0 -> (q (N, K/2) uint8 of e2m1 nibble pairs, s (N, K/32) uint8 of e8m0 scale bytes) with
+    w' = value(nibble) * 2^(s - 127) per block of 32 elements of a row (include/setok_hip.h, "MXFP4 weight-only decode")."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK != 0:
+        raise ValueError(f"quantize_mxfp4_rows: K={K} is not a multiple of {MXFP4_BLOCK}, the MX block")
+    if q is None:
+        q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    if s is None:
+        s = torch.empty((N, K // MXFP4_BLOCK), dtype=torch.uint8, device=w.device)
+    assert _mxfp4_check(q, s) == (N, K)
+    _lib.call("setok_quantize_mxfp4_rows", _stream(), _code(w.dtype), w.data_ptr(), _rows_ld(w), q.data_ptr(), _rows_ld(q), s.data_ptr(), _rows_ld(s), N, K)
+    return q, s
+
+
+def dequantize_mxfp4_rows(q: Tensor, s: Tensor, dtype: Optional[torch.dtype] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The exact inverse of quantize_mxfp4_rows into `dtype` (or into `out`, whose rows may be wider than K)."""
+    N, K = _mxfp4_check(q, s)
+    if out is None:
+        out = torch.empty((N, K), dtype=dtype, device=q.device)
+    assert out.shape == (N, K) and (dtype is None or out.dtype == dtype)
+    _lib.call("setok_dequantize_mxfp4_rows", _stream(), _code(out.dtype), q.data_ptr(), _rows_ld(q), s.data_ptr(), _rows_ld(s), out.data_ptr(),
+              _rows_ld(out), N, K)
+    return out
+
+
+def linear_mxfp4w(a: Tensor, q: Tensor, s: Tensor, residual: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                  scratch: Optional[Tensor] = None, min_wgs: Optional[int] = None) -> Tensor:
+    """out = a @ w'.T + residual with w' = value(nibble) * 2^(s - 127);  a: (M, K), q: (N, K/2) uint8, s: (N, K/32) uint8.  M <= 64 is ONE launch of
+    the weight-streaming kernel (every operand may be a column window of a wider buffer).  More rows dequantise w' into `scratch` — the caller's,
+    at least N * K elements of a.dtype — and run the existing `linear` on it: the same function, `linear`'s summation order.
+    `min_wgs` replaces the floor of the kernel's band rule (setok_linear_mxfp4w_wgs; None: the library's own, one workgroup per CU): it moves
+    columns between workgroups and changes no bit."""
+    M, Ka = a.shape
+    N, K = _mxfp4_check(q, s)
+    assert K == Ka
+    if M > MXFP4W_MAX_M:
+        if scratch is None or scratch.dtype != a.dtype or scratch.numel() < N * K:
+            raise ValueError(f"linear_mxfp4w: M={M} > {MXFP4W_MAX_M} dequantises the weight: pass `scratch`, {N * K} elements of {a.dtype}")
+        w = dequantize_mxfp4_rows(q, s, out=scratch.reshape(-1)[:N * K].view(N, K))
+        return linear(a, w, residual=residual, out=out)
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    assert out.shape == (M, N) and out.dtype == a.dtype
+    ldc = _rows_ld(out)
+    if residual is not None:
+        assert residual.shape == (M, N) and residual.dtype == a.dtype and (M == 1 or _rows_ld(residual) == ldc), "residual shares out's row stride"
+    args = (_stream(), _code(a.dtype), a.data_ptr(), _rows_ld(a), q.data_ptr(), _rows_ld(q), s.data_ptr(), _rows_ld(s),
+            None if residual is None else residual.data_ptr(), out.data_ptr(), ldc, M, N, K)
+    if min_wgs is None:
+        _lib.call("setok_linear_mxfp4w", *args)
+    else:
+        _lib.call("setok_linear_mxfp4w_wgs", *args, int(min_wgs))
+    return out
+
+
 # ---- the DiffLoss image head (csrc/diffusion.hip) ---------------------------------------------------------------------------------------------
 def timestep_embedding(t: Tensor, dim: int, dtype: torch.dtype, max_period: float = 10000.0, out: Optional[Tensor] = None) -> Tensor:
     """[cos(t f_j) | sin(t f_j)], f_j = exp(-ln(max_period) j / (dim / 2)): t fp32 (rows,) on the device -> (rows, dim) in `dtype`."""

@@ -4,8 +4,8 @@ to produce token n + 1 before: the whole prefill again over the sequence grown b
     python tools/bench_generate.py [--layers 32] [--batches 32,8,1] [--prompt 552] [--new 200] [--reps 5]
     python tools/bench_generate.py --steps-only 3 [--batch 32]          # prefill-free: a few decode steps and nothing else (what a kernel trace is pointed at)
     python tools/bench_generate.py --attention-only [--gqa 4]           # the decode-attention launch pair alone (what a counter run is pointed at)
-    python tools/bench_generate.py --weights fp8 ...                    # any of the above with the stack in fp8 storage (quantize_fp8_)
-    python tools/bench_generate.py --compare-weights [--rounds 3]       # native and fp8 arms alternated in one process: decode step + the four GEMMs
+    python tools/bench_generate.py --weights fp8 ...                    # any of the above with the stack in fp8 storage (quantize_fp8_); mxfp4: quantize_mxfp4_
+    python tools/bench_generate.py --compare-weights [--rounds 3]       # native, fp8 and mxfp4 arms alternated in one process: decode step + the four GEMMs
     python tools/bench_generate.py --compare-bands [--rounds 3]         # linear_fp8w's 16 / 32 / 64-column bands alternated in one process, four GEMMs
     python tools/bench_generate.py --compare-kv [--attention-only]      # native and fp8 KV caches alternated in one process: the decode step, or the attention pair alone
 
@@ -96,16 +96,21 @@ def _spread(xs):
 
 
 def _compare_weights(a, g, dev, dt, rnd):
-    """Both arms in ONE process, alternated round by round after a warm-up, every timing ended by a device synchronise: the decode step of a
-    native and of an fp8-quantised stack (two models with the same weights up to the rounding) at the prompt length, and `linear_fp8w` against
-    `linear` on the dequantised weight at the four layer shapes.  Every arm runs `--rounds` times: min / median / max are reported."""
+    """Three arms in ONE process, alternated round by round after a warm-up, every timing ended by a device synchronise: the decode step of a
+    native, an fp8-quantised and an mxfp4-quantised stack (three models with the same weights up to the rounding) at the prompt length, and
+    `linear_mxfp4w` against `linear_fp8w` against `linear` on the fp8-dequantised weight at the four layer shapes.  Every arm runs `--rounds`
+    times: min / median / max are reported, and the run is appended to `--weights-out`."""
     from setok_amd import ops
     T, N = a.prompt, a.new
     native = _llm(a.layers, g, dev, dt)
     fp8 = _llm(a.layers, g, dev, dt)
     fp8.load_state_dict(native.state_dict())
     fp8.quantize_fp8_()
-    arms = (("native", native), ("fp8", fp8))
+    mx4 = _llm(a.layers, g, dev, dt)
+    mx4.load_state_dict(native.state_dict())
+    mx4.quantize_mxfp4_()
+    arms = (("native", native), ("fp8", fp8), ("mxfp4", mx4))
+    ahead = lambda r, x, y: r[x]["max"] < r[y]["min"]                      # x faster than y by more than the spread of both arms
     step = {}
     for B in [int(b) for b in a.batches.split(",")]:
         caches = {k: _filled_cache(m, B, T + N, T, g) for k, m in arms}
@@ -121,38 +126,58 @@ def _compare_weights(a, g, dev, dt, rnd):
                 runs[k].append(_time(lambda: one(k, m), a.reps))
         r = {k: _spread(v) for k, v in runs.items()}
         r["fp8_over_native_median"] = round(r["fp8"]["median"] / r["native"]["median"], 3)
-        r["faster_by_more_than_the_spread"] = r["fp8"]["max"] < r["native"]["min"]
+        r["faster_by_more_than_the_spread"] = ahead(r, "fp8", "native")
+        r["mxfp4_over_native_median"] = round(r["mxfp4"]["median"] / r["native"]["median"], 3)
+        r["mxfp4_over_fp8_median"] = round(r["mxfp4"]["median"] / r["fp8"]["median"], 3)
+        r["mxfp4_faster_than_fp8_by_more_than_the_spread"] = ahead(r, "mxfp4", "fp8")
         step[f"B{B}"] = r
         del caches
-    del native, fp8
+    del native, fp8, mx4
     torch.cuda.empty_cache()
     kern = {}
     for Nn, K in LAYER_SHAPES:
-        # as many copies of each operand as hold 1.2 GB of q (23 to 71 at the layer shapes), visited round robin: the weights come from HBM, as
-        # the 32 layers of a step do
+        # as many copies of each operand as hold 1.2 GB of fp8 q (23 to 71 at the layer shapes; 0.6 GB of nibbles), visited round robin: the
+        # weights come from HBM, as the 32 layers of a step do
         copies = max(2, int(1.2e9 // (Nn * K)))
         w = [(torch.randn(Nn, K, generator=g, device=dev, dtype=torch.float32) * 0.02).to(dt) for _ in range(copies)]
         qe = [ops.quantize_fp8_rows(x) for x in w]
+        qs = [ops.quantize_mxfp4_rows(x) for x in w]
         w = [ops.dequantize_fp8_rows(q, e, dtype=dt) for q, e in qe]
         for M in (1, 8, 32, 64):
             x = rnd(M, K)
             out = torch.empty(M, Nn, dtype=dt, device=dev)
-            f_native = lambda: [ops.linear(x, wi, out=out) for wi in w]
-            f_fp8 = lambda: [ops.linear_fp8w(x, q, e, out=out) for q, e in qe]
-            runs = {"native": [], "fp8": []}
+            fns = dict(native=lambda: [ops.linear(x, wi, out=out) for wi in w],
+                       fp8=lambda: [ops.linear_fp8w(x, q, e, out=out) for q, e in qe],
+                       mxfp4=lambda: [ops.linear_mxfp4w(x, q, s, out=out) for q, s in qs])
+            runs = {k: [] for k in fns}
             for _ in range(a.rounds):
-                runs["native"].append(_time(f_native, a.reps) / copies)
-                runs["fp8"].append(_time(f_fp8, a.reps) / copies)
+                for k, fn in fns.items():
+                    runs[k].append(_time(fn, a.reps) / copies)
             r = {k: _spread(v) for k, v in runs.items()}
             r["fp8_q_tb_per_s"] = round(Nn * K / (r["fp8"]["median"] * 1e-3) / 1e12, 3)
             r["native_w_tb_per_s"] = round(2 * Nn * K / (r["native"]["median"] * 1e-3) / 1e12, 3)
+            r["mxfp4_qs_tb_per_s"] = round((Nn * K / 2 + Nn * K / 32) / (r["mxfp4"]["median"] * 1e-3) / 1e12, 3)
+            r["mxfp4_over_fp8_median"] = round(r["mxfp4"]["median"] / r["fp8"]["median"], 3)
+            r["mxfp4_over_native_median"] = round(r["mxfp4"]["median"] / r["native"]["median"], 3)
+            r["mxfp4_faster_than_fp8_by_more_than_the_spread"] = ahead(r, "mxfp4", "fp8")
             kern[f"N{Nn}_K{K}_M{M}"] = r
-        del w, qe
-    print(json.dumps(dict(
-        workload="cfg5 LLM decode step, Llama at Vicuna-7B dims, bf16: the stack's projection weights native (bf16) against fp8 e4m3 storage; "
-                 "ms per decode step at cache length = prompt, and ms per GEMM call at the four layer shapes (operands cycled through >= 1.2 GB)",
+        del w, qe, qs
+    run = dict(
+        workload="cfg5 LLM decode step, Llama at Vicuna-7B dims, bf16: the stack's projection weights native (bf16) against fp8 e4m3 storage against "
+                 "MXFP4 (e2m1 nibbles + one e8m0 scale per 32); ms per decode step at cache length = prompt, and ms per GEMM call at the four layer "
+                 "shapes (operands cycled through >= 1.2 GB of fp8 bytes)",
         layers=a.layers, prompt=T, reps=a.reps, rounds=a.rounds, device=torch.cuda.get_device_name(0), decode_step_ms=step, gemm_ms=kern,
-        peak_bytes=torch.cuda.max_memory_allocated())))
+        peak_bytes=torch.cuda.max_memory_allocated())
+    runs = []
+    if os.path.isfile(a.weights_out):
+        with open(a.weights_out) as f:
+            runs = json.load(f)
+    runs.append(run)
+    os.makedirs(os.path.dirname(os.path.abspath(a.weights_out)), exist_ok=True)
+    with open(a.weights_out, "w") as f:
+        json.dump(runs, f, indent=1)
+        f.write("\n")
+    print(json.dumps(run))
 
 
 def _fp8_twin(c):
@@ -283,12 +308,14 @@ def main():
     ap.add_argument("--steps-only", type=int, default=0)
     ap.add_argument("--attention-only", action="store_true")
     ap.add_argument("--gqa", type=int, default=4)
-    ap.add_argument("--weights", choices=("native", "fp8"), default="native")
+    ap.add_argument("--weights", choices=("native", "fp8", "mxfp4"), default="native")
     ap.add_argument("--compare-weights", action="store_true")
     ap.add_argument("--compare-bands", action="store_true")
     ap.add_argument("--compare-kv", action="store_true")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "generate_fp8kv_bench.json"),
                     help="--compare-kv appends its run to this JSON list")
+    ap.add_argument("--weights-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "generate_mxfp4_bench.json"),
+                    help="--compare-weights appends its run to this JSON list")
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     from setok_amd import ops
@@ -322,6 +349,8 @@ def main():
     llm = _llm(a.layers, g, dev, dt)
     if a.weights == "fp8":
         llm.quantize_fp8_()
+    elif a.weights == "mxfp4":
+        llm.quantize_mxfp4_()
     w_lm, w_e = llm.lm_head.weight.detach(), llm.model.embed_tokens.weight.detach()
 
     def token_step(c, h):
