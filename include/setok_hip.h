@@ -643,7 +643,7 @@ int setok_spec_accept(void* stream, const int64_t* draft, const int64_t* sel, in
 int setok_ngram_propose(void* stream, int64_t* hist, int32_t* hist_len, int B, int cap_h, int len_max, const int64_t* emitted, const int32_t* m,
                         int n_emit, int K, int max_ngram, int min_ngram, int64_t* out);
 
-/* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip): the decode step streams every projection weight once per token, so the stack's Linear
+/* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip; the M <= 64 GEMM it shares with MXFP4: csrc/wstream.h): the decode step streams every projection weight once per token, so the stack's Linear
  * weights may be STORED as OCP e4m3fn bytes with one power-of-two scale per output row.  A matrix W (N, K) becomes q (N, K) uint8 + e (N,) int8 and
  * means exactly
  *     W'[n, k] = value_e4m3fn(q[n, k]) * 2^e[n],      e[n] in [-15, 7].
@@ -685,7 +685,7 @@ int setok_linear_fp8w(void* stream, int dtype, const void* A, int64_t lda, const
 int setok_linear_fp8w_wgs(void* stream, int dtype, const void* A, int64_t lda, const uint8_t* q, int64_t ldq, const int8_t* e,
                           const void* residual, void* C, int64_t ldc, int M, int N, int K, int min_wgs);
 
-/* ---- MXFP4 weight-only decode (csrc/gemm_mxfp4w.hip): the same idea at half the bytes again, in the OCP Microscaling format gfx950 converts in
+/* ---- MXFP4 weight-only decode (csrc/gemm_mxfp4w.hip; the M <= 64 GEMM it shares with fp8: csrc/wstream.h): the same idea at half the bytes again, in the OCP Microscaling format gfx950 converts in
  * hardware.  A matrix W (N, K), K % 32 == 0, is stored in two arrays:
  *     q (N, K/2) uint8     byte j of a row holds element 2j in its low nibble and element 2j+1 in its high nibble (torch's float4_e2m1fn_x2 order)
  *     s (N, K/32) uint8    e8m0 scale bytes, plain row-major: block b of a row covers k in [32 b, 32 b + 32)

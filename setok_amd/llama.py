@@ -28,7 +28,7 @@ into the weights, and the KV-cached entry points refuse unmerged adapters (DESIG
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Optional
+from typing import Any, Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -37,6 +37,25 @@ from . import autograd, lora, ops
 from ._packcache import PackCacheMixin
 from .arch import SetokimVisionMixin, config_get
 from .lora import ALL_SEVEN
+
+
+class _WeightFormat(NamedTuple):
+    """A quantised storage format of the decoder stack: what `LlamaModel` needs to know of it (the kernels: csrc/wstream.h and the format's file)."""
+    weight_format: str                                   # LlamaModel.weight_format
+    tag: str                                             # the short name in messages and in quantize_<tag>_
+    quantize: Callable                                   # w (N, K) -> the stored pair
+    dequantize: Callable                                 # (*pair, out=) -> w' (N, K)
+    linear: Callable                                     # the weight-streaming GEMM on a pair ...
+    max_m: int                                           # ... and the rows it takes; more dequantise and go through ops.linear
+    shape: Callable                                      # pair -> (N, K)
+    k_granule: Optional[Callable] = None                 # dtype -> the in_features granule quantize_ insists on (None: any K)
+
+
+_FP8 = _WeightFormat("fp8_e4m3", "fp8", ops.quantize_fp8_rows, ops.dequantize_fp8_rows, ops.linear_fp8w, ops.FP8W_MAX_M,
+                     shape=lambda pair: tuple(pair[0].shape))                  # (no granule: the prefill works at any K through the dequantise path)
+_MXFP4 = _WeightFormat("mxfp4_e2m1", "mxfp4", ops.quantize_mxfp4_rows, ops.dequantize_mxfp4_rows, ops.linear_mxfp4w, ops.MXFP4W_MAX_M,
+                       shape=lambda pair: (pair[0].shape[0], 2 * pair[0].shape[1]),
+                       k_granule=lambda dtype: 32 if dtype == torch.float32 else 128)
 
 
 class _RMSNorm(nn.Module):
@@ -88,8 +107,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
                                      for _ in range(num_hidden_layers)])
         self.norm = _RMSNorm(hidden_size, rms_norm_eps)
         self._init_pack_cache()
-        self._fp8 = None                                                        # quantize_fp8_(): the packed stack in fp8 storage
-        self._mxfp4 = None                                                      # quantize_mxfp4_(): the packed stack in MXFP4 storage (never both)
+        self._quant = None                                                      # quantize_fp8_() / quantize_mxfp4_(): the packed stack in that storage, with its _WeightFormat
         self.lora = None                                                        # add_lora_(): a lora.LoraAdapters, outside self.layers
 
     # ---- LoRA adapters (lora.py; the arithmetic is llama_train.llama_lora_forward_train / llama_lora_backward) ---------------------------------
@@ -140,9 +158,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
     @property
     def weight_format(self) -> str:
         """"native" (the Linear weights in the model's element type), "fp8_e4m3" after quantize_fp8_() or "mxfp4_e2m1" after quantize_mxfp4_()."""
-        if self._mxfp4 is not None:
-            return "mxfp4_e2m1"
-        return "native" if self._fp8 is None else "fp8_e4m3"
+        return "native" if self._quant is None else self._quant["fmt"].weight_format
 
     @torch.no_grad()
     def quantize_fp8_(self, free_master: bool = True):
@@ -154,34 +170,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         `decode_step` streams the bytes through `ops.linear_fp8w`.  With `free_master` the Linear parameters release their storage (N * K + N
         bytes per matrix remain) and `state_dict()` is refused; without it the masters stay for `state_dict()` only — the fp8 copy computes, and an
         in-place update of any stack parameter afterwards is refused at the next forward instead of being silently ignored.  Call it on the device and in the dtype the model will run in.  Inference only."""
-        self._refuse_unmerged("LlamaModel.quantize_fp8_")
-        if self._mxfp4 is not None:
-            raise NotImplementedError("LlamaModel.quantize_fp8_: the stack is already in mxfp4 storage (a second quantisation would re-round it)")
-        if self._fp8 is not None:
-            raise NotImplementedError("LlamaModel.quantize_fp8_: the stack is already in fp8 storage (a second quantisation would re-round it)")
-        f32 = lambda t: t.detach().float().contiguous()
-        w0 = self.norm.weight
-        if not w0.is_cuda:
-            raise NotImplementedError("LlamaModel.quantize_fp8_: the fp8 quantiser runs on the device; move the model there first")
-        layers, largest = [], 0
-        for l in self.layers:
-            a, m = l.self_attn, l.mlp
-            fused = dict(wqkv=torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), wo=a.o_proj.weight.contiguous(),
-                         wgu=ops.interleave_gate_up(m.gate_proj.weight, m.up_proj.weight), wd=m.down_proj.weight.contiguous())
-            L = dict(n1=f32(l.input_layernorm.weight), n2=f32(l.post_attention_layernorm.weight))
-            for k, w in fused.items():
-                L[k] = ops.quantize_fp8_rows(w)
-                largest = max(largest, w.numel())
-            layers.append(L)
-            del fused
-            if free_master:
-                for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj):
-                    lin.weight.requires_grad_(False)
-                    lin.weight.data = torch.empty(0, dtype=w0.dtype, device=w0.device)
-        self._fp8 = dict(key=(w0.dtype, str(w0.device)), layers=layers, norm=f32(self.norm.weight), largest=largest, scratch=None,
-                         freed=bool(free_master), versions=self._versions(self._stack_and_embed_parameters()))
-        self._packed = {}
-        return self
+        return self._quantize_(_FP8, free_master)
 
     @torch.no_grad()
     def quantize_mxfp4_(self, free_master: bool = True):
@@ -193,25 +182,29 @@ class LlamaModel(PackCacheMixin, nn.Module):
         `ops.linear_mxfp4w` up to 64 rows.  With `free_master` the Linear parameters release their storage (N * K / 2 + N * K / 32 bytes per matrix
         remain) and `state_dict()` is refused.  Refused before anything is freed: a hidden or intermediate size off the streaming GEMM's K granule
         (128 in the 16-bit types, 32 in fp32; ValueError naming the matrix), a stack already quantised, unmerged adapters.  Inference only."""
-        self._refuse_unmerged("LlamaModel.quantize_mxfp4_")
-        if self._mxfp4 is not None:
-            raise NotImplementedError("LlamaModel.quantize_mxfp4_: the stack is already in mxfp4 storage (a second quantisation would re-round it)")
-        if self._fp8 is not None:
-            raise NotImplementedError("LlamaModel.quantize_mxfp4_: the stack is already in fp8 storage and its masters may be gone; mxfp4 "
-                                      "quantises the native weights")
+        return self._quantize_(_MXFP4, free_master)
+
+    def _quantize_(self, fmt: _WeightFormat, free_master: bool):
+        what = f"LlamaModel.quantize_{fmt.tag}_"
+        self._refuse_unmerged(what)
+        if self._quant is not None:
+            raise NotImplementedError(f"{what}: the stack is already in {self._quant['fmt'].tag} storage and its masters may be gone (a second "
+                                      "quantisation would re-round it)")
         f32 = lambda t: t.detach().float().contiguous()
         w0 = self.norm.weight
-        gran = 32 if w0.dtype == torch.float32 else 128
-        for li, l in enumerate(self.layers):
-            a, m = l.self_attn, l.mlp
-            for name, lin in (("self_attn.q_proj", a.q_proj), ("self_attn.k_proj", a.k_proj), ("self_attn.v_proj", a.v_proj),
-                              ("self_attn.o_proj", a.o_proj), ("mlp.gate_proj", m.gate_proj), ("mlp.up_proj", m.up_proj), ("mlp.down_proj", m.down_proj)):
-                K = lin.weight.shape[1]
-                if K % gran != 0:
-                    raise ValueError(f"LlamaModel.quantize_mxfp4_: layers.{li}.{name} has in_features={K}, not a multiple of {gran} (the K granule of "
-                                     f"the mxfp4 streaming GEMM in {w0.dtype}); nothing was quantised")
+        lins = lambda l: (("self_attn.q_proj", l.self_attn.q_proj), ("self_attn.k_proj", l.self_attn.k_proj), ("self_attn.v_proj", l.self_attn.v_proj),
+                          ("self_attn.o_proj", l.self_attn.o_proj), ("mlp.gate_proj", l.mlp.gate_proj), ("mlp.up_proj", l.mlp.up_proj),
+                          ("mlp.down_proj", l.mlp.down_proj))
+        if fmt.k_granule is not None:
+            gran = fmt.k_granule(w0.dtype)
+            for li, l in enumerate(self.layers):
+                for name, lin in lins(l):
+                    K = lin.weight.shape[1]
+                    if K % gran != 0:
+                        raise ValueError(f"{what}: layers.{li}.{name} has in_features={K}, not a multiple of {gran} (the K granule of the {fmt.tag} "
+                                         f"streaming GEMM in {w0.dtype}); nothing was quantised")
         if not w0.is_cuda:
-            raise NotImplementedError("LlamaModel.quantize_mxfp4_: the mxfp4 quantiser runs on the device; move the model there first")
+            raise NotImplementedError(f"{what}: the {fmt.tag} quantiser runs on the device; move the model there first")
         layers, largest = [], 0
         for l in self.layers:
             a, m = l.self_attn, l.mlp
@@ -219,63 +212,54 @@ class LlamaModel(PackCacheMixin, nn.Module):
                          wgu=ops.interleave_gate_up(m.gate_proj.weight, m.up_proj.weight), wd=m.down_proj.weight.contiguous())
             L = dict(n1=f32(l.input_layernorm.weight), n2=f32(l.post_attention_layernorm.weight))
             for k, w in fused.items():
-                L[k] = ops.quantize_mxfp4_rows(w)
+                L[k] = fmt.quantize(w)
                 largest = max(largest, w.numel())
             layers.append(L)
             del fused
             if free_master:
-                for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj):
+                for _, lin in lins(l):
                     lin.weight.requires_grad_(False)
                     lin.weight.data = torch.empty(0, dtype=w0.dtype, device=w0.device)
-        self._mxfp4 = dict(key=(w0.dtype, str(w0.device)), layers=layers, norm=f32(self.norm.weight), largest=largest, scratch=None,
+        self._quant = dict(fmt=fmt, key=(w0.dtype, str(w0.device)), layers=layers, norm=f32(self.norm.weight), largest=largest, scratch=None,
                            freed=bool(free_master), versions=self._versions(self._stack_and_embed_parameters()))
         self._packed = {}
         return self
 
     def state_dict(self, *args, **kwargs):
-        if self._mxfp4 is not None and self._mxfp4["freed"]:
-            raise NotImplementedError("LlamaModel.state_dict: the Linear weights were released by quantize_mxfp4_(free_master=True); saving an "
-                                      "mxfp4 stack is not implemented (quantise with free_master=False to keep the masters)")
-        if self._fp8 is not None and self._fp8["freed"]:
-            raise NotImplementedError("LlamaModel.state_dict: the Linear weights were released by quantize_fp8_(free_master=True); saving an fp8 "
-                                      "stack is not implemented (quantise with free_master=False to keep the masters)")
+        if self._quant is not None and self._quant["freed"]:
+            tag = self._quant["fmt"].tag
+            raise NotImplementedError(f"LlamaModel.state_dict: the Linear weights were released by quantize_{tag}_(free_master=True); saving "
+                                      f"a stack in {tag} storage is not implemented (quantise with free_master=False to keep the masters)")
         return super().state_dict(*args, **kwargs)
 
     def _w(self, w):
-        """A packed operand as `linear` takes it: itself, or — fp8 storage, a (q, e) pair; mxfp4 storage, a (q, s) pair — dequantised into the one
-        scratch buffer (stream order makes the reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
+        """A packed operand as `linear` takes it: itself, or — quantised storage, a (q, e) or (q, s) pair — dequantised into the one scratch
+        buffer (stream order makes the reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
         if not isinstance(w, tuple):
             return w
-        if self._mxfp4 is not None:
-            N, K = w[0].shape[0], 2 * w[0].shape[1]
-            return ops.dequantize_mxfp4_rows(w[0], w[1], out=self._fp8_scratch()[:N * K].view(N, K))
-        return ops.dequantize_fp8_rows(w[0], w[1], out=self._fp8_scratch()[:w[0].numel()].view(w[0].shape))
+        fmt = self._quant["fmt"]
+        N, K = fmt.shape(w)
+        return fmt.dequantize(*w, out=self._dequant_scratch()[:N * K].view(N, K))
 
-    def _fp8_scratch(self):
-        f = self._fp8 if self._mxfp4 is None else self._mxfp4                   # (one scratch buffer, whichever storage the stack is in)
+    def _dequant_scratch(self):
+        f = self._quant
         if f["scratch"] is None:
             f["scratch"] = torch.empty(f["largest"], dtype=f["key"][0], device=self.norm.weight.device)
         return f["scratch"]
 
     def _pack(self):
         w = self.norm.weight
-        if self._mxfp4 is not None:
-            if self._mxfp4["key"] != (w.dtype, str(w.device)):
-                raise NotImplementedError(f"LlamaModel: the stack was quantised to mxfp4 as {self._mxfp4['key']} and cannot follow a move to "
+        if self._quant is not None:
+            tag = self._quant["fmt"].tag
+            if self._quant["key"] != (w.dtype, str(w.device)):
+                raise NotImplementedError(f"LlamaModel: the stack was quantised to {tag} as {self._quant['key']} and cannot follow a move to "
                                           f"{(w.dtype, str(w.device))}")
-            if self._versions(self._stack_and_embed_parameters()) != self._mxfp4["versions"]:
-                raise NotImplementedError("LlamaModel: a parameter of the stack was modified in place after quantize_mxfp4_ (a LoRA merge, an "
-                                          "optimiser step): the mxfp4 copy is stale and re-quantising is not implemented; quantise after the last update")
-            return self._mxfp4
-        if self._fp8 is not None:
-            if self._fp8["key"] != (w.dtype, str(w.device)):
-                raise NotImplementedError(f"LlamaModel: the stack was quantised to fp8 as {self._fp8['key']} and cannot follow a move to "
-                                          f"{(w.dtype, str(w.device))}")
-            if self._versions(self._stack_and_embed_parameters()) != self._fp8["versions"]:
-                # (free_master=False keeps the masters for state_dict(); the fp8 copy is what computes, and it cannot follow them)
-                raise NotImplementedError("LlamaModel: a parameter of the stack was modified in place after quantize_fp8_ (a LoRA merge, an optimiser "
-                                          "step): the fp8 copy is stale and re-quantising is not implemented; quantise after the last update")
-            return self._fp8
+            if self._versions(self._stack_and_embed_parameters()) != self._quant["versions"]:
+                # (free_master=False keeps the masters for state_dict(); the quantised copy is what computes, and it cannot follow them)
+                raise NotImplementedError(f"LlamaModel: a parameter of the stack was modified in place after quantize_{tag}_ (a LoRA merge, an "
+                                          f"optimiser step): the {tag} copy is stale and re-quantising is not implemented; quantise after the last "
+                                          "update")
+            return self._quant
         key = (w.dtype, str(w.device), self._versions(self._stack_and_embed_parameters()))      # every tensor: a LoRA merge into q_proj / v_proj alone must rebuild the fused copies
         if self._packed.get("key") == key:
             return self._packed
@@ -302,10 +286,9 @@ class LlamaModel(PackCacheMixin, nn.Module):
           adapters attached (add_lora_), the stack frozen, an    the adapted forward with a grad_fn (autograd.LlamaLoraFn): backward() delivers
           adapter or inputs_embeds requires one                  d loss / d inputs_embeds and every dA, dB
         With adapters attached the no-graph rows apply them too (the same calls, nothing kept)."""
-        if self._mxfp4 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
-            raise NotImplementedError("LlamaModel.forward: a stack in mxfp4 storage is inference-only (no backward pass reads the mxfp4 weights)")
-        if self._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
-            raise NotImplementedError("LlamaModel.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 weights)")
+        if self._quant is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            tag = self._quant["fmt"].tag
+            raise NotImplementedError(f"LlamaModel.forward: a stack in {tag} storage is inference-only (no backward pass reads the {tag} weights)")
         if self.lora is not None and torch.is_grad_enabled() and not self.stack_requires_grad():
             # adapters attached, the stack frozen, an adapter or inputs_embeds requires a gradient: d / d inputs_embeds and every dA, dB
             names, params = self.lora.flat()
@@ -397,10 +380,10 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.key_mask[:, slot] = 1
         ws = cache.workspace(H)
         y = o = None
-        mx4 = self._mxfp4 is not None
-        fp8 = self._fp8 is not None or mx4                                          # quantised storage: (q, e) pairs, or mxfp4's (q, s) pairs
-        lin8 = ops.linear_mxfp4w if mx4 else ops.linear_fp8w                        # (MXFP4W_MAX_M == FP8W_MAX_M: the same row limit)
-        big = self._fp8_scratch() if fp8 and B > ops.FP8W_MAX_M else None          # more rows than the streaming kernel takes: dequantise, then `linear`
+        fmt = None if self._quant is None else self._quant["fmt"]                   # quantised storage: (q, e) pairs, or mxfp4's (q, s) pairs
+        fp8 = fmt is not None
+        lin8 = fmt.linear if fp8 else None
+        big = self._dequant_scratch() if fp8 and B > fmt.max_m else None            # more rows than the streaming kernel takes: dequantise, then `linear`
         for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
             qkv = lin8(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
@@ -457,10 +440,9 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.key_mask[:, len0:len0 + Tn] = am.to(torch.uint8)
         ws = cache.workspace(H, Tn, len0)
         y = o = None
-        mx4 = self._mxfp4 is not None
-        fp8 = self._fp8 is not None or mx4
-        lin8 = ops.linear_mxfp4w if mx4 else ops.linear_fp8w
-        stream8 = fp8 and M <= ops.FP8W_MAX_M                                   # few rows: the weight-streaming GEMM on the fp8 bytes (mxfp4 nibbles), as in decode_step
+        fmt = None if self._quant is None else self._quant["fmt"]
+        lin8 = fmt.linear if fmt is not None else None
+        stream8 = fmt is not None and M <= fmt.max_m                            # few rows: the weight-streaming GEMM on the fp8 bytes (mxfp4 nibbles), as in decode_step
         for li, L in enumerate(pk["layers"]):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
             qkv = lin8(y, *L["wqkv"]) if stream8 else ops.linear(y, self._w(L["wqkv"]))
@@ -611,11 +593,9 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         given = inputs_embeds
         with torch.set_grad_enabled(may_train):
             inputs_embeds, attention_mask, position_ids, new_labels = self._embed(input_ids, attention_mask, position_ids, inputs_embeds, labels, comp_images)
-        if self.model._mxfp4 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
-            raise NotImplementedError("SetokimLlamaPrefill.forward: a stack in mxfp4 storage is inference-only (no backward pass reads the mxfp4 "
-                                      "weights); run it under torch.no_grad() or detach inputs_embeds")
-        if self.model._fp8 is not None and torch.is_grad_enabled() and inputs_embeds.requires_grad:
-            raise NotImplementedError("SetokimLlamaPrefill.forward: a stack in fp8 storage is inference-only (no backward pass reads the fp8 "
+        if self.model.weight_format != "native" and torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            tag = self.model._quant["fmt"].tag
+            raise NotImplementedError(f"SetokimLlamaPrefill.forward: a stack in {tag} storage is inference-only (no backward pass reads the {tag} "
                                       "weights); run it under torch.no_grad() or detach inputs_embeds")
         adapters = self.model.lora.flat()[1] if self.model.lora is not None else []
         if may_train and (inputs_embeds.requires_grad or any(p.requires_grad for p in adapters)):

@@ -77,12 +77,10 @@ def check_request(model, r, lora_alpha, target_modules: Iterable[str], lora_drop
     """add_lora_'s refusals, each by name.  Returns the targets in canonical order."""
     if getattr(model, "lora", None) is not None:
         raise NotImplementedError("LlamaModel.add_lora_: adapters are already attached (a second set is not implemented; merge_lora_() first)")
-    if getattr(model, "_mxfp4", None) is not None:
-        raise NotImplementedError("LlamaModel.add_lora_: the stack is in mxfp4 storage (quantize_mxfp4_), which is inference-only; attach "
+    if model.weight_format != "native":
+        tag = model.weight_format.split("_")[0]                                     # "fp8_e4m3" -> "fp8", "mxfp4_e2m1" -> "mxfp4"
+        raise NotImplementedError(f"LlamaModel.add_lora_: the stack is in {tag} storage (quantize_{tag}_), which is inference-only; attach "
                                   "adapters to the native weights")
-    if model._fp8 is not None:
-        raise NotImplementedError("LlamaModel.add_lora_: the stack is in fp8 storage (quantize_fp8_), which is inference-only; attach adapters "
-                                  "to the native weights")
     targets = tuple(target_modules)
     unknown = [t for t in targets if t not in ALL_SEVEN]
     if unknown or not targets:

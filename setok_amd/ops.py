@@ -972,7 +972,7 @@ def ngram_propose(hist: Tensor, hist_len: Tensor, K: int, len_max: int, emitted:
     return out
 
 
-# ---- fp8 weight-only storage (csrc/gemm_fp8w.hip) -----------------------------------------------------------------------------------------------
+# ---- fp8 weight-only storage (csrc/gemm_fp8w.hip; the M <= 64 GEMM it shares with MXFP4: csrc/wstream.h, here _linear_wstream) -----------------
 FP8W_MAX_M = 64                                   # rows setok_linear_fp8w takes; more rows dequantise and go through `linear`
 
 
@@ -980,6 +980,33 @@ def _rows_ld(t: Tensor) -> int:
     """Row stride of a 2-d tensor whose rows are dense (a column window of a wider buffer is fine)."""
     assert t.dim() == 2 and t.is_cuda and (t.stride(1) == 1 or t.shape[1] == 1), "2-d device tensor with dense rows required"
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _linear_wstream(sym: str, max_m: int, dequantize, a: Tensor, q: Tensor, scale_args: tuple, pair: tuple, N: int, K: int,
+                    residual: Optional[Tensor], out: Optional[Tensor], scratch: Optional[Tensor], min_wgs: Optional[int]) -> Tensor:
+    """What linear_fp8w and linear_mxfp4w share once their operands are checked (csrc/wstream.h): up to `max_m` rows ONE launch of the entry point `sym`
+    (`sym`_wgs with a floor), more rows `dequantize(*pair)` into `scratch` and the existing `linear`.  `scale_args` is what the entry
+    point takes between q's row stride and the residual."""
+    M, Ka = a.shape
+    assert K == Ka
+    if M > max_m:
+        if scratch is None or scratch.dtype != a.dtype or scratch.numel() < N * K:
+            raise ValueError(f"{sym[6:]}: M={M} > {max_m} dequantises the weight: pass `scratch`, {N * K} elements of {a.dtype}")
+        w = dequantize(*pair, out=scratch.reshape(-1)[:N * K].view(N, K))
+        return linear(a, w, residual=residual, out=out)
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    assert out.shape == (M, N) and out.dtype == a.dtype
+    ldc = _rows_ld(out)
+    if residual is not None:
+        assert residual.shape == (M, N) and residual.dtype == a.dtype and (M == 1 or _rows_ld(residual) == ldc), "residual shares out's row stride"
+    args = (_stream(), _code(a.dtype), a.data_ptr(), _rows_ld(a), q.data_ptr(), _rows_ld(q), *scale_args,
+            None if residual is None else residual.data_ptr(), out.data_ptr(), ldc, M, N, K)
+    if min_wgs is None:
+        _lib.call(sym, *args)
+    else:
+        _lib.call(sym + "_wgs", *args, int(min_wgs))
+    return out
 
 
 def quantize_fp8_rows(w: Tensor, q: Optional[Tensor] = None, e: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -1012,30 +1039,12 @@ def linear_fp8w(a: Tensor, q: Tensor, e: Tensor, residual: Optional[Tensor] = No
     caller's, at least N * K elements of a.dtype — and run the existing `linear` on it: the same function, `linear`'s summation order.
     `min_wgs` replaces the floor of the kernel's band rule (setok_linear_fp8w_wgs; None: the library's own, one workgroup per CU): it moves
     columns between workgroups and changes no bit."""
-    M, K = a.shape
-    N, K2 = q.shape
-    assert K == K2 and q.dtype == torch.uint8 and e.shape == (N,) and e.dtype == torch.int8 and e.is_contiguous()
-    if M > FP8W_MAX_M:
-        if scratch is None or scratch.dtype != a.dtype or scratch.numel() < N * K:
-            raise ValueError(f"linear_fp8w: M={M} > {FP8W_MAX_M} dequantises the weight: pass `scratch`, {N * K} elements of {a.dtype}")
-        w = dequantize_fp8_rows(q, e, out=scratch.reshape(-1)[:N * K].view(N, K))
-        return linear(a, w, residual=residual, out=out)
-    if out is None:
-        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
-    assert out.shape == (M, N) and out.dtype == a.dtype
-    ldc = _rows_ld(out)
-    if residual is not None:
-        assert residual.shape == (M, N) and residual.dtype == a.dtype and (M == 1 or _rows_ld(residual) == ldc), "residual shares out's row stride"
-    args = (_stream(), _code(a.dtype), a.data_ptr(), _rows_ld(a), q.data_ptr(), _rows_ld(q), _p(e),
-            None if residual is None else residual.data_ptr(), out.data_ptr(), ldc, M, N, K)
-    if min_wgs is None:
-        _lib.call("setok_linear_fp8w", *args)
-    else:
-        _lib.call("setok_linear_fp8w_wgs", *args, int(min_wgs))
-    return out
+    N, K = q.shape
+    assert q.dtype == torch.uint8 and e.shape == (N,) and e.dtype == torch.int8 and e.is_contiguous()
+    return _linear_wstream("setok_linear_fp8w", FP8W_MAX_M, dequantize_fp8_rows, a, q, (_p(e),), (q, e), N, K, residual, out, scratch, min_wgs)
 
 
-# ---- MXFP4 weight-only storage (csrc/gemm_mxfp4w.hip) ---------------------------------------------------------------------------------------------
+# ---- MXFP4 weight-only storage (csrc/gemm_mxfp4w.hip; the M <= 64 GEMM it shares with fp8: csrc/wstream.h, here _linear_wstream above) ----------
 MXFP4W_MAX_M = 64                                 # rows setok_linear_mxfp4w takes; more rows dequantise and go through `linear`
 MXFP4_BLOCK = 32                                  # elements per e8m0 scale byte
 
@@ -1081,27 +1090,9 @@ def linear_mxfp4w(a: Tensor, q: Tensor, s: Tensor, residual: Optional[Tensor] = 
     at least N * K elements of a.dtype — and run the existing `linear` on it: the same function, `linear`'s summation order.
     `min_wgs` replaces the floor of the kernel's band rule (setok_linear_mxfp4w_wgs; None: the library's own, one workgroup per CU): it moves
     columns between workgroups and changes no bit."""
-    M, Ka = a.shape
     N, K = _mxfp4_check(q, s)
-    assert K == Ka
-    if M > MXFP4W_MAX_M:
-        if scratch is None or scratch.dtype != a.dtype or scratch.numel() < N * K:
-            raise ValueError(f"linear_mxfp4w: M={M} > {MXFP4W_MAX_M} dequantises the weight: pass `scratch`, {N * K} elements of {a.dtype}")
-        w = dequantize_mxfp4_rows(q, s, out=scratch.reshape(-1)[:N * K].view(N, K))
-        return linear(a, w, residual=residual, out=out)
-    if out is None:
-        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
-    assert out.shape == (M, N) and out.dtype == a.dtype
-    ldc = _rows_ld(out)
-    if residual is not None:
-        assert residual.shape == (M, N) and residual.dtype == a.dtype and (M == 1 or _rows_ld(residual) == ldc), "residual shares out's row stride"
-    args = (_stream(), _code(a.dtype), a.data_ptr(), _rows_ld(a), q.data_ptr(), _rows_ld(q), s.data_ptr(), _rows_ld(s),
-            None if residual is None else residual.data_ptr(), out.data_ptr(), ldc, M, N, K)
-    if min_wgs is None:
-        _lib.call("setok_linear_mxfp4w", *args)
-    else:
-        _lib.call("setok_linear_mxfp4w_wgs", *args, int(min_wgs))
-    return out
+    return _linear_wstream("setok_linear_mxfp4w", MXFP4W_MAX_M, dequantize_mxfp4_rows, a, q, (s.data_ptr(), _rows_ld(s)), (q, s), N, K, residual, out,
+                           scratch, min_wgs)
 
 
 # ---- the DiffLoss image head (csrc/diffusion.hip) ---------------------------------------------------------------------------------------------

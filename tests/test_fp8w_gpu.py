@@ -322,9 +322,9 @@ def test_storage_and_refusals_of_a_quantised_model():
     assert m.weight_format == "native"
     assert m.quantize_fp8_() is m and m.weight_format == "fp8_e4m3"
     assert all(l.weight.untyped_storage().nbytes() == 0 for l in lins)                            # the masters are gone ...
-    held = sum(q.numel() * q.element_size() + e.numel() * e.element_size() for L in m.model._fp8["layers"] for q, e in (L[k] for k in ("wqkv", "wo", "wgu", "wd")))
+    held = sum(q.numel() * q.element_size() + e.numel() * e.element_size() for L in m.model._quant["layers"] for q, e in (L[k] for k in ("wqkv", "wo", "wgu", "wd")))
     assert held == sum(n * k + n for n, k in shapes)                                              # ... N * K + N bytes per matrix remain
-    assert all(q.dtype == torch.uint8 and e.dtype == torch.int8 for L in m.model._fp8["layers"] for q, e in (L[k] for k in ("wqkv", "wo", "wgu", "wd")))
+    assert all(q.dtype == torch.uint8 and e.dtype == torch.int8 for L in m.model._quant["layers"] for q, e in (L[k] for k in ("wqkv", "wo", "wgu", "wd")))
     assert m.lm_head.weight.numel() and m.model.embed_tokens.weight.numel()                       # embed_tokens and lm_head stay
     with pytest.raises(NotImplementedError, match="fp8"):
         m.state_dict()

@@ -155,7 +155,7 @@ def test_add_lora_refuses_by_name(tiny, lib):
     with pytest.raises(NotImplementedError, match="already attached"):
         tiny.add_lora_(16, 32)
     fp8 = SetokimLlamaPrefill(dict(TINY))
-    fp8.model._fp8 = dict()                                                                    # (what quantize_fp8_ leaves behind; it needs a device)
+    fp8.model._quant = dict(fmt=sys.modules["setok_amd.llama"]._FP8)                           # (what quantize_fp8_ leaves behind; it needs a device)
     with pytest.raises(NotImplementedError, match="fp8 storage"):
         fp8.add_lora_(16, 32)
     for call in (lambda: SetokimLlamaPrefill(dict(TINY)).lora_state_dict(), lambda: SetokimLlamaPrefill(dict(TINY)).merge_lora_(),

@@ -382,11 +382,11 @@ def test_storage_and_refusals_of_a_quantised_model():
     lins = [l for l in m.model.layers.modules() if isinstance(l, torch.nn.Linear)]
     shapes = [tuple(l.weight.shape) for l in lins]
     assert m.weight_format == "native"
-    assert m.quantize_mxfp4_() is m and m.weight_format == "mxfp4_e2m1" and m.model._fp8 is None
+    assert m.quantize_mxfp4_() is m and m.weight_format == "mxfp4_e2m1" and m.model._quant["fmt"].tag == "mxfp4"
     assert all(l.weight.untyped_storage().nbytes() == 0 for l in lins)                            # the masters are gone ...
-    held = sum(q.numel() * q.element_size() + s.numel() * s.element_size() for L in m.model._mxfp4["layers"] for q, s in (L[k] for k in MATS))
+    held = sum(q.numel() * q.element_size() + s.numel() * s.element_size() for L in m.model._quant["layers"] for q, s in (L[k] for k in MATS))
     assert held == sum(n * k // 2 + n * k // 32 for n, k in shapes)                               # ... N K / 2 + N K / 32 bytes per matrix remain
-    assert all(q.dtype == torch.uint8 and s.dtype == torch.uint8 for L in m.model._mxfp4["layers"] for q, s in (L[k] for k in MATS))
+    assert all(q.dtype == torch.uint8 and s.dtype == torch.uint8 for L in m.model._quant["layers"] for q, s in (L[k] for k in MATS))
     assert m.lm_head.weight.numel() and m.model.embed_tokens.weight.numel()                       # embed_tokens and lm_head stay
     for call in (m.state_dict, m.model.state_dict, m.quantize_mxfp4_, m.quantize_fp8_, m.model.quantize_fp8_,
                  lambda: m.model.add_lora_(64, 128.0), lambda: m.to(torch.float16)(inputs_embeds=x.half(), attention_mask=am, position_ids=pos)):
@@ -405,7 +405,7 @@ def test_storage_and_refusals_of_a_quantised_model():
     f8.quantize_fp8_()
     with pytest.raises(NotImplementedError, match="mxfp4"):
         f8.quantize_mxfp4_()
-    assert f8.weight_format == "fp8_e4m3" and f8.model._mxfp4 is None
+    assert f8.weight_format == "fp8_e4m3" and f8.model._quant["fmt"].tag == "fp8"
     lo, _, _, _ = _fresh("dh128_left", dt)
     lo.model.add_lora_(64, 128.0)
     with pytest.raises(NotImplementedError, match=r"quantize_mxfp4_.*merge_lora_\(\)"):
