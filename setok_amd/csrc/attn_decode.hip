@@ -4,7 +4,7 @@
 //   setok_attention_decode_gqa  one query row per (sequence, query head) against the cached keys / values: eager_attention_forward for one new token
 //   setok_argmax_rows           greedy selection on the device (lowest index of the row maximum)
 //   setok_kv_append_fp8, setok_attention_decode_gqa_fp8kv   the same two over a cache stored as e4m3fn rows with a power-of-two exponent per row
-//                               (second half of this file)
+//                               (the same decode kernel over the KvFp8 format of attn_partials.h)
 //
 // The decode attention is bound by the K / V bytes it reads.  Its structure:
 //   - work is cut over (key chunk of SETOK_DECODE_CHUNK slots, key / value head, sequence); the chunk length is a constant, so the partition of a
@@ -24,16 +24,8 @@
 
 namespace {
 
-template <typename T> __device__ inline float rnd(float v) { return (float)(T)v; }
-
-template <typename T> struct Raw16;
-template <> struct Raw16<float> { typedef f32x4 type; };
-template <> struct Raw16<bf16> { typedef bf16x8 type; };
-
 constexpr int DEC_CHUNK = SETOK_DECODE_CHUNK;
-constexpr int DEC_WAVES = 4;
-constexpr int DEC_WKEYS = DEC_CHUNK / DEC_WAVES;          // keys per wave
-static_assert(DEC_WKEYS == 32, "the wave's slice is 32 keys: NSTEP = LPR / 2 below");
+constexpr int DEC_WAVES = 4;                              // a wave's slice is CHUNK / 4 keys: 32 native (NSTEP = LPR / 2 below), 64 over e4m3 rows
 
 // Sum over aligned groups of N lanes (N a power of two), every lane of a group ending with the same bits: an xor butterfly.  Inside a row of 16 lanes the
 // exchanges are DPP modifiers on the add (quad_perm for xor 1 and 2; once a quad's lanes agree, row_half_mirror and row_mirror pair the same partial sums
@@ -73,20 +65,24 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const T* __restrict__ qk
 
 // ---- decode attention, a cache row spread over LPR lanes -------------------------------------------------------------------------------------
 // grid (chunks, Hkv * (G / GT), B); GT query heads of one group per workgroup (G itself for G in {1, 2, 4, 8}).  ws: per (sequence, query head,
-// chunk) Dh + 2 floats [max, sum, accumulators].
-template <typename T, int LPR, int GT>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                          const uint8_t* __restrict__ kmask, float* __restrict__ ws, int cap, int len, int H,
-                                                          int Hkv, float scale) {
-    constexpr int VEC = Elem<T>::VEC, DH = LPR * VEC, KPS = 64 / LPR, NSTEP = DEC_WKEYS / KPS;
-    typedef typename Raw16<T>::type V16;
+// chunk) Dh + 2 floats [max, sum, accumulators].  F is the cache's format (attn_partials.h): a lane holds F::VEC elements of a row, so a load
+// instruction covers 64 / LPR keys and a wave's slice is F::CHUNK / 4 keys — 32 native, 64 over e4m3 rows: 8 + 8 loads of 16 bytes per lane at head
+// dim 128 either way.  Scaling of an e4m3 row: 2^e of a K row multiplies the FINISHED dot product (before `scale`), 2^e of a V row is folded into
+// the ROUNDED probability — both exact, so every product and sum equals the one over K', V'.  A slot that does not count is discarded by selection:
+// its exponent byte is replaced by 0 before a scale is built.
+template <typename T, typename F, int LPR, int GT>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ q, int64_t ldq, F kv, const uint8_t* __restrict__ kmask,
+                                                          float* __restrict__ ws, int cap, int len, int H, int Hkv, float scale) {
+    constexpr int VEC = F::VEC, DH = LPR * VEC, KPS = 64 / LPR, WKEYS = F::CHUNK / DEC_WAVES, NSTEP = WKEYS / KPS, QV = Elem<T>::VEC;
+    static_assert(WKEYS % KPS == 0 && NSTEP >= 1, "a wave's slice is a whole number of load steps");
+    typedef typename F::Raw V16;
     __shared__ float red[DEC_WAVES][GT][DH + 2];
     const int c = blockIdx.x, b = blockIdx.z, nch = gridDim.x;
     const int G = H / Hkv, npass = G / GT;
     const int hk = blockIdx.y / npass, h0 = hk * G + (blockIdx.y % npass) * GT;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane / LPR, cc = lane % LPR;
     const int64_t rowbase = ((int64_t)b * Hkv + hk) * cap;
-    const int jw = c * DEC_CHUNK + wave * DEC_WKEYS;                   // the wave's first key
+    const int jw = c * F::CHUNK + wave * WKEYS;                        // the wave's first key
 
     if (jw >= len) {                                                   // the whole slice lies past len (the last chunk): no key, nothing to load
         if (r == 0) {
@@ -99,27 +95,36 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
         }
     } else {
         // every K and V load of the wave's slice is issued here, before the first use; a slot at or past len is read as slot len - 1 (in bounds) and masked
-        // (the mask bytes first: loads return in order, and a score must not have to wait for the V rows issued behind its K row)
+        // (the mask and exponent bytes first: loads return in order, and a score must not have to wait for the V rows issued behind its K row)
         V16 kr[NSTEP], vr[NSTEP];
         uint8_t mb[NSTEP];
+        int8_t ek[NSTEP], ev[NSTEP];
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
             mb[i] = kmask[(int64_t)b * cap + jc];                         // (unconditional: a load behind a branch is waited for on the spot)
+            if constexpr (F::SCALED) {
+                ek[i] = kv.ke[rowbase + jc];
+                ev[i] = kv.ve[rowbase + jc];
+            }
         }
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            kr[i] = *reinterpret_cast<const V16*>(kc + (rowbase + jc) * DH + cc * VEC);
+            kr[i] = *reinterpret_cast<const V16*>(kv.k + (rowbase + jc) * DH + cc * VEC);
         }
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            vr[i] = *reinterpret_cast<const V16*>(vc + (rowbase + jc) * DH + cc * VEC);
+            vr[i] = *reinterpret_cast<const V16*>(kv.v + (rowbase + jc) * DH + cc * VEC);
         }
         float qf[GT][VEC];
+        int cq = cc;
+        if constexpr (LPR == 1) asm volatile("" : "+v"(cq));           // (head dim 16 over e4m3 rows: q's address is uniform, and 16 GT scalar registers of q spill at GT = 8; keep it a vector load)
 #pragma unroll
-        for (int g = 0; g < GT; ++g) ld_vec<T>(q + (int64_t)b * ldq + (int64_t)(h0 + g) * DH + cc * VEC, qf[g]);
+        for (int g = 0; g < GT; ++g)
+#pragma unroll
+            for (int u = 0; u < VEC / QV; ++u) ld_vec<T>(q + (int64_t)b * ldq + (int64_t)(h0 + g) * DH + cq * VEC + u * QV, qf[g] + u * QV);
         __builtin_amdgcn_sched_barrier(0);                                // all of the above in flight before the first wait: hipcc otherwise sinks the loads to their uses
         bool ok[NSTEP];
 #pragma unroll
@@ -131,15 +136,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             float kf[VEC];
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) kf[e] = (float)kr[i][e];
+            F::decode(kr[i], kf);
+            float sk = 0.f;
+            if constexpr (F::SCALED) sk = fp8w_scale(ok[i] ? (int)ek[i] : 0);      // (a dead slot's exponent byte may hold anything)
 #pragma unroll
             for (int g = 0; g < GT; ++g) {
                 float a = 0.f;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) a = fmaf(qf[g][e], kf[e], a);
                 a = row_sum<LPR>(a);                                              // over the row's LPR lanes: every lane ends with the same bits
-                s[i][g] = ok[i] ? a * scale : -INFINITY;
+                if constexpr (F::SCALED) s[i][g] = ok[i] ? a * sk * scale : -INFINITY;      // (and its codes too, the NaN code included)
+                else s[i][g] = ok[i] ? a * scale : -INFINITY;
                 m[g] = fmaxf(m[g], s[i][g]);
             }
         }
@@ -155,13 +162,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             float vf[VEC];
+            F::decode(vr[i], vf);
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) vf[e] = ok[i] ? (float)vr[i][e] : 0.f;      // (a masked slot may hold anything, NaN included)
+            for (int e = 0; e < VEC; ++e) vf[e] = ok[i] ? vf[e] : 0.f;                // (a masked slot may hold anything, NaN included)
+            float sv = 0.f;
+            if constexpr (F::SCALED) sv = fp8w_scale(ok[i] ? (int)ev[i] : 0);
 #pragma unroll
             for (int g = 0; g < GT; ++g) {
                 const float p = m[g] == -INFINITY ? 0.f : dec_exp<T>(s[i][g] - m[g]);
                 l[g] += p;
-                const float pr = rnd<T>(p);                                           // probabilities cast to the element type (HF)
+                float pr = rnd<T>(p);                                                 // probabilities cast to the element type (HF)
+                if constexpr (F::SCALED) pr = pr * sv;                                // the rounded probability times 2^e of the V row
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) acc[g][e] = fmaf(pr, vf[e], acc[g][e]);
             }
@@ -201,48 +212,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
     }
 }
 
-// ---- decode attention, any head dim (Dh % 8 == 0): one wave per (chunk, query head, sequence), a key per lane -----------------------------------
-template <typename T>
-__global__ __launch_bounds__(64) void attn_decode_any_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                             const uint8_t* __restrict__ kmask, float* __restrict__ ws, int cap, int len, int H,
-                                                             int Hkv, int Dh, float scale) {
-    __shared__ float ps[DEC_CHUNK];
-    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, nch = gridDim.x, lane = threadIdx.x;
-    const int hk = h / (H / Hkv), j0 = c * DEC_CHUNK;
-    const T* qr = q + (int64_t)b * ldq + (int64_t)h * Dh;
-    const T* kb = kc + ((int64_t)b * Hkv + hk) * cap * Dh;
-    const T* vb = vc + ((int64_t)b * Hkv + hk) * cap * Dh;
-    float mx = -INFINITY;
-    for (int jj = lane; jj < DEC_CHUNK; jj += 64) {
-        const int j = j0 + jj;
-        float sc = -INFINITY;
-        if (j < len && kmask[(int64_t)b * cap + j]) {
-            float a = 0.f;
-            for (int d = 0; d < Dh; ++d) a = fmaf((float)qr[d], (float)kb[(int64_t)j * Dh + d], a);
-            sc = a * scale;
-        }
-        ps[jj] = sc;
-        mx = fmaxf(mx, sc);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int jj = lane; jj < DEC_CHUNK; jj += 64) {
-        const float e = mx == -INFINITY ? 0.f : dec_exp<T>(ps[jj] - mx);
-        ps[jj] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    float* part = ws + (((int64_t)b * H + h) * nch + c) * (Dh + 2);
-    if (lane == 0) { part[0] = mx; part[1] = sum; }
-    for (int d = lane; d < Dh; d += 64) {
-        float o = 0.f;
-        for (int jj = 0; jj < DEC_CHUNK; ++jj)
-            if (ps[jj] != 0.f) o = fmaf(rnd<T>(ps[jj]), (float)vb[(int64_t)(j0 + jj) * Dh + d], o);      // (a non-zero weight: slot < len and unmasked)
-        part[2 + d] = o;
-    }
-}
-
 // ---- argmax over the rows of a matrix: lowest index of the maximum (a NaN counts as the maximum, like torch.argmax) ---------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* __restrict__ x, int64_t ld, int V, int64_t* __restrict__ out) {
@@ -275,44 +244,69 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* __restrict__ 
     if (threadIdx.x == 0) out[blockIdx.x] = bi[0];
 }
 
-template <typename T, int LPR>
-int launch_decode(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, const uint8_t* km, float* ws, int B, int H, int Hkv, int cap,
-                  int len, float scale) {
-    const int G = H / Hkv, nch = cdiv(len, DEC_CHUNK);
+template <typename T, typename F, int LPR>
+void launch_decode(hipStream_t s, const T* q, int64_t ldq, F kv, const uint8_t* km, float* ws, int B, int H, int Hkv, int cap, int len, float scale) {
+    const int G = H / Hkv, nch = cdiv(len, F::CHUNK);
     const int GT = G % 8 == 0 ? 8 : G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1;
     dim3 grid(nch, Hkv * (G / GT), B);
     switch (GT) {
-        case 8: attn_decode_kernel<T, LPR, 8><<<grid, 256, 0, s>>>(q, ldq, kc, vc, km, ws, cap, len, H, Hkv, scale); break;
-        case 4: attn_decode_kernel<T, LPR, 4><<<grid, 256, 0, s>>>(q, ldq, kc, vc, km, ws, cap, len, H, Hkv, scale); break;
-        case 2: attn_decode_kernel<T, LPR, 2><<<grid, 256, 0, s>>>(q, ldq, kc, vc, km, ws, cap, len, H, Hkv, scale); break;
-        default: attn_decode_kernel<T, LPR, 1><<<grid, 256, 0, s>>>(q, ldq, kc, vc, km, ws, cap, len, H, Hkv, scale); break;
+        case 8: attn_decode_kernel<T, F, LPR, 8><<<grid, 256, 0, s>>>(q, ldq, kv, km, ws, cap, len, H, Hkv, scale); break;
+        case 4: attn_decode_kernel<T, F, LPR, 4><<<grid, 256, 0, s>>>(q, ldq, kv, km, ws, cap, len, H, Hkv, scale); break;
+        case 2: attn_decode_kernel<T, F, LPR, 2><<<grid, 256, 0, s>>>(q, ldq, kv, km, ws, cap, len, H, Hkv, scale); break;
+        default: attn_decode_kernel<T, F, LPR, 1><<<grid, 256, 0, s>>>(q, ldq, kv, km, ws, cap, len, H, Hkv, scale); break;
     }
-    return 0;
 }
 
-template <typename T>
-int decode_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, const uint8_t* km, T* out, float* ws, int B, int H, int Hkv, int Dh,
-             int cap, int len, float scale) {
-    const int nch = cdiv(len, DEC_CHUNK);
-    switch (Dh % Elem<T>::VEC == 0 ? Dh / Elem<T>::VEC : 0) {
-        case 2: launch_decode<T, 2>(s, q, ldq, kc, vc, km, ws, B, H, Hkv, cap, len, scale); break;
-        case 4: launch_decode<T, 4>(s, q, ldq, kc, vc, km, ws, B, H, Hkv, cap, len, scale); break;
-        case 8: launch_decode<T, 8>(s, q, ldq, kc, vc, km, ws, B, H, Hkv, cap, len, scale); break;
-        case 16: launch_decode<T, 16>(s, q, ldq, kc, vc, km, ws, B, H, Hkv, cap, len, scale); break;       // head dim 128 in the 16-bit types
-        case 32: launch_decode<T, 32>(s, q, ldq, kc, vc, km, ws, B, H, Hkv, cap, len, scale); break;
-        default: attn_decode_any_kernel<T><<<dim3(nch, H, B), 64, 0, s>>>(q, ldq, kc, vc, km, ws, cap, len, H, Hkv, Dh, scale); break;
+// Both entry points (`name`: the entry point's, for its messages).  A head dim with a lane layout takes the chunk kernel — over e4m3 rows head dims
+// 16 / 32 / 64 / 128, native every LPR = Dh / VEC in {2, ..., 32} — and every other one the wave-per-chunk kernel of attn_partials.h.
+template <typename T, typename F>
+int decode_t(const char* name, hipStream_t s, const T* q, int64_t ldq, F kv, const uint8_t* km, T* out, float* ws, int B, int H, int Hkv, int Dh, int cap,
+             int len, float scale) {
+    const int nch = cdiv(len, F::CHUNK);
+    auto any = [&] { attn_chunk_any_kernel<T, F, F::CHUNK, false><<<dim3(nch, H, B), 64, 0, s>>>(q, ldq, kv, km, ws, 1, H, Hkv, Dh, cap, len - 1, scale); };
+#define DEC_LPR(N) launch_decode<T, F, N>(s, q, ldq, kv, km, ws, B, H, Hkv, cap, len, scale); break
+    if constexpr (F::SCALED) {
+        switch (Dh) {
+            case 16: DEC_LPR(1);
+            case 32: DEC_LPR(2);
+            case 64: DEC_LPR(4);
+            case 128: DEC_LPR(8);
+            default: any(); break;
+        }
+    } else {
+        switch (Dh % F::VEC == 0 ? Dh / F::VEC : 0) {
+            case 2: DEC_LPR(2);
+            case 4: DEC_LPR(4);
+            case 8: DEC_LPR(8);
+            case 16: DEC_LPR(16);                                      // head dim 128 in the 16-bit types
+            case 32: DEC_LPR(32);
+            default: any(); break;
+        }
     }
-    SETOK_CHECK_LAUNCH("setok_attention_decode(chunks)");
-    attn_decode_merge_kernel<T><<<B * H, 64, 0, s>>>(ws, out, nch, H, Dh);
-    SETOK_CHECK_LAUNCH("setok_attention_decode(merge)");
+#undef DEC_LPR
+    if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(chunks): %s", name, hipGetErrorString(e));
+    attn_decode_merge_kernel<T><<<B * H, 64, 0, s>>>(ws, out, nch, H, Dh);      // one merge: the partials have the same layout in both formats
+    if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(merge): %s", name, hipGetErrorString(e));
     return SETOK_OK;
 }
 
-// ==== the fp8 KV cache (include/setok_hip.h, "FP8 KV cache") =====================================================================================
+// What both decode entry points require of their arguments; `caches` is how the entry point's alignment message calls its K / V operands.
+int check_decode(const char* name, const char* caches, bool operands, bool aligned, int dtype, int64_t ldq, int B, int H, int Hkv, int Dh, int cap, int len,
+                 int chunk, int64_t ws_floats) {
+    SETOK_CHECK_ARG(operands, "%s: null operand", name);
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "%s: bad dtype %d", name, dtype);
+    SETOK_CHECK_ARG(B >= 0 && B <= 65535 && H > 0 && Hkv > 0 && H % Hkv == 0, "%s: bad shape B=%d H=%d Hkv=%d", name, B, H, Hkv);
+    SETOK_CHECK_ARG(Dh > 0 && Dh % 8 == 0, "%s: unsupported head dim %d (a multiple of 8)", name, Dh);
+    SETOK_CHECK_ARG(cap > 0 && len >= 1 && len <= cap, "%s: len = %d outside [1, cap = %d] (len > cap)", name, len, cap);
+    SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned, "%s: q rows (stride %lld) and the %s must be 16-byte aligned", name, (long long)ldq,
+                    caches);
+    const int64_t need = (int64_t)B * H * cdiv(len, chunk) * (Dh + 2);
+    SETOK_CHECK_ARG(ws_floats >= need, "%s: workspace of %lld floats, %lld needed", name, (long long)ws_floats, (long long)need);
+    return SETOK_OK;
+}
+
+// ==== filling the fp8 KV cache (include/setok_hip.h, "FP8 KV cache") ==============================================================================
 // A cache row is Dh e4m3fn bytes + one int8 exponent and means value(q[d]) * 2^e (fp8.h: the rule of the weight path).
-constexpr int F8_CHUNK = SETOK_DECODE_CHUNK_FP8KV;
-constexpr int F8_WKEYS = F8_CHUNK / DEC_WAVES;             // keys per wave: 64
-constexpr int F8_VEC = 16;                                 // cache elements per 16-byte load
 
 // Maximum over aligned groups of N lanes of non-negative values, every lane of a group ending with the same bits: row_sum's exchanges.
 template <int CTRL> __device__ inline float dpp_max(float a) {
@@ -392,221 +386,6 @@ void launch_append_fp8(hipStream_t s, const T* qkv, uint8_t* kq, int8_t* ke, uin
 #undef F8_APPEND
 }
 
-// ---- decode attention over the fp8 cache, a cache row spread over LPR = Dh / 16 lanes -------------------------------------------------------------
-// attn_decode_kernel with fp8 rows: the same cut over (chunk, key / value head, sequence), the same order of loads (mask and exponent bytes,
-// unconditionally, ahead of the K rows, ahead of the V rows, ahead of q; a sched_barrier before the first wait), the same partials.  A lane
-// holds 16 elements of a row, so a load instruction covers 64 / LPR keys and a wave's slice is 64 keys: 8 + 8 loads of 16 bytes per lane at
-// head dim 128, what the 16-bit kernel has in flight.  Conversion is v_cvt_pk_f32_fp8 (exact).  Scaling: 2^e of a K row multiplies the
-// FINISHED dot product (before `scale`), 2^e of a V row is folded into the ROUNDED probability — both exact, so every product and sum equals
-// the one over K', V'.  A slot that does not count is discarded by selection: its exponent byte is replaced by 0 before a scale is built.
-template <typename T, int LPR, int GT>
-__global__ __launch_bounds__(256) void attn_decode_fp8kv_kernel(const T* __restrict__ q, int64_t ldq, const uint8_t* __restrict__ kq,
-                                                                const int8_t* __restrict__ ke, const uint8_t* __restrict__ vq,
-                                                                const int8_t* __restrict__ ve, const uint8_t* __restrict__ kmask,
-                                                                float* __restrict__ ws, int cap, int len, int H, int Hkv, float scale) {
-    constexpr int VEC = F8_VEC, DH = LPR * VEC, KPS = 64 / LPR, NSTEP = F8_WKEYS / KPS, QV = Elem<T>::VEC;
-    __shared__ float red[DEC_WAVES][GT][DH + 2];
-    const int c = blockIdx.x, b = blockIdx.z, nch = gridDim.x;
-    const int G = H / Hkv, npass = G / GT;
-    const int hk = blockIdx.y / npass, h0 = hk * G + (blockIdx.y % npass) * GT;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane / LPR, cc = lane % LPR;
-    const int64_t rowbase = ((int64_t)b * Hkv + hk) * cap;
-    const int jw = c * F8_CHUNK + wave * F8_WKEYS;                     // the wave's first key
-
-    if (jw >= len) {                                                   // the whole slice lies past len: no key, nothing to load
-        if (r == 0) {
-#pragma unroll
-            for (int g = 0; g < GT; ++g) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) red[wave][g][2 + cc * VEC + e] = 0.f;
-                if (cc == 0) { red[wave][g][0] = -INFINITY; red[wave][g][1] = 0.f; }
-            }
-        }
-    } else {
-        u32x4 kr[NSTEP], vr[NSTEP];
-        uint8_t mb[NSTEP];
-        int8_t ek[NSTEP], ev[NSTEP];
-#pragma unroll
-        for (int i = 0; i < NSTEP; ++i) {                              // a slot at or past len is read as slot len - 1 (in bounds) and discarded
-            const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            mb[i] = kmask[(int64_t)b * cap + jc];
-            ek[i] = ke[rowbase + jc];
-            ev[i] = ve[rowbase + jc];
-        }
-#pragma unroll
-        for (int i = 0; i < NSTEP; ++i) {
-            const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            kr[i] = *reinterpret_cast<const u32x4*>(kq + (rowbase + jc) * DH + cc * VEC);
-        }
-#pragma unroll
-        for (int i = 0; i < NSTEP; ++i) {
-            const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            vr[i] = *reinterpret_cast<const u32x4*>(vq + (rowbase + jc) * DH + cc * VEC);
-        }
-        float qf[GT][VEC];
-        int cq = cc;
-        if constexpr (LPR == 1) asm volatile("" : "+v"(cq));           // (head dim 16: q's address is uniform, and 16 GT scalar registers of q spill at GT = 8; keep it a vector load)
-#pragma unroll
-        for (int g = 0; g < GT; ++g)
-#pragma unroll
-            for (int u = 0; u < VEC / QV; ++u) ld_vec<T>(q + (int64_t)b * ldq + (int64_t)(h0 + g) * DH + cq * VEC + u * QV, qf[g] + u * QV);
-        __builtin_amdgcn_sched_barrier(0);                             // all of the above in flight before the first wait
-        bool ok[NSTEP];
-#pragma unroll
-        for (int i = 0; i < NSTEP; ++i) ok[i] = (jw + i * KPS + r < len) & (mb[i] != 0);
-
-        float s[NSTEP][GT], m[GT];
-#pragma unroll
-        for (int g = 0; g < GT; ++g) m[g] = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NSTEP; ++i) {
-            float kf[VEC];
-            fp8w_decode16(kr[i], kf);
-            const float sk = fp8w_scale(ok[i] ? (int)ek[i] : 0);       // (a dead slot's exponent byte may hold anything)
-#pragma unroll
-            for (int g = 0; g < GT; ++g) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) a = fmaf(qf[g][e], kf[e], a);
-                a = row_sum<LPR>(a);
-                s[i][g] = ok[i] ? a * sk * scale : -INFINITY;          // (and its codes too, the NaN code included)
-                m[g] = fmaxf(m[g], s[i][g]);
-            }
-        }
-        float l[GT], acc[GT][VEC];
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-#pragma unroll
-            for (int o = LPR; o < 64; o <<= 1) m[g] = fmaxf(m[g], __shfl_xor(m[g], o, 64));
-            l[g] = 0.f;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[g][e] = 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < NSTEP; ++i) {
-            float vf[VEC];
-            fp8w_decode16(vr[i], vf);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) vf[e] = ok[i] ? vf[e] : 0.f;
-            const float sv = fp8w_scale(ok[i] ? (int)ev[i] : 0);
-#pragma unroll
-            for (int g = 0; g < GT; ++g) {
-                const float p = m[g] == -INFINITY ? 0.f : dec_exp<T>(s[i][g] - m[g]);
-                l[g] += p;
-                const float pr = rnd<T>(p) * sv;                       // the rounded probability times 2^e of the V row
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) acc[g][e] = fmaf(pr, vf[e], acc[g][e]);
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-#pragma unroll
-            for (int o = LPR; o < 64; o <<= 1) {
-                l[g] += __shfl_xor(l[g], o, 64);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) acc[g][e] += __shfl_xor(acc[g][e], o, 64);
-            }
-            if (r == 0) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) red[wave][g][2 + cc * VEC + e] = acc[g][e];
-                if (cc == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
-            }
-        }
-    }
-    __syncthreads();
-    // the chunk's partial: the four waves in wave order
-    for (int idx = tid; idx < GT * DH; idx += 256) {
-        const int g = idx / DH, d = idx % DH;
-        float M = red[0][g][0];
-#pragma unroll
-        for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red[w][g][0]);
-        float L = 0.f, val = 0.f;
-#pragma unroll
-        for (int w = 0; w < DEC_WAVES; ++w) {
-            const float f = red[w][g][0] == -INFINITY ? 0.f : dec_exp<T>(red[w][g][0] - M);
-            L = fmaf(f, red[w][g][1], L);
-            val = fmaf(f, red[w][g][2 + d], val);
-        }
-        float* part = ws + (((int64_t)b * H + h0 + g) * nch + c) * (DH + 2);
-        part[2 + d] = val;
-        if (d == 0) { part[0] = M; part[1] = L; }
-    }
-}
-
-// ---- decode attention over the fp8 cache, any head dim (Dh % 8 == 0): one wave per (chunk, query head, sequence), a key per lane -----------------
-template <typename T>
-__global__ __launch_bounds__(64) void attn_decode_fp8kv_any_kernel(const T* __restrict__ q, int64_t ldq, const uint8_t* __restrict__ kq,
-                                                                   const int8_t* __restrict__ ke, const uint8_t* __restrict__ vq,
-                                                                   const int8_t* __restrict__ ve, const uint8_t* __restrict__ kmask,
-                                                                   float* __restrict__ ws, int cap, int len, int H, int Hkv, int Dh, float scale) {
-    __shared__ float ps[F8_CHUNK];
-    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, nch = gridDim.x, lane = threadIdx.x;
-    const int hk = h / (H / Hkv), j0 = c * F8_CHUNK;
-    const T* qr = q + (int64_t)b * ldq + (int64_t)h * Dh;
-    const int64_t rowbase = ((int64_t)b * Hkv + hk) * cap;
-    float mx = -INFINITY;
-    for (int jj = lane; jj < F8_CHUNK; jj += 64) {
-        const int j = j0 + jj;
-        float sc = -INFINITY;
-        if (j < len && kmask[(int64_t)b * cap + j]) {                  // (only a slot that counts is decoded and scaled)
-            const uint8_t* kb = kq + (rowbase + j) * Dh;
-            float a = 0.f;
-            for (int d = 0; d < Dh; ++d) a = fmaf((float)qr[d], __builtin_amdgcn_cvt_pk_f32_fp8((int)kb[d], false)[0], a);
-            sc = a * fp8w_scale(ke[rowbase + j]) * scale;
-        }
-        ps[jj] = sc;
-        mx = fmaxf(mx, sc);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int jj = lane; jj < F8_CHUNK; jj += 64) {
-        const float e = mx == -INFINITY ? 0.f : dec_exp<T>(ps[jj] - mx);
-        ps[jj] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    float* part = ws + (((int64_t)b * H + h) * nch + c) * (Dh + 2);
-    if (lane == 0) { part[0] = mx; part[1] = sum; }
-    for (int d = lane; d < Dh; d += 64) {
-        float o = 0.f;
-        for (int jj = 0; jj < F8_CHUNK; ++jj)
-            if (ps[jj] != 0.f)                                         // (a non-zero weight: slot < len and unmasked)
-                o = fmaf(rnd<T>(ps[jj]) * fp8w_scale(ve[rowbase + j0 + jj]), __builtin_amdgcn_cvt_pk_f32_fp8((int)vq[(rowbase + j0 + jj) * Dh + d], false)[0], o);
-        part[2 + d] = o;
-    }
-}
-
-template <typename T, int LPR>
-void launch_decode_fp8kv(hipStream_t s, const T* q, int64_t ldq, const uint8_t* kq, const int8_t* ke, const uint8_t* vq, const int8_t* ve,
-                         const uint8_t* km, float* ws, int B, int H, int Hkv, int cap, int len, float scale) {
-    const int G = H / Hkv, nch = cdiv(len, F8_CHUNK);
-    const int GT = G % 8 == 0 ? 8 : G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1;
-    dim3 grid(nch, Hkv * (G / GT), B);
-    switch (GT) {
-        case 8: attn_decode_fp8kv_kernel<T, LPR, 8><<<grid, 256, 0, s>>>(q, ldq, kq, ke, vq, ve, km, ws, cap, len, H, Hkv, scale); break;
-        case 4: attn_decode_fp8kv_kernel<T, LPR, 4><<<grid, 256, 0, s>>>(q, ldq, kq, ke, vq, ve, km, ws, cap, len, H, Hkv, scale); break;
-        case 2: attn_decode_fp8kv_kernel<T, LPR, 2><<<grid, 256, 0, s>>>(q, ldq, kq, ke, vq, ve, km, ws, cap, len, H, Hkv, scale); break;
-        default: attn_decode_fp8kv_kernel<T, LPR, 1><<<grid, 256, 0, s>>>(q, ldq, kq, ke, vq, ve, km, ws, cap, len, H, Hkv, scale); break;
-    }
-}
-
-template <typename T>
-int decode_fp8kv_t(hipStream_t s, const T* q, int64_t ldq, const uint8_t* kq, const int8_t* ke, const uint8_t* vq, const int8_t* ve, const uint8_t* km,
-                   T* out, float* ws, int B, int H, int Hkv, int Dh, int cap, int len, float scale) {
-    const int nch = cdiv(len, F8_CHUNK);
-    switch (Dh) {
-        case 16: launch_decode_fp8kv<T, 1>(s, q, ldq, kq, ke, vq, ve, km, ws, B, H, Hkv, cap, len, scale); break;
-        case 32: launch_decode_fp8kv<T, 2>(s, q, ldq, kq, ke, vq, ve, km, ws, B, H, Hkv, cap, len, scale); break;
-        case 64: launch_decode_fp8kv<T, 4>(s, q, ldq, kq, ke, vq, ve, km, ws, B, H, Hkv, cap, len, scale); break;
-        case 128: launch_decode_fp8kv<T, 8>(s, q, ldq, kq, ke, vq, ve, km, ws, B, H, Hkv, cap, len, scale); break;
-        default: attn_decode_fp8kv_any_kernel<T><<<dim3(nch, H, B), 64, 0, s>>>(q, ldq, kq, ke, vq, ve, km, ws, cap, len, H, Hkv, Dh, scale); break;
-    }
-    SETOK_CHECK_LAUNCH("setok_attention_decode_fp8kv(chunks)");
-    attn_decode_merge_kernel<T><<<B * H, 64, 0, s>>>(ws, out, nch, H, Dh);      // the native merge: the partials have the same layout
-    SETOK_CHECK_LAUNCH("setok_attention_decode_fp8kv(merge)");
-    return SETOK_OK;
-}
 
 }  // namespace
 
@@ -629,20 +408,15 @@ extern "C" int setok_kv_append_fp8(void* stream, int dtype, const void* qkv, uin
 extern "C" int setok_attention_decode_gqa_fp8kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const int8_t* k_e,
                                                 const uint8_t* v_q, const int8_t* v_e, const uint8_t* key_mask, void* out, int B, int H, int Hkv,
                                                 int Dh, int cap, int len, float scale, float* ws, int64_t ws_floats) {
-    SETOK_CHECK_ARG(q && k_q && k_e && v_q && v_e && key_mask && out && ws, "setok_attention_decode_fp8kv: null operand");
-    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_attention_decode_fp8kv: bad dtype %d", dtype);
-    SETOK_CHECK_ARG(B >= 0 && B <= 65535 && H > 0 && Hkv > 0 && H % Hkv == 0, "setok_attention_decode_fp8kv: bad shape B=%d H=%d Hkv=%d", B, H, Hkv);
-    SETOK_CHECK_ARG(Dh > 0 && Dh % 8 == 0, "setok_attention_decode_fp8kv: unsupported head dim %d (a multiple of 8)", Dh);
-    SETOK_CHECK_ARG(cap > 0 && len >= 1 && len <= cap, "setok_attention_decode_fp8kv: len = %d outside [1, cap = %d] (len > cap)", len, cap);
-    SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_q) && aligned16(v_q),
-                    "setok_attention_decode_fp8kv: q rows (stride %lld) and the code caches must be 16-byte aligned", (long long)ldq);
-    const int64_t need = (int64_t)B * H * cdiv(len, F8_CHUNK) * (Dh + 2);
-    SETOK_CHECK_ARG(ws_floats >= need, "setok_attention_decode_fp8kv: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)need);
+    const char* name = "setok_attention_decode_fp8kv";
+    if (int e = check_decode(name, "code caches", q && k_q && k_e && v_q && v_e && key_mask && out && ws, aligned16(q) && aligned16(k_q) && aligned16(v_q),
+                             dtype, ldq, B, H, Hkv, Dh, cap, len, KvFp8::CHUNK, ws_floats))
+        return e;
     if (B == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SETOK_BF16)
-        return decode_fp8kv_t<bf16>(s, (const bf16*)q, ldq, k_q, k_e, v_q, v_e, key_mask, (bf16*)out, ws, B, H, Hkv, Dh, cap, len, scale);
-    return decode_fp8kv_t<float>(s, (const float*)q, ldq, k_q, k_e, v_q, v_e, key_mask, (float*)out, ws, B, H, Hkv, Dh, cap, len, scale);
+    const KvFp8 kv{k_q, k_e, v_q, v_e};
+    if (dtype == SETOK_BF16) return decode_t<bf16>(name, s, (const bf16*)q, ldq, kv, key_mask, (bf16*)out, ws, B, H, Hkv, Dh, cap, len, scale);
+    return decode_t<float>(name, s, (const float*)q, ldq, kv, key_mask, (float*)out, ws, B, H, Hkv, Dh, cap, len, scale);
 }
 
 extern "C" int setok_kv_append(void* stream, int dtype, const void* qkv, void* k_cache, void* v_cache, int B, int T, int H, int Hkv, int Dh, int cap,
@@ -667,20 +441,17 @@ extern "C" int setok_kv_append(void* stream, int dtype, const void* qkv, void* k
 extern "C" int setok_attention_decode_gqa(void* stream, int dtype, const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
                                           const uint8_t* key_mask, void* out, int B, int H, int Hkv, int Dh, int cap, int len, float scale, float* ws,
                                           int64_t ws_floats) {
-    SETOK_CHECK_ARG(q && k_cache && v_cache && key_mask && out && ws, "setok_attention_decode: null operand");
-    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_attention_decode: bad dtype %d", dtype);
-    SETOK_CHECK_ARG(B >= 0 && B <= 65535 && H > 0 && Hkv > 0 && H % Hkv == 0, "setok_attention_decode: bad shape B=%d H=%d Hkv=%d", B, H, Hkv);
-    SETOK_CHECK_ARG(Dh > 0 && Dh % 8 == 0, "setok_attention_decode: unsupported head dim %d (a multiple of 8)", Dh);
-    SETOK_CHECK_ARG(cap > 0 && len >= 1 && len <= cap, "setok_attention_decode: len = %d outside [1, cap = %d] (len > cap)", len, cap);
-    SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_cache) && aligned16(v_cache),
-                    "setok_attention_decode: q rows (stride %lld) and the caches must be 16-byte aligned", (long long)ldq);
-    const int64_t need = (int64_t)B * H * cdiv(len, DEC_CHUNK) * (Dh + 2);
-    SETOK_CHECK_ARG(ws_floats >= need, "setok_attention_decode: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)need);
+    const char* name = "setok_attention_decode";
+    if (int e = check_decode(name, "caches", q && k_cache && v_cache && key_mask && out && ws, aligned16(q) && aligned16(k_cache) && aligned16(v_cache), dtype,
+                             ldq, B, H, Hkv, Dh, cap, len, DEC_CHUNK, ws_floats))
+        return e;
     if (B == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == SETOK_BF16)
-        return decode_t<bf16>(s, (const bf16*)q, ldq, (const bf16*)k_cache, (const bf16*)v_cache, key_mask, (bf16*)out, ws, B, H, Hkv, Dh, cap, len, scale);
-    return decode_t<float>(s, (const float*)q, ldq, (const float*)k_cache, (const float*)v_cache, key_mask, (float*)out, ws, B, H, Hkv, Dh, cap, len, scale);
+        return decode_t<bf16>(name, s, (const bf16*)q, ldq, KvNative<bf16>{(const bf16*)k_cache, (const bf16*)v_cache}, key_mask, (bf16*)out, ws, B, H, Hkv, Dh,
+                              cap, len, scale);
+    return decode_t<float>(name, s, (const float*)q, ldq, KvNative<float>{(const float*)k_cache, (const float*)v_cache}, key_mask, (float*)out, ws, B, H, Hkv,
+                           Dh, cap, len, scale);
 }
 
 extern "C" int setok_argmax_rows(void* stream, int dtype, const void* x, int64_t ld, int rows, int V, int64_t* out) {

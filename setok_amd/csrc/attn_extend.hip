@@ -17,14 +17,13 @@
 // registers across the chunk, S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_32x32x16 with the online softmax per lane.  The probabilities are
 // rounded to the element type by the operand pack, the normaliser sums the unrounded values.  A slot that counts for no query may hold anything:
 // its scores are replaced by selection and its V row is zeroed in LDS before the tile is used (0 * NaN would reach the accumulators otherwise).
-// Everything else (fp32, other head dims) is one wave per (chunk, query head, query row, sequence): attn_decode_any_kernel with a per-row limit.
+// Everything else (fp32, other head dims) is one wave per (query row, query head, chunk) on a grid (B * Tn, H, chunks): attn_chunk_any_kernel of
+// attn_partials.h, the decode path's fallback, with the row's own limit len0 + i + 1.
 #include "common.h"
 #include "lds_mma.h"
 #include "attn_partials.h"
 
 namespace {
-
-template <typename T> __device__ inline float rnd(float v) { return (float)(T)v; }
 
 constexpr int EXT_CHUNK = SETOK_EXTEND_CHUNK;
 constexpr int XD = 128;                  // head dim of the MFMA kernel
@@ -196,51 +195,6 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __rest
     }
 }
 
-// ---- any element type and head dim (Dh % 8 == 0): one wave per (query row of a sequence, query head, chunk), a key per lane -----------------------------
-// grid (B * Tn, H, chunks).  attn_decode_any_kernel with the row's own limit len0 + i + 1 in the place of `len`.
-template <typename T>
-__global__ __launch_bounds__(64) void attn_extend_any_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                             const uint8_t* __restrict__ kmask, float* __restrict__ ws, int Tn, int H, int Hkv, int Dh,
-                                                             int cap, int len0, float scale) {
-    __shared__ float ps[EXT_CHUNK];
-    const int64_t row = blockIdx.x;                                    // b * Tn + i
-    const int h = blockIdx.y, c = blockIdx.z, nch = gridDim.z, lane = threadIdx.x;
-    const int b = (int)(row / Tn), len = len0 + (int)(row % Tn) + 1;   // this row counts slots below len
-    const int hk = h / (H / Hkv), j0 = c * EXT_CHUNK;
-    const T* qr = q + row * ldq + (int64_t)h * Dh;
-    const T* kb = kc + ((int64_t)b * Hkv + hk) * cap * Dh;
-    const T* vb = vc + ((int64_t)b * Hkv + hk) * cap * Dh;
-    float mx = -INFINITY;
-    for (int jj = lane; jj < EXT_CHUNK; jj += 64) {
-        const int j = j0 + jj;
-        float sc = -INFINITY;
-        if (j < len && kmask[(int64_t)b * cap + j]) {                  // (only a slot that counts is read)
-            float a = 0.f;
-            for (int d = 0; d < Dh; ++d) a = fmaf((float)qr[d], (float)kb[(int64_t)j * Dh + d], a);
-            sc = a * scale;
-        }
-        ps[jj] = sc;
-        mx = fmaxf(mx, sc);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int jj = lane; jj < EXT_CHUNK; jj += 64) {
-        const float e = mx == -INFINITY ? 0.f : dec_exp<T>(ps[jj] - mx);
-        ps[jj] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    float* part = ws + ((row * H + h) * nch + c) * (Dh + 2);
-    if (lane == 0) { part[0] = mx; part[1] = sum; }
-    for (int d = lane; d < Dh; d += 64) {
-        float o = 0.f;
-        for (int jj = 0; jj < EXT_CHUNK; ++jj)
-            if (ps[jj] != 0.f) o = fmaf(rnd<T>(ps[jj]), (float)vb[(int64_t)(j0 + jj) * Dh + d], o);      // (a non-zero weight: the slot counts for this row)
-        part[2 + d] = o;
-    }
-}
-
 // slots per partial on the path a call takes: the MFMA kernel with more than 32 stacked rows spans XSPAN chunks, everything else one
 static inline int extend_span(bool low, int Tn, int H, int Hkv, int Dh) { return low && Dh == XD && (H / Hkv) * Tn > 32 ? XSPAN * EXT_CHUNK : EXT_CHUNK; }
 
@@ -258,7 +212,8 @@ int extend_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, c
             attn_extend_kernel<4><<<dim3(nch, Hkv * cdiv(MR, 128), B), 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, km, ws, Tn, H, Hkv,
                                                                                   cap, len0, span, sl);
     } else {
-        attn_extend_any_kernel<T><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kc, vc, km, ws, Tn, H, Hkv, Dh, cap, len0, scale);
+        attn_chunk_any_kernel<T, KvNative<T>, EXT_CHUNK, true><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, KvNative<T>{kc, vc}, km, ws, Tn, H, Hkv, Dh, cap, len0,
+                                                                                               scale);
     }
     SETOK_CHECK_LAUNCH("setok_attention_extend(chunks)");
     attn_decode_merge_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, nch, H, Dh);      // the decode path's merge with (b * Tn + i) as its sequence

@@ -1,9 +1,11 @@
 // attn_partials.h — what the attention kernels that cut a sequence's keys into chunks share (attn_decode.hip, attn_extend.hip): every chunk leaves
 // fp32 partials — per (sequence, query head, chunk) Dh + 2 floats [max, sum, Dh accumulators] — in the caller's workspace, and a second launch merges a
 // query head's chunks in chunk order.  ONE definition of the merge and of the exponential both sides of it use: a partial is only meaningful to the
-// merge that rescales it.
+// merge that rescales it.  Also here, once: the two cache formats as the kernels see them, and the wave-per-chunk kernel every head dim without a
+// lane layout falls back to, whichever entry point it came through.
 #pragma once
 #include "common.h"
+#include "fp8.h"
 
 namespace {
 
@@ -11,6 +13,88 @@ namespace {
 template <typename T> __device__ inline float dec_exp(float x) {
     if constexpr (sizeof(T) == 4) return expf(x);
     else return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
+}
+
+template <typename T> __device__ inline float rnd(float v) { return (float)(T)v; }
+
+template <typename T> struct Raw16;
+template <> struct Raw16<float> { typedef f32x4 type; };
+template <> struct Raw16<bf16> { typedef bf16x8 type; };
+
+// ---- the cache formats: one layer's cache as a kernel argument (by value) and what a kernel must know to read it ------------------------------
+// VEC elements per 16-byte load, CHUNK slots per decode chunk, Raw the 16 bytes in registers, decode() Raw -> VEC floats, at() one element (the
+// fallback's read).  SCALED: a row carries a power-of-two exponent byte (ke / ve), whose 2^e multiplies the finished dot product and the rounded
+// probability.
+template <typename T> struct KvNative {
+    static constexpr int VEC = Elem<T>::VEC, CHUNK = SETOK_DECODE_CHUNK;
+    static constexpr bool SCALED = false;
+    typedef typename Raw16<T>::type Raw;
+    const T *k, *v;
+    __device__ static inline void decode(const Raw& r, float* f) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) f[e] = (float)r[e];
+    }
+    __device__ static inline float at(const T* p, int64_t i) { return (float)p[i]; }
+};
+struct KvFp8 {                                                         // e4m3fn rows + one int8 exponent per row (fp8.h)
+    static constexpr int VEC = 16, CHUNK = SETOK_DECODE_CHUNK_FP8KV;
+    static constexpr bool SCALED = true;
+    typedef u32x4 Raw;
+    const uint8_t* k;
+    const int8_t* ke;
+    const uint8_t* v;
+    const int8_t* ve;
+    __device__ static inline void decode(const Raw& r, float* f) { fp8w_decode16(r, f); }      // v_cvt_pk_f32_fp8: exact
+    __device__ static inline float at(const uint8_t* p, int64_t i) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)p[i], false)[0]; }
+};
+
+// ---- any head dim (Dh % 8 == 0): one wave per (query row, query head, chunk of CHUNK slots), a key per lane ------------------------------------
+// Row b * Tn + i counts slot j iff j <= len0 + i and its mask byte is non-zero (a decode call: Tn = 1, len0 = len - 1).  Only a slot that counts is
+// read.  grid (rows, H, chunks) with ROWS_X, else (chunks, H, rows): each caller keeps the grid its entry point's limits were written for.
+template <typename T, typename F, int CHUNK, bool ROWS_X>
+__global__ __launch_bounds__(64) void attn_chunk_any_kernel(const T* __restrict__ q, int64_t ldq, F kv, const uint8_t* __restrict__ kmask,
+                                                            float* __restrict__ ws, int Tn, int H, int Hkv, int Dh, int cap, int len0, float scale) {
+    __shared__ float ps[CHUNK];
+    const int row = ROWS_X ? blockIdx.x : blockIdx.z;
+    const int h = blockIdx.y, c = ROWS_X ? blockIdx.z : blockIdx.x, nch = ROWS_X ? gridDim.z : gridDim.x, lane = threadIdx.x;
+    const int b = row / Tn, len = len0 + row % Tn + 1;                 // this row counts slots below len
+    const int hk = h / (H / Hkv), j0 = c * CHUNK;
+    const T* qr = q + (int64_t)row * ldq + (int64_t)h * Dh;
+    const int64_t rowbase = ((int64_t)b * Hkv + hk) * cap;
+    float mx = -INFINITY;
+    for (int jj = lane; jj < CHUNK; jj += 64) {
+        const int j = j0 + jj;
+        float sc = -INFINITY;
+        if (j < len && kmask[(int64_t)b * cap + j]) {
+            float a = 0.f;
+            for (int d = 0; d < Dh; ++d) a = fmaf((float)qr[d], F::at(kv.k, (rowbase + j) * Dh + d), a);
+            if constexpr (F::SCALED) sc = a * fp8w_scale(kv.ke[rowbase + j]) * scale;
+            else sc = a * scale;
+        }
+        ps[jj] = sc;
+        mx = fmaxf(mx, sc);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int jj = lane; jj < CHUNK; jj += 64) {
+        const float e = mx == -INFINITY ? 0.f : dec_exp<T>(ps[jj] - mx);
+        ps[jj] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();
+    float* part = ws + (((int64_t)row * H + h) * nch + c) * (Dh + 2);
+    if (lane == 0) { part[0] = mx; part[1] = sum; }
+    for (int d = lane; d < Dh; d += 64) {
+        float o = 0.f;
+        for (int jj = 0; jj < CHUNK; ++jj)
+            if (ps[jj] != 0.f) {                                       // (a non-zero weight: the slot counts for this row)
+                float pr = rnd<T>(ps[jj]);
+                if constexpr (F::SCALED) pr = pr * fp8w_scale(kv.ve[rowbase + j0 + jj]);
+                o = fmaf(pr, F::at(kv.v, (rowbase + j0 + jj) * Dh + d), o);
+            }
+        part[2 + d] = o;
+    }
 }
 
 // ---- merge: one workgroup per (sequence, query head), the chunks in chunk order ----------------------------------------------------------------

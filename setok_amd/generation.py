@@ -9,11 +9,23 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
 from . import ops
+
+
+@dataclass
+class _KVFormat:
+    """What differs between the cache formats, chosen once in `KVCache.__init__`: the per-layer tensor lists in the order both ops take them,
+    `append(qkv, *tensors, T, H, pos0)`, `attend(q, *tensors, key_mask, H, length, scale, ws=, out=)`, the decode attention's slots per partial,
+    and whether the format can be extended by several tokens (`extend_attend`, `grown`)."""
+    tensors: Tuple[List[torch.Tensor], ...]
+    append: Callable
+    attend: Callable
+    chunk: int
+    extendable: bool
 
 
 class KVCache:
@@ -23,8 +35,8 @@ class KVCache:
     slots are filled and masked).  Memory: 2 * layers * B * Hkv * cap * Dh elements.
 
     `kv_format="fp8"` stores a row as Dh e4m3fn bytes + one int8 power-of-two exponent instead (`k_q`, `v_q` (B, Hkv, cap, Dh) uint8 and `k_e`, `v_e`
-    (B, Hkv, cap) int8 per layer; `k` and `v` are then empty): 2 * layers * B * Hkv * cap * (Dh + 1) bytes.  `append` and `attend` are the
-    two calls that differ between the formats."""
+    (B, Hkv, cap) int8 per layer; `k` and `v` are then empty): 2 * layers * B * Hkv * cap * (Dh + 1) bytes.  What differs between the formats is
+    one `_KVFormat` record."""
 
     FORMATS = ("native", "fp8")
 
@@ -41,8 +53,10 @@ class KVCache:
             # a row is Dh e4m3fn bytes + one int8 exponent and means value(code) * 2^exponent (include/setok_hip.h, "FP8 KV cache")
             self.k_q, self.v_q = zeros((B, Hkv, cap, Dh), torch.uint8), zeros((B, Hkv, cap, Dh), torch.uint8)
             self.k_e, self.v_e = zeros((B, Hkv, cap), torch.int8), zeros((B, Hkv, cap), torch.int8)
+            self._fmt = _KVFormat((self.k_q, self.k_e, self.v_q, self.v_e), ops.kv_append_fp8, ops.attention_decode_fp8kv, ops.DECODE_CHUNK_FP8KV, False)
         else:
             self.k, self.v = zeros((B, Hkv, cap, Dh), dtype), zeros((B, Hkv, cap, Dh), dtype)
+            self._fmt = _KVFormat((self.k, self.v), ops.kv_append, ops.attention_decode, ops.DECODE_CHUNK, True)
         self.key_mask = torch.zeros((B, cap), dtype=torch.uint8, device=device)
         self.next_pos = torch.zeros(B, dtype=torch.int64, device=device)
         self.len = 0
@@ -56,29 +70,24 @@ class KVCache:
 
     def append(self, li: int, qkv: torch.Tensor, T: int, H: int, pos0: int) -> None:
         """Layer `li`: the post-rotary k / v columns of the fused qkv buffer -> slots [pos0, pos0 + T), in the cache's own format."""
-        if self.kv_format == "fp8":
-            ops.kv_append_fp8(qkv, self.k_q[li], self.k_e[li], self.v_q[li], self.v_e[li], T, H, pos0)
-        else:
-            ops.kv_append(qkv, self.k[li], self.v[li], T, H, pos0)
+        self._fmt.append(qkv, *(t[li] for t in self._fmt.tensors), T, H, pos0)
 
     def attend(self, li: int, q: torch.Tensor, H: int, length: int, scale: float, ws: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
         """Layer `li`: one query row per (sequence, query head) against slots [0, length), in the cache's own format."""
-        if self.kv_format == "fp8":
-            return ops.attention_decode_fp8kv(q, self.k_q[li], self.k_e[li], self.v_q[li], self.v_e[li], self.key_mask, H, length, scale, ws=ws, out=out)
-        return ops.attention_decode(q, self.k[li], self.v[li], self.key_mask, H, length, scale, ws=ws, out=out)
+        return self._fmt.attend(q, *(t[li] for t in self._fmt.tensors), self.key_mask, H, length, scale, ws=ws, out=out)
 
     def extend_attend(self, li: int, q: torch.Tensor, H: int, Tn: int, len0: int, scale: float, ws: torch.Tensor,
                       out: Optional[torch.Tensor]) -> torch.Tensor:
         """Layer `li`: Tn query rows per (sequence, query head) against slots [0, len0 + Tn), causal inside the new rows (ops.attention_extend).  The
         native format only: reading several query rows over e4m3 rows is a second kernel."""
-        if self.kv_format == "fp8":
+        if not self._fmt.extendable:
             raise NotImplementedError("KVCache.extend_attend: extending an fp8 KV cache by several tokens is not implemented (the extend attention "
                                       "over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
         return ops.attention_extend(q, self.k[li], self.v[li], self.key_mask, H, Tn, len0, scale, ws=ws, out=out)
 
     def grown(self, cap: int) -> "KVCache":
         """A cache of capacity `cap` >= self.len holding the same filled slots, mask and positions (`cap` is part of the layout, so growing copies)."""
-        if self.kv_format == "fp8":
+        if not self._fmt.extendable:
             raise NotImplementedError("KVCache.grown: an fp8 KV cache cannot be extended by several tokens, so it is never grown")
         if cap < self.len:
             raise ValueError(f"KVCache.grown: cap={cap} is below the {self.len} filled slots")
@@ -102,15 +111,12 @@ class KVCache:
         self.len = n
 
     def nbytes(self) -> int:
-        if self.kv_format == "fp8":                                    # codes + exponents
-            return sum(t.numel() * t.element_size() for t in self.k_q + self.k_e + self.v_q + self.v_e)
-        return sum(t.numel() * t.element_size() for t in self.k + self.v)
+        return sum(t.numel() * t.element_size() for layers in self._fmt.tensors for t in layers)
 
     def workspace(self, H: int, Tn: int = 0, len0: int = 0) -> torch.Tensor:
         """The attention's fp32 partials: the decode step's, sized once for the full capacity, or — with Tn > 0 — the larger of that and what an
         extend of Tn rows behind len0 slots needs."""
-        chunk = ops.DECODE_CHUNK_FP8KV if self.kv_format == "fp8" else ops.DECODE_CHUNK
-        need = ops.attention_decode_workspace(self.B, H, self.Dh, self.cap, chunk)
+        need = ops.attention_decode_workspace(self.B, H, self.Dh, self.cap, self._fmt.chunk)
         if Tn > 0:
             need = max(need, ops.attention_extend_workspace(self.B, Tn, H, self.Dh, len0, self.Hkv, self.dtype))
         if self._ws is None or self._ws.numel() < need:

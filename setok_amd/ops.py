@@ -781,17 +781,24 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tens
     q.stride(0) (the step's fused qkv buffer is read in place); key_mask (B, cap) uint8.  Returns (B, H*Dh)."""
     B, Hkv, cap, Dh = k_cache.shape
     assert v_cache.shape == k_cache.shape and k_cache.dtype == v_cache.dtype == q.dtype
+    return _attention_decode("setok_attention_decode_gqa", q, (_p(k_cache), _p(v_cache)), key_mask, B, H, Hkv, Dh, cap, length, scale, DECODE_CHUNK, ws, out)
+
+
+def _attention_decode(symbol: str, q: Tensor, cache_ptrs: tuple, key_mask: Tensor, B: int, H: int, Hkv: int, Dh: int, cap: int, length: int,
+                      scale: float, chunk: int, ws: Optional[Tensor], out: Optional[Tensor]) -> Tensor:
+    """What the decode attention over either cache format does once the cache's own operands are checked: `cache_ptrs` are the cache's
+    pointers in the order of `symbol`'s signature, `chunk` the format's slots per partial."""
     assert q.shape[0] == B and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
     assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, cap)
-    need = attention_decode_workspace(B, H, Dh, length)
+    need = attention_decode_workspace(B, H, Dh, length, chunk)
     if ws is None:
         ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
     assert ws.dtype == torch.float32 and ws.numel() >= need
     if out is None:
         out = torch.empty((B, H * Dh), dtype=q.dtype, device=q.device)
     assert out.shape == (B, H * Dh) and out.dtype == q.dtype
-    _lib.call("setok_attention_decode_gqa", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_cache), _p(v_cache), _p(key_mask), _p(out),
-              B, H, Hkv, Dh, cap, length, scale, _p(ws), ws.numel())
+    _lib.call(symbol, _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), *cache_ptrs, _p(key_mask), _p(out), B, H, Hkv, Dh, cap, length, scale,
+              _p(ws), ws.numel())
     return out
 
 
@@ -817,18 +824,8 @@ def attention_decode_fp8kv(q: Tensor, k_q: Tensor, k_e: Tensor, v_q: Tensor, v_e
                            ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """attention_decode over an fp8 cache (the keys / values are value(code) * 2^exponent, exactly); q and the result in q.dtype."""
     B, Hkv, cap, Dh = _fp8kv_shapes(k_q, k_e, v_q, v_e)
-    assert q.shape[0] == B and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
-    assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, cap)
-    need = attention_decode_workspace(B, H, Dh, length, DECODE_CHUNK_FP8KV)
-    if ws is None:
-        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
-    assert ws.dtype == torch.float32 and ws.numel() >= need
-    if out is None:
-        out = torch.empty((B, H * Dh), dtype=q.dtype, device=q.device)
-    assert out.shape == (B, H * Dh) and out.dtype == q.dtype
-    _lib.call("setok_attention_decode_gqa_fp8kv", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_q), _p(k_e), _p(v_q), _p(v_e),
-              _p(key_mask), _p(out), B, H, Hkv, Dh, cap, length, scale, _p(ws), ws.numel())
-    return out
+    return _attention_decode("setok_attention_decode_gqa_fp8kv", q, (_p(k_q), _p(k_e), _p(v_q), _p(v_e)), key_mask, B, H, Hkv, Dh, cap, length, scale,
+                             DECODE_CHUNK_FP8KV, ws, out)
 
 
 # ---- extending a cache by Tn tokens (csrc/attn_extend.hip) ---------------------------------------------------------------------------------------

@@ -110,7 +110,7 @@ def _check_attention(dt, H, Hkv, Dh, n, cap, seed, compare_native):
 
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("H,Hkv", [(2, 2), (4, 2), (8, 2), (4, 1), (8, 1)])
-@pytest.mark.parametrize("Dh", [16, 64, 128])
+@pytest.mark.parametrize("Dh", [16, 64, 128, 32])                      # 1, 4, 8 and 2 lanes per row
 def test_attention_decode_fp8kv_against_fp64_on_the_dequantised_cache(dt, H, Hkv, Dh):
     for n in LENS:
         _check_attention(dt, H, Hkv, Dh, n, n + 5, 100 + n, True)

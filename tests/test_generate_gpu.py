@@ -104,9 +104,16 @@ def _decode(qkv, k, v, mask, H, n, Dh):
     return ops.attention_decode(qkv.to(DEV), k.to(DEV), v.to(DEV), mask.to(DEV), H, n, Dh ** -0.5)
 
 
-@pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("H,Hkv", [(2, 2), (4, 2), (8, 2), (4, 1), (8, 1)])          # MHA, GQA G = 2 and 4, MQA (G = 4 and 8)
-@pytest.mark.parametrize("Dh", [16, 64, 128])
+def _decode_cases():
+    """Head dims 16, 64, 128 in every element type and head grouping (MHA, GQA G = 2 and 4, MQA G = 4 and 8), and the lane layouts those leave out:
+    head dims 8 and 32 in fp32 (2 and 8 lanes per row), 32 and 256 in the 16-bit types (4 and 32 lanes), each with one and eight query heads per
+    workgroup.  The ids are those of three stacked parametrisations (Dh, then H-Hkv, then dt)."""
+    cases = [(dt, H, Hkv, Dh) for Dh in (16, 64, 128) for H, Hkv in [(2, 2), (4, 2), (8, 2), (4, 1), (8, 1)] for dt in DTYPES]
+    cases += [(dt, H, Hkv, Dh) for dt in DTYPES for Dh in ((8, 32) if dt == torch.float32 else (32, 256)) for H, Hkv in [(2, 2), (8, 1)]]
+    return [pytest.param(dt, H, Hkv, Dh, id=f"{Dh}-{H}-{Hkv}-dt{DTYPES.index(dt)}") for dt, H, Hkv, Dh in cases]
+
+
+@pytest.mark.parametrize("dt,H,Hkv,Dh", _decode_cases())
 def test_attention_decode_against_fp64(dt, H, Hkv, Dh):
     tol = _tol(dt, Dh)
     for n in LENS:
