@@ -7,7 +7,11 @@ rounds q, k, v to the element type and computes every reference from the rounded
 the offsets then scale by that factor on the kernel's side and on the reference's alike).
 
 `walk` replays the tile walk of attn_vit_kernel (setok_amd/csrc/attn_vit.hip) in fp32 and counts what the inputs make it do; `emulate` is the same
-walk producing an output, with the roundings of the 16-bit kernel: the bound a test asserts on the GPU is first shown attainable here."""
+walk producing an output, with the roundings of the 16-bit kernel: the bound a test asserts on the GPU is first shown attainable here.
+
+`build_cache` is `build` for a (queries, cached keys) problem — the extend and decode kernels — and `emulate_chunked` the per-row replay of their
+chunked walk (setok_amd/csrc/attn_extend.hip, attn_decode.hip, attn_partials.h): an online softmax over key tiles inside a span, one fp32 partial per
+span, the merge of attn_decode_merge_kernel.  It also reports the smallest factors the inputs make the walk apply."""
 import math
 from typing import List, NamedTuple
 
@@ -150,3 +154,76 @@ def emulate(q, k, v, scale, dt, tile: int = 32, defer_nats: float = DEFER_NATS):
         _walk_tile(s, s.shape[0], tile, defer_raw, c, step)
         out[q0:q0 + 32] = (o * (1.0 / l_run)[:, None]).to(dt)
     return out
+
+
+# ---- cached keys: the extend and decode kernels -------------------------------------------------------------------------------------------------
+NEG = -1.0e30                                      # attn_extend.hip's finite sentinel of a slot that does not count
+LN2 = 0.69314718055994530942
+FAULTS = ("no_rescale", "log2_max")                # planted errors of emulate_chunked (tests/test_cache_attn_programs_cpu.py); never in a kernel
+
+
+def build_cache(Tq: int, n: int, Dh: int, G: int, program: str, seed: int, tile: int = 32):
+    """(q (Tq, G, Dh), k (n, Dh), v (n, Dh)), fp32: one key / value head of a cache of n slots and the G query heads it serves, Tq query rows each.
+    Steered through dimension 0 as `build` does: q[..., 0] = sqrt(Dh), k[:, 0] = offsets(n, program, tile)."""
+    g = torch.Generator().manual_seed(seed)
+    q = 0.5 * torch.randn(Tq, G, Dh, generator=g)
+    k = 0.5 * torch.randn(n, Dh, generator=g)
+    v = torch.randn(n, Dh, generator=g)
+    q[..., 0] = math.sqrt(Dh)
+    k[:, 0] = offsets(n, program, tile)
+    return q, k, v
+
+
+def _dec_exp(x, dt):
+    """attn_partials.h's dec_exp: expf in fp32, v_exp_f32 of x log2(e) in the 16-bit types."""
+    return torch.exp(x) if dt == torch.float32 else torch.exp2(x * LOG2E)
+
+
+def emulate_chunked(q, k, v, counts, scale, dt, span: int, tile: int = 32, fault: str = None):
+    """Per-row replay of the chunked walk with the kernel's roundings.  q (..., R, Dh), k and v (..., n, Dh), counts (..., R, n) bool: row r counts
+    slot j.  fp32 scores of the `dt` inputs in log2 units; a slot that does not count is replaced by the -1e30 sentinel BY SELECTION (its K row may
+    be NaN) and a V row that counts for no row is zeroed; the online maximum, sum and accumulators run over `tile`-key tiles inside each span of
+    `span` slots; P is rounded to `dt` for the PV product, the sum is taken over the unrounded values; a span's partial is (m ln2, l, o), or
+    (-inf, 0, 0) for a row that counted nothing in it; the merge runs in span order by the rule of attn_decode_merge_kernel.  tile = span is one
+    softmax per chunk: the generic kernel, and a decode kernel's chunk when its wave slices are not modelled.
+    Returns (out (..., R, Dh) in `dt`, the smallest rescale factor applied inside a span to a row that had counted a key, the smallest merge
+    factor applied to a partial that had) — 1.0 where none was applied.  `fault` plants one error: "no_rescale" leaves the accumulators
+    unscaled when the maximum moves, "log2_max" leaves the partial's maximum in log2 units."""
+    assert fault is None or fault in FAULTS
+    q, k, v = q.to(dt).float(), k.to(dt).float(), v.to(dt).float()
+    n = k.shape[-2]
+    t = torch.where(counts, (q @ k.transpose(-1, -2)) * (scale * LOG2E), torch.full((), NEG))
+    v = torch.where(counts.any(-2)[..., None], v, torch.zeros(()))
+    rows = t.shape[:-1]
+    min_rescale = min_merge = 1.0
+    parts = []
+    for s0 in range(0, n, span):
+        m_run, l_run, o = torch.full(rows, NEG), torch.zeros(rows), torch.zeros(rows + (v.shape[-1],))
+        for k0 in range(s0, min(n, s0 + span), tile):
+            tt = t[..., k0:k0 + tile]
+            m_new = torch.maximum(m_run, tt.amax(-1))
+            alpha = torch.exp2(m_run - m_new)
+            moved = (m_run > NEG) & (m_new > m_run)
+            if bool(moved.any()):
+                min_rescale = min(min_rescale, float(alpha[moved].min()))
+            l_run = l_run * alpha
+            if fault != "no_rescale":
+                o = o * alpha[..., None]
+            m_run = m_new
+            p = torch.where(tt <= NEG, torch.zeros(()), torch.exp2(tt - m_run[..., None]))
+            l_run = l_run + p.sum(-1)
+            o = o + p.to(dt).float() @ v[..., k0:k0 + tile, :]
+        some = m_run > NEG
+        mc = torch.where(some, m_run * (1.0 if fault == "log2_max" else LN2), torch.full((), -math.inf))
+        parts.append((mc, torch.where(some, l_run, torch.zeros(())), torch.where(some[..., None], o, torch.zeros(()))))
+    M = torch.stack([mc for mc, _, _ in parts]).amax(0)
+    L, O = torch.zeros(rows), torch.zeros(rows + (v.shape[-1],))
+    for mc, l, o in parts:
+        some = mc > -math.inf
+        f = torch.where(some, _dec_exp(mc - M, dt), torch.zeros(()))
+        if bool(some.any()):
+            min_merge = min(min_merge, float(f[some].min()))
+        L = L + f * l
+        O = O + f[..., None] * o
+    inv = torch.where(L > 0, 1.0 / L, torch.zeros(()))
+    return (O * inv[..., None]).to(dt), min_rescale, min_merge
