@@ -643,6 +643,66 @@ int setok_spec_accept(void* stream, const int64_t* draft, const int64_t* sel, in
 int setok_ngram_propose(void* stream, int64_t* hist, int32_t* hist_len, int B, int cap_h, int len_max, const int64_t* emitted, const int32_t* m,
                         int n_emit, int K, int max_ngram, int min_ngram, int64_t* out);
 
+/* ---- Beam search (csrc/beam.hip): HuggingFace's `GenerationMixin._beam_search` with do_sample=False and no logits processors, over B sequences of
+ * n = num_beams running beams each (flat row b * n + i), the cache and the decode step running on B * n rows.  Pure addition: the ABI stays 9.
+ *
+ * The rule, per step `step` = 0, 1, .. (the step selects new token number step + 1), with C = max(2, 1 + n_eos) * n:
+ *   1. the logits are taken as fp32, acc[j][v] = running[b][j] + log_softmax(row j)[v] in fp32, and the C largest acc of the sequence's n_in * V
+ *      candidates are kept in descending order (setok_beam_topk).  Step 0 has n_in = 1: the prefill ran on B rows, the one row's running score is
+ *      0 - HF replicates the prompt n times and starts beams 1 .. n - 1 at -1e9, which selects the same candidates as long as V >= C.
+ *   2. candidate c "hits" when its token is an eos id or step + 1 == max_new.
+ *   3. the next running beams are the n best candidates by acc + hit * -1e9; running beam i gets that score, the candidate's token, and the
+ *      candidate's beam as its parent.
+ *   4. the finished set holds n entries (score, finished?), initially (-1e9, no).  A candidate's entry score is
+ *        acc / (step + 1) ** length_penalty  + (-1e9 if the set is full - all n finished - and early_stopping is True)
+ *                                            + (-1e9 if the sequence's heuristic flag is already down)  + (-1e9 unless it hits and c < n),
+ *      one fp32 addition each; its finished? bit is (hits and c < n).  The n best of (old entries, then candidates) form the new set.
+ *   5. the heuristic flag (initially up) stays up while  running[0] / L ** length_penalty  >  (-1e9 for an entry that is not finished, the set's
+ *      minimum score for one that is)  holds for some entry, with L = max_new when early_stopping is "never" and length_penalty > 0, else step + 1.
+ *   6. the loop continues while some sequence's flag is up, and not (every entry of every sequence is finished and early_stopping is True), and
+ *      not every candidate of every sequence hit.
+ *   `x ** length_penalty` is Python's `int ** float`: a double power of the double length_penalty, rounded once to fp32 where the fp32 tensor is divided by it.  Every selection
+ *   is by (value descending, index ascending), a total order; the fixtures keep every ordering the result depends on 1e-3 apart.
+ *   At the end the entries of each sequence's finished set are its hypotheses in descending score.  A hypothesis is kept as back-pointers: per
+ *   step the token and the parent of every running beam; a finished entry is (score, length, parent, last token).
+ *
+ * setok_beam_topk - step 1 of the rule.  logits: B * n_in rows of V columns, row stride ld elements, dtype = the build's 16-bit type or fp32; running
+ *   (B, n_in) fp32.  Outputs cand_score (B, C) fp32, cand_token (B, C) int64, cand_beam (B, C) int32 (the j of the row), descending, ties to the lower
+ *   flat index j * V + v; status (B) int32 = 1 iff a row of the sequence holds a NaN or +inf or no finite entry (such a row contributes no candidate;
+ *   the other sequences are not affected), else 0.  -inf entries are legal and lose against every finite one.  ws: B * n_in * 516 bytes.
+ *   Two launches: one workgroup of 1024 threads per row finds the row's maximum, sums exp(x - max) - every thread over the elements
+ *   [(k * 1024 + t) * VEC, + VEC) in order of k, then the wave butterfly, then the 16 waves in order: the order depends on V alone - and keeps the row's
+ *   best 64 acc (every wave a sorted list, one entry per lane; an entry's rank among the 16 lists is its place in its own plus a binary search in each other one); one workgroup per sequence then merges its n_in lists the same way.  No
+ *   atomics; a sequence's result is the same bits alone and inside any batch.  Refused: a null operand, B < 0, n_in outside [1, 16], V outside
+ *   [1, 2^20], ld < V, C outside [1, 64] or > n_in * V ("bad C"), another dtype, a workspace that is too small.
+ *
+ * setok_beam_advance - steps 2 to 6, one launch of one workgroup, one wave per sequence (looping above 16).  eos (n_eos) int64 (NULL with n_eos == 0);
+ *   topk_status (B) int32 is setok_beam_topk's.  early_stopping: 0 False, 1 True, 2 "never".  State, updated in place: run_score (B, n) fp32;
+ *   fin_score (B, n) fp32, fin_flag (B, n) uint8, fin_len (B, n) int32 (new tokens), fin_parent (B, n) int32 (the running beam of the step before
+ *   that the entry's last token was selected from) and fin_token (B, n) int64; heur (B) uint8.  The caller initialises fin_score to -1e9, heur to 1 and
+ *   everything else to 0.  bp_token (max_new, B * n) int64 and bp_parent (max_new, B * n) int32 receive row `step`.  Outputs next_token (B * n) int64,
+ *   src_row (B * n) int32 = b * n + parent (what setok_kv_reorder takes), summary (2) int32 = { 1 iff the loop continues, 1 iff a status is set }.
+ *   Refused: a null operand, B < 0, n outside [1, 16], C outside [n, 64] ("bad C"), n_eos < 0, step outside [0, max_new), a non-finite
+ *   length_penalty, early_stopping outside {0, 1, 2}.
+ *
+ * setok_kv_reorder - for each of n_tensors cache tensors (rows, Hkv, cap, row_bytes[t] bytes), slots [slot0, slot1) of row r become what row
+ *   src_row[r] held before the call.  ptrs (n_tensors) device pointers, row_bytes (n_tensors) int32 and scratch_unit (n_tensors) int64 - the sum of
+ *   row_bytes rounded up to 16 over the tensors before t - are DEVICE tables built once per cache; unit_total is that sum over all tensors.  Two
+ *   launches whatever the number of tensors: every (tensor, row, head) gathers its source's ns = slot1 - slot0 slots into the scratch
+ *   (unit_total * rows * Hkv * ns bytes, 16-byte aligned), then copies them back, so any mapping inside a group is safe, several rows taking one
+ *   parent included.  A row with src_row[r] == r moves nothing.  A src_row[r] outside r's own group [r / n * n, r / n * n + n) counts as r and sets
+ *   status[r] = 1 (status (rows) int32 is otherwise left as it is: the caller zeroes it once).  Refused: a null operand, n_tensors outside
+ *   [1, 65535], rows % n != 0, slots outside [0, cap], a scratch that is too small or misaligned. */
+int setok_beam_topk(void* stream, int dtype, const void* logits, int64_t ld, int B, int n_in, int V, const float* running, int C,
+                    float* cand_score, int64_t* cand_token, int32_t* cand_beam, int32_t* status, void* ws, int64_t ws_bytes);
+int setok_beam_advance(void* stream, const float* cand_score, const int64_t* cand_token, const int32_t* cand_beam, const int32_t* topk_status,
+                       int B, int n, int C, const int64_t* eos, int n_eos, int step, int max_new, double length_penalty, int early_stopping,
+                       float* run_score, float* fin_score, uint8_t* fin_flag, int32_t* fin_len, int32_t* fin_parent, int64_t* fin_token,
+                       uint8_t* heur, int64_t* bp_token, int32_t* bp_parent, int64_t* next_token, int32_t* src_row, int32_t* summary);
+int setok_kv_reorder(void* stream, const void* const* ptrs, const int32_t* row_bytes, const int64_t* scratch_unit, int n_tensors,
+                     int64_t unit_total, int rows, int n, int Hkv, int cap, int slot0, int slot1, const int32_t* src_row, void* scratch,
+                     int64_t scratch_bytes, int32_t* status);
+
 /* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip; the M <= 64 GEMM it shares with MXFP4: csrc/wstream.h): the decode step streams every projection weight once per token, so the stack's Linear
  * weights may be STORED as OCP e4m3fn bytes with one power-of-two scale per output row.  A matrix W (N, K) becomes q (N, K) uint8 + e (N,) int8 and
  * means exactly

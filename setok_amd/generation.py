@@ -4,7 +4,8 @@ keeps between steps as HF's `past_key_values` (:99,133,189), and what it returns
 `KVCache` is allocated once per `generate` call; `LlamaModel.prefill` fills slots [0, T') of every layer, every `LlamaModel.decode_step` appends
 one slot for all sequences, `LlamaModel.extend` appends Tn >= 1 slots (chunked prefill, the next turn of a conversation).  The loop itself is
 `SetokimLlamaPrefill.generate` (llama.py); `GenerationState` is what it hands back so that a later call can continue from the same cache.
-`Drafter` / `LookupDrafter` are the sources of proposals for `generate(draft=...)`, which verifies K drafted tokens per `extend`."""
+`Drafter` / `LookupDrafter` are the sources of proposals for `generate(draft=...)`, which verifies K drafted tokens per `extend`.  `BeamSearch` is the
+setting of `generate(beams=...)`, which decodes on `KVCache.expanded(num_beams)` and re-points the beams' slots with `KVCache.reorder` every step."""
 from __future__ import annotations
 
 import math
@@ -61,6 +62,7 @@ class KVCache:
         self.next_pos = torch.zeros(B, dtype=torch.int64, device=device)
         self.len = 0
         self._ws: Optional[torch.Tensor] = None
+        self._plan = None                                                          # ops.KVReorderPlan of the first `reorder`
 
     @classmethod
     def for_model(cls, model, B: int, cap: int, device=None, kv_format: str = "native") -> "KVCache":
@@ -109,6 +111,29 @@ class KVCache:
         if n < self.len:
             self.key_mask[:, n:self.len] = 0
         self.len = n
+
+    def expanded(self, n: int) -> "KVCache":
+        """A cache of B * n rows whose row b * n + j copies row b (filled slots, mask, positions): what beam search decodes on.  A torch copy, once
+        per `generate` call; the format and the capacity stay."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"KVCache.expanded: n={n!r} must be an int >= 1")
+        new = KVCache(self.num_layers, self.B * n, self.Hkv, self.cap, self.Dh, self.dtype, self.key_mask.device, self.kv_format)
+        L = self.len
+        for dst, src in zip(new._fmt.tensors, self._fmt.tensors):
+            for d, t in zip(dst, src):
+                d[:, :, :L].copy_(t[:, :, :L].repeat_interleave(n, dim=0))
+        new.key_mask.copy_(self.key_mask.repeat_interleave(n, dim=0))
+        new.next_pos.copy_(self.next_pos.repeat_interleave(n, dim=0))
+        new.len = L
+        return new
+
+    def reorder(self, src_row: torch.Tensor, slot0: int, n: int) -> torch.Tensor:
+        """Slots [slot0, len) of row r of every tensor of every layer become what row src_row[r] held (src_row (self.B,) int32, inside r's own group of n
+        rows): two launches for the whole cache (ops.kv_reorder).  The slots below slot0 - the prompt, identical across a sequence's beams - never
+        move; mask and positions are shared by a group.  Returns the sticky (B,) int32 status: 1 where a src_row was outside its group."""
+        if self._plan is None or self._plan.n != n:
+            self._plan = ops.KVReorderPlan([t for layers in self._fmt.tensors for t in layers], n)
+        return ops.kv_reorder(self._plan, src_row, slot0, self.len, reserve=self.cap - slot0)
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for layers in self._fmt.tensors for t in layers)
@@ -179,6 +204,34 @@ class Sampler:
         return ops.sample_rows(logits, self.uniforms(step, logits.shape[0], logits.device), self.temperature, self.top_k, self.top_p)
 
 
+class BeamSearch:
+    """Beam search for `SetokimLlamaPrefill.generate(beams=...)`: HF's `num_beams`, `length_penalty`, `early_stopping` (False, True or "never") and
+    `num_return_sequences` with HF's meaning (include/setok_hip.h, "Beam search", states the rule).  The arguments are validated here and raise
+    ValueError; what depends on the call - C = max(2, 1 + n_eos) * num_beams <= 64 and V >= C - is checked by `candidates`."""
+
+    def __init__(self, num_beams: int, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1):
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= ops.BEAM_MAX_N:
+            raise ValueError(f"BeamSearch: num_beams={num_beams!r} must be an int in [1, {ops.BEAM_MAX_N}]")
+        if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= num_beams:
+            raise ValueError(f"BeamSearch: num_return_sequences={num_return_sequences!r} must be an int in [1, num_beams] = [1, {num_beams}]")
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
+            raise ValueError(f"BeamSearch: length_penalty={length_penalty!r} must be a finite number")
+        if not (isinstance(early_stopping, bool) or (isinstance(early_stopping, str) and early_stopping == "never")):
+            raise ValueError(f"BeamSearch: early_stopping={early_stopping!r} is not one of False, True, 'never'")
+        self.num_beams, self.length_penalty = num_beams, float(length_penalty)
+        self.early_stopping, self.num_return_sequences = early_stopping, num_return_sequences
+
+    def candidates(self, n_eos: int, V: int) -> int:
+        """C, the candidates kept per sequence and step; ValueError when one wave cannot hold them or the vocabulary cannot supply them."""
+        C = max(2, 1 + n_eos) * self.num_beams
+        if C > ops.BEAM_MAX_C:
+            raise ValueError(f"BeamSearch: C = max(2, 1 + n_eos) * num_beams = {C} candidates per sequence exceed {ops.BEAM_MAX_C} "
+                             f"({n_eos} eos ids, {self.num_beams} beams)")
+        if V < C:
+            raise ValueError(f"BeamSearch: the vocabulary (V = {V}) is smaller than the C = {C} candidates a step keeps")
+        return C
+
+
 @dataclass
 class GenerationState:
     """What `generate(return_past=True)` hands back and `generate(past=...)` continues from: the `KVCache` and `pending` (B,) int64 — the last real
@@ -194,11 +247,15 @@ class GenerationState:
 class GenerateOutput:
     """`generate(return_dict_in_generate=True)`: sequences (B, n_new) int64 — the NEW tokens only; hidden_states (B, n_new, D): row j is the final-norm
     state that produced token j (what the reference collects as `x[-1]` per step, setokim_llama.py:363, for its image head); logits (B, n_new, V)
-    when requested; past (a GenerationState) with `return_past`."""
+    when requested; past (a GenerationState) with `return_past`.  With `beams=` the rows are the B * num_return_sequences hypotheses, row b * R + r in
+    descending score: sequences_scores (B * R,) float32 and beam_indices (B * R, n_new) int32 - entry [r, j] is the flat row b * num_beams + beam
+    whose state produced token j, -1 past the hypothesis' end (HF's meaning) -; hidden_states and logits follow that ancestry, zeros past the end."""
     sequences: torch.Tensor
     hidden_states: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
     past: Optional[GenerationState] = None
+    sequences_scores: Optional[torch.Tensor] = None
+    beam_indices: Optional[torch.Tensor] = None
 
 
 class Drafter:

@@ -651,7 +651,7 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
                  eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
                  output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", sampler=None, prefill_chunk: Optional[int] = None,
-                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, draft=None, **unsupported):
+                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, draft=None, beams=None, **unsupported):
         """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
         the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
         embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
@@ -696,11 +696,23 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         each sequence's last emitted one, an eos included).  Refused before any device call: a `draft` that is no Drafter (TypeError), a `draft.K`
         outside [1, 63] (ValueError), `kv_cache="fp8"` with a draft (NotImplementedError: `extend` refuses that cache).  `draft=None` is the plain loop.
 
+        `beams=` (a generation.BeamSearch(num_beams, length_penalty, early_stopping, num_return_sequences)) runs HF's beam search
+        (include/setok_hip.h, "Beam search", states the rule): after the prefill on B rows the cache is replicated to B * num_beams rows
+        (`KVCache.expanded`) and a step is lm_head on those rows, `setok_beam_topk` (the C = max(2, 1 + n_eos) * num_beams best accumulated
+        log-probabilities per sequence), `setok_beam_advance` (running beams, finished set, stop test; its 2-int summary is the step's one host
+        read), `KVCache.reorder` (every beam's generated slots become its parent's, two launches for the whole cache), the new ids' embedding rows
+        and `decode_step`.  Returns (B * R, n_new) int64, R = num_return_sequences: rows b * R + r in descending score, cropped to the longest returned
+        hypothesis, shorter ones padded with `pad_token_id` (default: the first eos id).  `GenerateOutput` then carries `sequences_scores`,
+        `beam_indices`, and hidden_states / logits gathered along each hypothesis' ancestry.  `prefill_chunk=` and `kv_cache="fp8"` work as in the
+        plain loop (a step appends one slot).  Refused before any device call: a `beams` that is no BeamSearch (TypeError); C > 64 or V < C
+        (ValueError); `beams=` with `sampler=`, `draft=`, `past=` or `return_past=True` (NotImplementedError: beam sampling and continuing a beam
+        state are not built).  `beams=None` is the plain loop bit for bit.
+
         HF's own spelling stays refused: `do_sample=True`, temperature= / top_p= / top_k= or beams raise NotImplementedError (the reference's
         defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here: pass a
         `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
-        from .generation import Drafter, GenerateOutput, GenerationState, KVCache, Sampler
+        from .generation import BeamSearch, Drafter, GenerateOutput, GenerationState, KVCache, Sampler
         self.model._refuse_unmerged("SetokimLlamaPrefill.generate")
         sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
         if do_sample or sampling:
@@ -729,6 +741,17 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             if kv_cache == "fp8":
                 raise NotImplementedError("SetokimLlamaPrefill.generate: draft= with kv_cache='fp8' is not implemented (a round extends the cache by "
                                           "K + 1 tokens, and the extend attention over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
+        C = 0
+        if beams is not None:
+            if not isinstance(beams, BeamSearch):
+                raise TypeError(f"SetokimLlamaPrefill.generate: beams must be a generation.BeamSearch or None, got {type(beams).__name__}")
+            for name, given in (("sampler=", sampler is not None), ("draft=", draft is not None), ("past=", past is not None),
+                                ("return_past=True", bool(return_past))):
+                if given:
+                    raise NotImplementedError(f"SetokimLlamaPrefill.generate: beams= with {name} is not implemented (beam sampling, drafting "
+                                              "into beams and continuing a beam state are not built)")
+            n_eos = 0 if eos_token_id is None else 1 if isinstance(eos_token_id, int) else len(list(eos_token_id))
+            C = beams.candidates(n_eos, self.lm_head.weight.shape[0])
         for name, v in (("prefill_chunk", prefill_chunk), ("cache_capacity", cache_capacity)):
             if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
                 raise ValueError(f"SetokimLlamaPrefill.generate: {name}={v!r} must be an integer >= 1 (or None)")
@@ -810,6 +833,9 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                 last = (amw.bool() * torch.arange(c1 - c0, device=dev)[None]).max(dim=1).values
                 hw = hidden[torch.arange(B, device=dev), last]
                 h = hw.contiguous() if h is None else torch.where(amw.bool().any(dim=1)[:, None], hw, h)
+        if beams is not None:
+            return self._generate_beams(beams, C, h, cache, max_new_tokens, eos, (pad if eos is not None else int(pad_token_id or 0)),
+                                        return_dict_in_generate, output_hidden_states, output_logits)
         if draft is not None:
             return self._generate_speculative(draft, h, cache, inputs, attention_mask, max_new_tokens, eos, pad if eos is not None else 0, sampler,
                                               return_dict_in_generate, output_hidden_states, output_logits, return_past)
@@ -862,6 +888,65 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             state = GenerationState(cache=cache, pending=torch.where(real == n, seq[:, -1], torch.full_like(real, -1)))
         return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if output_hidden_states else None,
                               logits=torch.stack(lgs, dim=1) if output_logits else None, past=state)
+
+    def _generate_beams(self, beams, C, h, cache, max_new, eos, pad, as_dict, want_hidden, want_logits):
+        """generate()'s loop with beam search, from the last attended state `h` (B, D) on.  The running scores, the finished set and the back-pointers
+        live on the device (ops.BeamState); the host reads `setok_beam_advance`'s 2-int summary once per step, and the hypotheses are materialised
+        from the back-pointers once at the end."""
+        from .generation import GenerateOutput
+        B, D = h.shape
+        n, R, dev = beams.num_beams, beams.num_return_sequences, h.device
+        w_lm = self.lm_head.weight.detach().contiguous()
+        w_e = self.model.embed_tokens.weight.detach().contiguous()
+        state = ops.BeamState(B, n, max_new, dev)
+        cache = cache.expanded(n)
+        fed0 = cache.len                                                           # the first slot a decode step of this call fills: what `reorder` moves starts here
+        running0 = torch.zeros((B, 1), dtype=torch.float32, device=dev)            # step 0: one row per sequence, score 0
+        ws = torch.empty(B * n * (2 * ops.BEAM_MAX_C + 1), dtype=torch.int32, device=dev)
+        hids, lgs = [], []
+        for step in range(max_new):
+            logits = ops.linear(h, w_lm)                                           # (B, V) at step 0, then (B * n, V)
+            cand = ops.beam_topk(logits, running0 if step == 0 else state.run_score, C, ws)
+            tok, src_row, summary = ops.beam_advance(*cand, state, eos, step, beams.length_penalty, beams.early_stopping)
+            if want_hidden:
+                hids.append(h.repeat_interleave(n, dim=0) if step == 0 else h)
+            if want_logits:
+                lgs.append(logits.repeat_interleave(n, dim=0) if step == 0 else logits)
+            go_on, bad = summary.tolist()                                          # the step's one host read
+            if bad:
+                rows = torch.nonzero(cand[3]).flatten().tolist()
+                raise RuntimeError(f"SetokimLlamaPrefill.generate: the logits of sequence(s) {rows} hold a NaN or +inf at beam-search step {step}")
+            if not go_on:
+                break
+            cache.reorder(src_row, fed0, n)
+            e = ops.splice_rows(tok.to(torch.int32).reshape(B * n, 1), w_e, None)
+            h = self.model.decode_step(e.reshape(B * n, D), cache)
+        # the returned hypotheses: the first R entries of every finished set, walked back through the parents
+        length = state.fin_len[:, :R].reshape(B * R).long().clamp_min(1)
+        beam = state.fin_parent[:, :R].reshape(B * R).long()
+        n_new = int(length.max())
+        base = (torch.arange(B, device=dev) * n).repeat_interleave(R)
+        rows = torch.arange(B * R, device=dev)
+        seq = torch.full((B * R, n_new), pad, dtype=torch.int64, device=dev)
+        anc = torch.full((B * R, n_new), -1, dtype=torch.int64, device=dev)
+        seq[rows, length - 1] = state.fin_token[:, :R].reshape(B * R)
+        anc[rows, length - 1] = base + beam
+        for j in range(n_new - 2, -1, -1):
+            live = j <= length - 2                                                 # token j of these hypotheses belongs to running beam `beam` after step j
+            at = base + beam
+            parent = state.bp_parent[j][at].long()
+            seq[:, j] = torch.where(live, state.bp_token[j][at], seq[:, j])
+            anc[:, j] = torch.where(live, base + parent, anc[:, j])
+            beam = torch.where(live, parent, beam)
+        if not as_dict:
+            return seq
+
+        def along(kept):                                                           # (steps, B * n, X) -> (B * R, n_new, X): row j from the state that produced token j
+            got = torch.stack(kept[:n_new], dim=0)[torch.arange(n_new, device=dev)[None], anc.clamp_min(0)]
+            return got * (anc >= 0)[..., None].to(got.dtype)
+
+        return GenerateOutput(sequences=seq, hidden_states=along(hids) if want_hidden else None, logits=along(lgs) if want_logits else None,
+                              sequences_scores=state.fin_score[:, :R].reshape(B * R).clone(), beam_indices=anc.to(torch.int32))
 
     def _generate_speculative(self, draft, h, cache, prompt_ids, prompt_mask, max_new, eos, pad, sampler, as_dict, want_hidden, want_logits, want_past):
         """generate()'s loop with a drafter, from the last attended state `h` (B, D) on.  Between rounds the state lives on the device: pending

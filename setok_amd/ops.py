@@ -969,6 +969,131 @@ def ngram_propose(hist: Tensor, hist_len: Tensor, K: int, len_max: int, emitted:
     return out
 
 
+# ---- beam search (csrc/beam.hip) -----------------------------------------------------------------------------------------------------------------
+BEAM_MAX_C = 64                                   # candidates per sequence: C = max(2, 1 + n_eos) * num_beams
+BEAM_MAX_N = 16                                   # beams per sequence
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}  # setok_beam_advance's code of HF's early_stopping
+
+
+def beam_topk(logits: Tensor, running: Tensor, C: int, ws: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Per sequence, the C largest of running[b][j] + log_softmax(row j)[v] over its n_in rows (include/setok_hip.h, "Beam search"): logits
+    (B * n_in, V) with any row stride, running (B, n_in) fp32 -> (cand_score (B, C) fp32, cand_token (B, C) int64, cand_beam (B, C) int32,
+    status (B,) int32 = 1 where a row of the sequence holds a NaN or +inf), descending, ties to the lower flat index j * V + v."""
+    if logits.dim() != 2 or running.dim() != 2 or running.shape[0] * running.shape[1] != logits.shape[0]:
+        raise ValueError(f"beam_topk: logits must be (B * n_in, V) and running (B, n_in), got {tuple(logits.shape)} and {tuple(running.shape)}")
+    (B, n_in), V = running.shape, logits.shape[1]
+    if isinstance(C, bool) or not isinstance(C, int) or not 1 <= C <= BEAM_MAX_C or C > n_in * V:
+        raise ValueError(f"beam_topk: C={C!r} must be an int in [1, {BEAM_MAX_C}] and at most n_in * V = {n_in * V}")
+    if not 1 <= n_in <= BEAM_MAX_N:
+        raise ValueError(f"beam_topk: n_in={n_in} is outside [1, {BEAM_MAX_N}]")
+    assert logits.stride(1) == 1 and logits.is_cuda
+    _i(running, torch.float32, (B, n_in), "beam_topk: running")
+    dev = logits.device
+    need = B * n_in * (BEAM_MAX_C * 2 + 1)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.int32, device=dev)
+    assert ws.dtype == torch.int32 and ws.is_cuda and ws.is_contiguous()
+    score = torch.empty((B, C), dtype=torch.float32, device=dev)
+    token = torch.empty((B, C), dtype=torch.int64, device=dev)
+    beam = torch.empty((B, C), dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    rows = B * n_in
+    _lib.call("setok_beam_topk", _stream(), _code(logits.dtype), logits.data_ptr(), logits.stride(0) if rows > 1 else max(logits.stride(0), V), B, n_in, V,
+              running.data_ptr(), C, score.data_ptr(), token.data_ptr(), beam.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4)
+    return score, token, beam, status
+
+
+class BeamState:
+    """The device-resident state of `setok_beam_advance` for B sequences of n beams over at most max_new steps (include/setok_hip.h, "Beam search")."""
+
+    def __init__(self, B: int, n: int, max_new: int, device):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.B, self.n, self.max_new = B, n, max_new
+        self.run_score = z((B, n), torch.float32)
+        self.fin_score = torch.full((B, n), -1.0e9, dtype=torch.float32, device=device)
+        self.fin_flag, self.fin_len, self.fin_parent, self.fin_token = z((B, n), torch.uint8), z((B, n), torch.int32), z((B, n), torch.int32), z((B, n), torch.int64)
+        self.heur = torch.ones(B, dtype=torch.uint8, device=device)
+        self.bp_token, self.bp_parent = z((max_new, B * n), torch.int64), z((max_new, B * n), torch.int32)
+        self.next_token, self.src_row, self.summary = z(B * n, torch.int64), z(B * n, torch.int32), z(2, torch.int32)
+
+
+def beam_advance(score: Tensor, token: Tensor, beam: Tensor, status: Tensor, state: BeamState, eos: Optional[Tensor], step: int,
+                 length_penalty: float = 1.0, early_stopping=False) -> Tuple[Tensor, Tensor, Tensor]:
+    """One step of HF's beam bookkeeping on the candidates of `beam_topk` (include/setok_hip.h, "Beam search"), one launch: `state` is updated in
+    place; returns (next_token (B * n,) int64, src_row (B * n,) int32, summary (2,) int32 = {continue, bad row}) - views of the state."""
+    B, n = state.B, state.n
+    if score.dim() != 2:
+        raise ValueError(f"beam_advance: the candidates must be (B, C), got {tuple(score.shape)}")
+    C = score.shape[1]
+    if not n <= C <= BEAM_MAX_C:
+        raise ValueError(f"beam_advance: C={C} is outside [n, {BEAM_MAX_C}] = [{n}, {BEAM_MAX_C}]")
+    if not (isinstance(early_stopping, bool) or (isinstance(early_stopping, str) and early_stopping == "never")):
+        raise ValueError(f"beam_advance: early_stopping={early_stopping!r} is not one of False, True, 'never'")
+    if not 0 <= step < state.max_new:
+        raise ValueError(f"beam_advance: step {step} is outside [0, max_new = {state.max_new})")
+    _i(score, torch.float32, (B, C), "beam_advance: cand_score"); _i(token, torch.int64, (B, C), "beam_advance: cand_token")
+    _i(beam, torch.int32, (B, C), "beam_advance: cand_beam"); _i(status, torch.int32, (B,), "beam_advance: status")
+    n_eos = 0
+    if eos is not None:
+        n_eos = eos.numel()
+        _i(eos, torch.int64, (n_eos,), "beam_advance: eos")
+    s = state
+    _lib.call("setok_beam_advance", _stream(), score.data_ptr(), token.data_ptr(), beam.data_ptr(), status.data_ptr(), B, n, C,
+              eos.data_ptr() if n_eos else None, n_eos, int(step), s.max_new, float(length_penalty), EARLY_STOPPING[early_stopping],
+              s.run_score.data_ptr(), s.fin_score.data_ptr(), s.fin_flag.data_ptr(), s.fin_len.data_ptr(), s.fin_parent.data_ptr(), s.fin_token.data_ptr(),
+              s.heur.data_ptr(), s.bp_token.data_ptr(), s.bp_parent.data_ptr(), s.next_token.data_ptr(), s.src_row.data_ptr(), s.summary.data_ptr())
+    return s.next_token, s.src_row, s.summary
+
+
+class KVReorderPlan:
+    """The device tables `setok_kv_reorder` takes, built once for a list of cache tensors - each (rows, Hkv, cap) or (rows, Hkv, cap, Dh), contiguous,
+    any element size - and the scratch region, grown to the largest slot range asked for."""
+
+    def __init__(self, tensors, n: int):
+        t0 = tensors[0]
+        self.rows, self.Hkv, self.cap = t0.shape[:3]
+        self.n, self.tensors = n, list(tensors)
+        if self.rows % n:
+            raise ValueError(f"kv_reorder: {self.rows} rows are not groups of n = {n}")
+        rb = []
+        for t in self.tensors:
+            if tuple(t.shape[:3]) != (self.rows, self.Hkv, self.cap) or t.dim() not in (3, 4) or not (t.is_cuda and t.is_contiguous()):
+                raise ValueError(f"kv_reorder: every tensor must be a contiguous device (rows, Hkv, cap[, Dh]) = ({self.rows}, {self.Hkv}, {self.cap}), "
+                                 f"got {tuple(t.shape)}")
+            rb.append(t.element_size() * (t.shape[3] if t.dim() == 4 else 1))
+        unit, acc = [], 0
+        for b in rb:
+            unit.append(acc)
+            acc += (b + 15) // 16 * 16
+        dev = t0.device
+        self.unit_total = acc
+        self.ptrs = torch.tensor([t.data_ptr() for t in self.tensors], dtype=torch.int64).to(dev)
+        self.row_bytes = torch.tensor(rb, dtype=torch.int32).to(dev)
+        self.scratch_unit = torch.tensor(unit, dtype=torch.int64).to(dev)
+        self.scratch: Optional[Tensor] = None
+        self.status = torch.zeros(self.rows, dtype=torch.int32, device=dev)
+
+    def room(self, ns: int) -> Tensor:
+        need = self.unit_total * self.rows * self.Hkv * ns
+        if self.scratch is None or self.scratch.numel() < need:
+            self.scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.status.device)
+        return self.scratch
+
+
+def kv_reorder(plan: KVReorderPlan, src_row: Tensor, slot0: int, slot1: int, reserve: Optional[int] = None) -> Tensor:
+    """Slots [slot0, slot1) of row r of every tensor of `plan` become what row src_row[r] (int32, inside r's own group of plan.n rows) held before the
+    call: two launches for all tensors (include/setok_hip.h, "Beam search").  `reserve`: size the scratch for that many slots at once.  Returns
+    plan.status (rows,) int32: 1 where a src_row was outside its group (that row then keeps its data), sticky across calls."""
+    if not 0 <= slot0 <= slot1 <= plan.cap:
+        raise ValueError(f"kv_reorder: slots [{slot0}, {slot1}) are not inside the cache (cap = {plan.cap})")
+    _i(src_row, torch.int32, (plan.rows,), "kv_reorder: src_row")
+    scratch = plan.room(max(slot1 - slot0, reserve or 0))
+    _lib.call("setok_kv_reorder", _stream(), plan.ptrs.data_ptr(), plan.row_bytes.data_ptr(), plan.scratch_unit.data_ptr(), len(plan.tensors),
+              plan.unit_total, plan.rows, plan.n, plan.Hkv, plan.cap, int(slot0), int(slot1), src_row.data_ptr(), scratch.data_ptr(), scratch.numel(),
+              plan.status.data_ptr())
+    return plan.status
+
+
 # ---- fp8 weight-only storage (csrc/gemm_fp8w.hip; the M <= 64 GEMM it shares with MXFP4: csrc/wstream.h, here _linear_wstream) -----------------
 FP8W_MAX_M = 64                                   # rows setok_linear_fp8w takes; more rows dequantise and go through `linear`
 
