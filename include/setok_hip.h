@@ -703,6 +703,52 @@ int setok_kv_reorder(void* stream, const void* const* ptrs, const int32_t* row_b
                      int64_t unit_total, int rows, int n, int Hkv, int cap, int slot0, int slot1, const int32_t* src_row, void* scratch,
                      int64_t scratch_bytes, int32_t* status);
 
+/* ---- Logits processors (csrc/logits.hip): HuggingFace's RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor,
+ * MinNewTokensLengthLogitsProcessor and SuppressTokensLogitsProcessor, in the order of `GenerationMixin._get_logits_processor`, applied to a
+ * step's logits BEFORE a token is selected (setok_argmax_rows) and before the warpers that setok_sample_rows implements.  Pure addition: the ABI
+ * version stays 9.
+ *
+ * A sequence b has a history hist[b][0 .. hist_len[b]) (hist (B, cap_h) int64, hist_len (B) int32) and a prompt_len[b] (int32).  The call works on
+ * B * n rows; row (b, i) = b * n + i sees the virtual history
+ *     Hs = hist[b][0 .. hist_len[b])  followed by  tail[b][0 .. i)        (tail (B, n - 1) int64, NULL with n == 1),   L = hist_len[b] + i.
+ * n = 1 is the plain loop; n = K + 1 is a verify round of draft-and-verify whose tail holds the K drafts.
+ * With x_v = float(logit_v) in fp32 (HF casts the step's logits to fp32 before its processors), for v in [0, V):
+ *   1. out[v] = x_v.
+ *   2. Penalty (penalty != 1): if v occurs in Hs, out[v] = x_v < 0 ? x_v * penalty : x_v / penalty - both in fp32, `penalty` rounded to fp32
+ *      once, a true division (no reciprocal multiply); once, however often v occurs.
+ *   3. N-gram ban (ngram = g >= 1 and L + 1 >= g): for every j in [0, L - g] with Hs[j .. j + g - 1) == Hs[L - g + 1 .. L) (g - 1 tokens;
+ *      with g = 1 every occurring token), out[Hs[j + g - 1]] = -inf.  A window whose compared tokens or banned token include an id outside
+ *      [0, V) bans nothing.
+ *   4. Minimum length (min_new > 0 and L - prompt_len[b] < min_new): out[e] = -inf for every eos id e in [0, V).
+ *   5. Suppression: out[s] = -inf for every suppressed id s in [0, V).
+ * A ban wins over the penalty.  Ids outside [0, V) - image placeholders, everything behind a negative draft - match nothing and are never
+ * dereferenced.  NaN and +-inf logits go through the arithmetic as IEEE gives them; what the selection kernels do with a bad row does not
+ * change.  Slots at or behind hist_len[b] (a hist_len outside [0, cap_h] is clamped into it), logits columns >= V and out columns >= V are
+ * never read or written.
+ *
+ * setok_logits_process - one workgroup of 256 threads per row.  logits: (B * n, V) in `dtype`, row stride ld >= V elements, any alignment (V =
+ *   32003 included); out: (B * n, V) fp32, row stride ld_out >= V, must not overlap logits.  16-byte loads from the first 16-byte boundary of a row
+ *   on, 16-byte stores where the out row then sits on one.  Threads stride over the history windows as in setok_ngram_propose.  No atomics.
+ *   Up to three writers can aim at one column and several history positions can hold one token; the stored bits do not depend on timing:
+ *   the copy, the penalty and the bans are three phases separated by workgroup barriers (a barrier orders the workgroup's global stores), every
+ *   penalty value is computed from the untouched INPUT (duplicates store identical bits), and every ban stores the same -inf.
+ *   eos (n_eos) and suppress (n_suppress) int64, NULL with a count of 0.
+ *   Refused on the host before any launch (-1, setok_last_error): a null operand, B < 0, n outside [1, 64], V outside [1, 2^20], ld < V,
+ *   ld_out < V, cap_h < 1, a null tail with n > 1, ngram outside [0, 8], min_new < 0, n_eos or n_suppress outside [0, 64], a penalty that is
+ *   not finite or <= 0, an out that overlaps logits, a dtype the library does not serve.  B == 0 launches nothing.
+ *
+ * setok_history_append - one workgroup of 64 threads per sequence: hist[b][hist_len[b] ..] = emitted[b][0 .. m[b]) (emitted (B, n_emit) int64;
+ *   m (B) int32 clamped to [0, n_emit], NULL = every row appends n_emit entries), then hist_len[b] += m[b].  A launch of its own: the rows of one
+ *   sequence run in different workgroups of the process kernel, all of which read the history.  len_max is the caller's host-side bound on
+ *   max_b (hist_len[b] + m[b]): the call is refused when len_max > cap_h ("hist_len + m > cap_h"), and the kernel never writes at or behind cap_h
+ *   whatever the device values say.  Refused as well: a null operand, B < 0, cap_h < 1, n_emit outside [0, 64].  B == 0 or n_emit == 0 launches
+ *   nothing. */
+int setok_logits_process(void* stream, int dtype, const void* logits, int64_t ld, int B, int n, int V, const int64_t* hist, const int32_t* hist_len,
+                         const int32_t* prompt_len, int cap_h, const int64_t* tail, float penalty, int ngram, int min_new, const int64_t* eos,
+                         int n_eos, const int64_t* suppress, int n_suppress, float* out, int64_t ld_out);
+int setok_history_append(void* stream, int64_t* hist, int32_t* hist_len, int B, int cap_h, int len_max, const int64_t* emitted, const int32_t* m,
+                         int n_emit);
+
 /* ---- FP8 weight-only decode (csrc/gemm_fp8w.hip; the M <= 64 GEMM it shares with MXFP4: csrc/wstream.h): the decode step streams every projection weight once per token, so the stack's Linear
  * weights may be STORED as OCP e4m3fn bytes with one power-of-two scale per output row.  A matrix W (N, K) becomes q (N, K) uint8 + e (N,) int8 and
  * means exactly

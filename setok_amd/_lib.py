@@ -114,6 +114,8 @@ SIGNATURES = {
     "setok_beam_topk": [_vp, _i, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64],
     "setok_beam_advance": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "setok_kv_reorder": [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp],
+    "setok_logits_process": [_vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _i, _i, _vp, _i, _vp, _i, _vp, _i64],
+    "setok_history_append": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i],
     "setok_quantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i, _i],
     "setok_dequantize_fp8_rows": [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _i],
     "setok_linear_fp8w": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i],

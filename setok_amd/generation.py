@@ -5,7 +5,8 @@ keeps between steps as HF's `past_key_values` (:99,133,189), and what it returns
 one slot for all sequences, `LlamaModel.extend` appends Tn >= 1 slots (chunked prefill, the next turn of a conversation).  The loop itself is
 `SetokimLlamaPrefill.generate` (llama.py); `GenerationState` is what it hands back so that a later call can continue from the same cache.
 `Drafter` / `LookupDrafter` are the sources of proposals for `generate(draft=...)`, which verifies K drafted tokens per `extend`.  `BeamSearch` is the
-setting of `generate(beams=...)`, which decodes on `KVCache.expanded(num_beams)` and re-points the beams' slots with `KVCache.reorder` every step."""
+setting of `generate(beams=...)`, which decodes on `KVCache.expanded(num_beams)` and re-points the beams' slots with `KVCache.reorder` every step.
+`LogitsProcessors` is the setting of `generate(processors=...)`, which changes a step's logits before a token is selected."""
 from __future__ import annotations
 
 import math
@@ -232,6 +233,82 @@ class BeamSearch:
         return C
 
 
+def _prompt_history(B: int, device, prompt_ids: Optional[torch.Tensor], prompt_mask: Optional[torch.Tensor], cap_h: int):
+    """(hist (B, cap_h) int64 filled with -1, hist_len (B,) int32) on `device`: each sequence's attended prompt ids in order.  Negative ids (image
+    placeholders) stay; with `prompt_ids` None (`inputs_embeds` alone) the histories start empty."""
+    T = 0 if prompt_ids is None else prompt_ids.shape[1]
+    hist = torch.full((B, cap_h), -1, dtype=torch.int64, device=device)
+    hist_len = torch.zeros(B, dtype=torch.int32, device=device)
+    if T:
+        ids = prompt_ids.to(device=device, dtype=torch.int64)
+        if prompt_mask is None:
+            hist[:, :T] = ids
+            hist_len.fill_(T)
+        else:
+            am = prompt_mask.to(device).bool()
+            order = torch.argsort((~am).to(torch.int8), dim=1, stable=True)       # the attended columns first, in their order
+            hist[:, :T] = ids.gather(1, order)
+            hist_len.copy_(am.sum(1))
+    return hist, hist_len
+
+
+class LogitsProcessors:
+    """What `SetokimLlamaPrefill.generate(processors=...)` applies to a step's logits before a token is selected: HF's `repetition_penalty`,
+    `no_repeat_ngram_size`, `min_new_tokens` and `suppress_tokens` with HF's meaning and order (include/setok_hip.h, "Logits processors", states the
+    rule), one launch of `setok_logits_process` per step and one of `setok_history_append` behind the selection.  The neutral values - 1.0, 0, 0, None -
+    switch a processor off; `min_new_tokens` bans the call's `eos_token_id` and does nothing without one.  The arguments are validated here and raise
+    ValueError.  The object holds settings only: a call's histories live in the `ProcessorState` that `begin` returns."""
+
+    def __init__(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens=None):
+        if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not math.isfinite(repetition_penalty) \
+                or repetition_penalty <= 0:
+            raise ValueError(f"LogitsProcessors: repetition_penalty={repetition_penalty!r} must be a finite number > 0 (1.0 = no penalty)")
+        if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, int) or not 0 <= no_repeat_ngram_size <= ops.LOGITS_MAX_NGRAM:
+            raise ValueError(f"LogitsProcessors: no_repeat_ngram_size={no_repeat_ngram_size!r} must be an int in [0, {ops.LOGITS_MAX_NGRAM}] (0 = no ban)")
+        if isinstance(min_new_tokens, bool) or not isinstance(min_new_tokens, int) or min_new_tokens < 0:
+            raise ValueError(f"LogitsProcessors: min_new_tokens={min_new_tokens!r} must be an int >= 0")
+        ids = [] if suppress_tokens is None else suppress_tokens
+        if isinstance(ids, (str, bytes)) or not hasattr(ids, "__iter__"):
+            raise ValueError(f"LogitsProcessors: suppress_tokens={suppress_tokens!r} must be a list of token ids or None")
+        ids = list(ids)
+        if len(ids) > ops.LOGITS_MAX_IDS or any(isinstance(s, bool) or not isinstance(s, int) or s < 0 for s in ids):
+            raise ValueError(f"LogitsProcessors: suppress_tokens={suppress_tokens!r} must hold at most {ops.LOGITS_MAX_IDS} ints >= 0")
+        self.repetition_penalty, self.no_repeat_ngram_size = float(repetition_penalty), no_repeat_ngram_size
+        self.min_new_tokens, self.suppress_tokens = min_new_tokens, ids
+
+    def begin(self, B: int, device, prompt_ids: Optional[torch.Tensor], prompt_mask: Optional[torch.Tensor], max_new_tokens: int,
+              eos: Optional[torch.Tensor]) -> "ProcessorState":
+        """The state of one `generate` call: the histories start as each sequence's attended prompt ids (`LookupDrafter.begin`'s convention) and have
+        room for `max_new_tokens` more; `eos` is the call's (n_eos,) int64 device tensor or None."""
+        return ProcessorState(self, B, device, prompt_ids, prompt_mask, max_new_tokens, eos)
+
+
+class ProcessorState:
+    """A call's histories on the device - hist (B, cap_h) int64, hist_len and prompt_len (B,) int32 - and the two launches that use them."""
+
+    def __init__(self, settings: LogitsProcessors, B, device, prompt_ids, prompt_mask, max_new_tokens, eos):
+        T = 0 if prompt_ids is None else prompt_ids.shape[1]
+        self.settings = settings
+        self.hist, self.hist_len = _prompt_history(B, device, prompt_ids, prompt_mask, T + int(max_new_tokens))
+        self.prompt_len = self.hist_len.clone()
+        self._hi = T                                                               # host bound on every hist_len
+        if eos is not None and eos.numel() > ops.LOGITS_MAX_IDS:
+            raise ValueError(f"LogitsProcessors: {eos.numel()} eos ids exceed the {ops.LOGITS_MAX_IDS} a call takes")
+        self.eos = eos if settings.min_new_tokens > 0 else None                    # only the minimum-length ban reads them
+        self.suppress = torch.tensor(settings.suppress_tokens, dtype=torch.int64, device=device) if settings.suppress_tokens else None
+
+    def process(self, logits: torch.Tensor, tail: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 (B * n, V): the scores a token is selected from; row b * n + i sees the history followed by tail[b, :i] (the drafts of a round)."""
+        s = self.settings
+        return ops.logits_process(logits, self.hist, self.hist_len, self.prompt_len, tail, s.repetition_penalty, s.no_repeat_ngram_size,
+                                  s.min_new_tokens, self.eos, self.suppress)
+
+    def append(self, emitted: torch.Tensor, m: Optional[torch.Tensor] = None) -> None:
+        """emitted (B, n) int64: row b's first m[b] entries (all n with m None) join its history."""
+        self._hi = min(self._hi + emitted.shape[1], self.hist.shape[1])            # a call emits max_new_tokens per sequence at the most
+        ops.history_append(self.hist, self.hist_len, emitted.contiguous(), self._hi, m)
+
+
 @dataclass
 class GenerationState:
     """What `generate(return_past=True)` hands back and `generate(past=...)` continues from: the `KVCache` and `pending` (B,) int64 — the last real
@@ -249,13 +326,15 @@ class GenerateOutput:
     state that produced token j (what the reference collects as `x[-1]` per step, setokim_llama.py:363, for its image head); logits (B, n_new, V)
     when requested; past (a GenerationState) with `return_past`.  With `beams=` the rows are the B * num_return_sequences hypotheses, row b * R + r in
     descending score: sequences_scores (B * R,) float32 and beam_indices (B * R, n_new) int32 - entry [r, j] is the flat row b * num_beams + beam
-    whose state produced token j, -1 past the hypothesis' end (HF's meaning) -; hidden_states and logits follow that ancestry, zeros past the end."""
+    whose state produced token j, -1 past the hypothesis' end (HF's meaning) -; hidden_states and logits follow that ancestry, zeros past the end.
+    With `processors=` and `output_scores`: scores (B, n_new, V) float32, the processed logits token j was selected from, before the sampler's warpers."""
     sequences: torch.Tensor
     hidden_states: Optional[torch.Tensor] = None
     logits: Optional[torch.Tensor] = None
     past: Optional[GenerationState] = None
     sequences_scores: Optional[torch.Tensor] = None
     beam_indices: Optional[torch.Tensor] = None
+    scores: Optional[torch.Tensor] = None
 
 
 class Drafter:
@@ -308,19 +387,8 @@ class LookupDrafter(Drafter):
         T = 0 if prompt_ids is None else prompt_ids.shape[1]
         self._limit = None if max_new_tokens is None else T + int(max_new_tokens)
         cap_h = T + (int(max_new_tokens) if max_new_tokens is not None else 64) + self.K + 1
-        self.hist = torch.full((B, cap_h), -1, dtype=torch.int64, device=device)
-        self.hist_len = torch.zeros(B, dtype=torch.int32, device=device)
+        self.hist, self.hist_len = _prompt_history(B, device, prompt_ids, prompt_mask, cap_h)
         self._queued, self._hi = None, T
-        if T:
-            ids = prompt_ids.to(device=device, dtype=torch.int64)
-            if prompt_mask is None:
-                self.hist[:, :T] = ids
-                self.hist_len.fill_(T)
-            else:
-                am = prompt_mask.to(device).bool()
-                order = torch.argsort((~am).to(torch.int8), dim=1, stable=True)   # the attended columns first, in their order
-                self.hist[:, :T] = ids.gather(1, order)
-                self.hist_len.copy_(am.sum(1))
 
     def _room(self, n: int) -> int:
         """The bound on hist_len after `n` more entries per row; the history is regrown when a row could not take them."""

@@ -651,7 +651,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
     def generate(self, inputs=None, comp_images=None, attention_mask=None, position_ids=None, inputs_embeds=None, max_new_tokens: int = 200,
                  eos_token_id=None, pad_token_id=None, do_sample: bool = False, return_dict_in_generate: bool = False,
                  output_hidden_states: bool = False, output_logits: bool = False, images=None, kv_cache: str = "native", sampler=None, prefill_chunk: Optional[int] = None,
-                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, draft=None, beams=None, **unsupported):
+                 return_past: bool = False, past=None, cache_capacity: Optional[int] = None, draft=None, beams=None, processors=None,
+                 output_scores: bool = False, **unsupported):
         """Greedy decoding with a KV cache: `SetokimLlamaForCausalLM.generate` (setokim_llama.py:329-396) — encode the images, splice them into
         the prompt (the existing `_embed`), prefill, then one token per step: lm_head on the B last states, argmax on the device, the new ids'
         embedding rows, `LlamaModel.decode_step`.  `images=` is the reference's keyword for `comp_images`.
@@ -708,11 +709,24 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         (ValueError); `beams=` with `sampler=`, `draft=`, `past=` or `return_past=True` (NotImplementedError: beam sampling and continuing a beam
         state are not built).  `beams=None` is the plain loop bit for bit.
 
+        `processors=` (a generation.LogitsProcessors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)) changes every step's
+        logits before the token is selected, by HF's rule and in HF's order (include/setok_hip.h, "Logits processors").  Each sequence keeps a
+        history on the device that starts as its attended prompt ids in order (`LookupDrafter.begin`'s convention: negative ids stay and match
+        nothing, and with `inputs_embeds` alone it starts empty); `prompt_len` is its length.  A step is then lm_head, `setok_logits_process` (the
+        fp32 scores), the same argmax or sampler launch on those scores, and `setok_history_append`: two launches more than without.  With `draft=`
+        the K + 1 rows of a round are processed in one launch, row i seeing the history plus drafts 0 .. i - 1, and the emitted tokens are appended
+        after the accept rule: the tokens are the plain loop's.  `min_new_tokens` bans the `eos_token_id` ids and does nothing without one (HF's
+        rule).  `output_scores=True` (with `return_dict_in_generate`) adds `GenerateOutput.scores` (B, n_new, V) float32: the processed logits each
+        token was selected from, before the sampler's warpers.  Refused before any device call: a `processors` that is no LogitsProcessors
+        (TypeError); `processors=` with `beams=` (NotImplementedError: HF applies processors to the beams' log-probabilities, a different rule) or
+        with `past=` (NotImplementedError: a GenerationState keeps no history); `output_scores=True` without `processors=` or without
+        `return_dict_in_generate` (ValueError).  `processors=None` is the loop without them bit for bit.
+
         HF's own spelling stays refused: `do_sample=True`, temperature= / top_p= / top_k= or beams raise NotImplementedError (the reference's
         defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here: pass a
         `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
-        from .generation import BeamSearch, Drafter, GenerateOutput, GenerationState, KVCache, Sampler
+        from .generation import BeamSearch, Drafter, GenerateOutput, GenerationState, KVCache, LogitsProcessors, Sampler
         self.model._refuse_unmerged("SetokimLlamaPrefill.generate")
         sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
         if do_sample or sampling:
@@ -752,6 +766,21 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                                               "into beams and continuing a beam state are not built)")
             n_eos = 0 if eos_token_id is None else 1 if isinstance(eos_token_id, int) else len(list(eos_token_id))
             C = beams.candidates(n_eos, self.lm_head.weight.shape[0])
+        if processors is not None:
+            if not isinstance(processors, LogitsProcessors):
+                raise TypeError(f"SetokimLlamaPrefill.generate: processors must be a generation.LogitsProcessors or None, got {type(processors).__name__}")
+            if beams is not None:
+                raise NotImplementedError("SetokimLlamaPrefill.generate: processors= with beams= is not implemented (HF applies its processors to "
+                                          "the beams' log-probabilities, which is a different rule)")
+            if past is not None:
+                raise NotImplementedError("SetokimLlamaPrefill.generate: processors= with past= is not implemented (a GenerationState keeps no "
+                                          "history of the earlier turns)")
+            n_eos = 0 if eos_token_id is None else 1 if isinstance(eos_token_id, int) else len(list(eos_token_id))
+            if processors.min_new_tokens > 0 and n_eos > ops.LOGITS_MAX_IDS:
+                raise ValueError(f"SetokimLlamaPrefill.generate: min_new_tokens with {n_eos} eos ids exceeds the {ops.LOGITS_MAX_IDS} a step bans")
+        if output_scores and (processors is None or not return_dict_in_generate):
+            raise ValueError("SetokimLlamaPrefill.generate: output_scores=True needs processors= (the scores are the processed logits) and "
+                             "return_dict_in_generate=True (they are GenerateOutput.scores)")
         for name, v in (("prefill_chunk", prefill_chunk), ("cache_capacity", cache_capacity)):
             if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
                 raise ValueError(f"SetokimLlamaPrefill.generate: {name}={v!r} must be an integer >= 1 (or None)")
@@ -838,27 +867,33 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                                         return_dict_in_generate, output_hidden_states, output_logits)
         if draft is not None:
             return self._generate_speculative(draft, h, cache, inputs, attention_mask, max_new_tokens, eos, pad if eos is not None else 0, sampler,
-                                              return_dict_in_generate, output_hidden_states, output_logits, return_past)
+                                              return_dict_in_generate, output_hidden_states, output_logits, return_past, processors, output_scores)
+        proc = None if processors is None else processors.begin(B, dev, inputs, attention_mask, max_new_tokens, eos)
         fed0 = cache.len                                                           # the first slot a decode step of this call fills
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
-        toks, hids, lgs = [], [], []
+        toks, hids, lgs, scs = [], [], [], []
         raws = []                                                                  # sampler only: the tokens as drawn, -1 where a row could not be drawn from
         for step in range(max_new_tokens):
             logits = ops.linear(h, w_lm)                                           # (B, V): never copied to the host
+            scores = logits if proc is None else proc.process(logits)              # (B, V) fp32 with processors: what the token is selected from
             if sampler is None:
-                tok = ops.argmax_rows(logits)
+                tok = ops.argmax_rows(scores)
             else:
-                raw = sampler.select(logits, step)
+                raw = sampler.select(scores, step)
                 raws.append(raw)
                 tok = raw.clamp_min(0)                                             # a valid row for the embedding lookup; the error is raised below
             if eos is not None:
                 tok = torch.where(finished, torch.full_like(tok, pad), tok)
                 finished = finished | torch.isin(tok, eos)
             toks.append(tok)
+            if proc is not None:
+                proc.append(tok.reshape(B, 1))
             if output_hidden_states:
                 hids.append(h)
             if output_logits:
                 lgs.append(logits)
+            if output_scores:
+                scs.append(scores)
             if step + 1 == max_new_tokens:
                 break
             if eos is not None:
@@ -887,7 +922,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             cache.next_pos = cache.next_pos - (n - 1 - real).clamp_min(0)
             state = GenerationState(cache=cache, pending=torch.where(real == n, seq[:, -1], torch.full_like(real, -1)))
         return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if output_hidden_states else None,
-                              logits=torch.stack(lgs, dim=1) if output_logits else None, past=state)
+                              logits=torch.stack(lgs, dim=1) if output_logits else None, past=state,
+                              scores=torch.stack(scs, dim=1) if output_scores else None)
 
     def _generate_beams(self, beams, C, h, cache, max_new, eos, pad, as_dict, want_hidden, want_logits):
         """generate()'s loop with beam search, from the last attended state `h` (B, D) on.  The running scores, the finished set and the back-pointers
@@ -948,10 +984,12 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         return GenerateOutput(sequences=seq, hidden_states=along(hids) if want_hidden else None, logits=along(lgs) if want_logits else None,
                               sequences_scores=state.fin_score[:, :R].reshape(B * R).clone(), beam_indices=anc.to(torch.int32))
 
-    def _generate_speculative(self, draft, h, cache, prompt_ids, prompt_mask, max_new, eos, pad, sampler, as_dict, want_hidden, want_logits, want_past):
+    def _generate_speculative(self, draft, h, cache, prompt_ids, prompt_mask, max_new, eos, pad, sampler, as_dict, want_hidden, want_logits, want_past,
+                              processors=None, want_scores=False):
         """generate()'s loop with a drafter, from the last attended state `h` (B, D) on.  Between rounds the state lives on the device: pending
         (B,) int64, count (B,) int32, finished (B,) uint8 and seq (B, max_new) int64; `setok_spec_accept` advances it, and the host reads the
-        kernel's 3-int summary once per round."""
+        kernel's 3-int summary once per round.  With `processors` the K + 1 rows of a round are processed in one launch (row i sees the history plus
+        drafts 0 .. i - 1) before the selection, and the emitted tokens join the history behind the accept rule."""
         from .generation import GenerateOutput, GenerationState
         B, D = h.shape
         K, dev = draft.K, h.device
@@ -967,7 +1005,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         rows_b = torch.arange(B, device=dev)[:, None]
         # outputs: column max_new takes the rows no sequence emitted and is cut off at the end
         hid_out = torch.zeros((B, max_new + 1, D), dtype=h.dtype, device=dev) if want_hidden else None
-        lg_out = None
+        lg_out, sc_out = None, None
+        proc = None if processors is None else processors.begin(B, dev, prompt_ids, prompt_mask, max_new, eos)
 
         def select(logits, n):                                                     # logits (B * n, V) -> (B, n) int64
             if sampler is None:
@@ -975,9 +1014,9 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             ur = u[(count.long()[:, None] + steps[:, :n]).clamp_max(max_new - 1), rows_b].reshape(B * n).contiguous()
             return ops.sample_rows(logits, ur, sampler.temperature, sampler.top_k, sampler.top_p).reshape(B, n)
 
-        def keep(hidden, logits, before, m, n):                                    # row i < m[b] of sequence b -> column before[b] + i
-            nonlocal lg_out
-            if not (want_hidden or want_logits):
+        def keep(hidden, logits, scores, before, m, n):                            # row i < m[b] of sequence b -> column before[b] + i
+            nonlocal lg_out, sc_out
+            if not (want_hidden or want_logits or want_scores):
                 return
             cols = torch.where(steps[:, :n] < m.long()[:, None], before.long()[:, None] + steps[:, :n], torch.full_like(steps[:, :n], max_new))
             if want_hidden:
@@ -986,6 +1025,10 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
                 if lg_out is None:
                     lg_out = torch.zeros((B, max_new + 1, logits.shape[-1]), dtype=logits.dtype, device=dev)
                 lg_out[rows_b, cols] = logits.reshape(B, n, -1)
+            if want_scores:
+                if sc_out is None:
+                    sc_out = torch.zeros((B, max_new + 1, scores.shape[-1]), dtype=scores.dtype, device=dev)
+                sc_out[rows_b, cols] = scores.reshape(B, n, -1)
 
         def after_round():
             mx, live, bad = summary.tolist()                                       # the round's one host read
@@ -999,12 +1042,15 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         draft.begin(B, dev, prompt_ids, prompt_mask, max_new)
         # step 0: the token selected from the last attended state, put into the loop state by the accept rule with no drafts
         logits = ops.linear(h, w_lm)
-        sel = select(logits, 1)
+        scores = logits if proc is None else proc.process(logits)
+        sel = select(scores, 1)
         before = count.clone()
         emitted, m, _ = ops.spec_accept(sel[:, :0].contiguous(), sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, cache.len,
                                         summary=summary)
         cache.key_mask[:, cache.len] = 0                                           # (nothing was fed: the slot the rule marked is not filled yet)
-        keep(h, logits, before, m, 1)
+        keep(h, logits, scores, before, m, 1)
+        if proc is not None:
+            proc.append(emitted, m)
         draft.update(emitted, m)
         _, live = after_round()
         while live > 0:
@@ -1020,10 +1066,13 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             len0 = cache.len
             hidden = self.model.extend(ops.splice_rows(ids, w_e, None), cache, am)         # (B, K + 1, D): one pass over the weights
             logits = ops.linear(hidden.reshape(B * (K + 1), D), w_lm)
-            sel = select(logits, K + 1)
+            scores = logits if proc is None else proc.process(logits, d)
+            sel = select(scores, K + 1)
             before = count.clone()
             emitted, m, _ = ops.spec_accept(d, sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, len0, summary=summary)
-            keep(hidden, logits, before, m, K + 1)
+            keep(hidden, logits, scores, before, m, K + 1)
+            if proc is not None:
+                proc.append(emitted, m)
             draft.update(emitted, m)
             mx, live = after_round()
             cache.truncate(len0 + mx)
@@ -1033,7 +1082,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
             return out
         state = GenerationState(cache=cache, pending=pending) if want_past else None
         return GenerateOutput(sequences=out, hidden_states=hid_out[:, :n].contiguous() if want_hidden else None,
-                              logits=lg_out[:, :n].contiguous() if want_logits else None, past=state)
+                              logits=lg_out[:, :n].contiguous() if want_logits else None, past=state,
+                              scores=sc_out[:, :n].contiguous() if want_scores else None)
 
     def _head(self, inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss):
         hidden = self.model._forward(inputs_embeds, attention_mask, position_ids)  # setokim_llama.py:130-140

@@ -969,6 +969,67 @@ def ngram_propose(hist: Tensor, hist_len: Tensor, K: int, len_max: int, emitted:
     return out
 
 
+# ---- logits processors (csrc/logits.hip) ---------------------------------------------------------------------------------------------------------
+LOGITS_MAX_NGRAM = 8
+LOGITS_MAX_IDS = 64                               # eos ids / suppressed ids per call
+
+
+def logits_process(logits: Tensor, hist: Tensor, hist_len: Tensor, prompt_len: Tensor, tail: Optional[Tensor] = None, penalty: float = 1.0,
+                   ngram: int = 0, min_new: int = 0, eos: Optional[Tensor] = None, suppress: Optional[Tensor] = None,
+                   out: Optional[Tensor] = None) -> Tensor:
+    """fp32 (B * n, V): the step's logits (B * n, V; any row stride) after the repetition penalty, the n-gram bans, the minimum-length eos ban and
+    the suppression (include/setok_hip.h, "Logits processors"), one launch.  hist (B, cap_h) int64 with hist_len (B,) int32 valid entries and
+    prompt_len (B,) int32; row b * n + i sees sequence b's history followed by tail[b, :i] (tail (B, n - 1) int64, None with n = 1).  eos and
+    suppress: (count <= 64,) int64 or None.  `out` may be a (B * n, V) fp32 view with any row stride; it must not overlap `logits`."""
+    if logits.dim() != 2 or hist.dim() != 2:
+        raise ValueError(f"logits_process: logits must be (B * n, V) and hist (B, cap_h), got {tuple(logits.shape)} and {tuple(hist.shape)}")
+    rows, V = logits.shape
+    B, cap_h = hist.shape
+    n = 1 if tail is None else tail.shape[1] + 1
+    if rows != B * n:
+        raise ValueError(f"logits_process: {rows} rows of logits are not B * n = {B} * {n}")
+    assert logits.stride(1) == 1 and logits.is_cuda
+    i64, i32 = torch.int64, torch.int32
+    _i(hist, i64, (B, cap_h), "logits_process: hist"); _i(hist_len, i32, (B,), "logits_process: hist_len")
+    _i(prompt_len, i32, (B,), "logits_process: prompt_len")
+    if tail is not None:
+        _i(tail, i64, (B, n - 1), "logits_process: tail")
+    counts = []
+    for ids, what in ((eos, "eos"), (suppress, "suppress")):
+        counts.append(0 if ids is None else ids.numel())
+        if ids is not None:
+            _i(ids, i64, (counts[-1],), f"logits_process: {what}")
+    if out is None:
+        out = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.shape == (rows, V) and out.stride(1) == 1 and out.is_cuda
+    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), V)
+    ld_out = out.stride(0) if rows > 1 else max(out.stride(0), V)
+    _lib.call("setok_logits_process", _stream(), _code(logits.dtype), logits.data_ptr(), ld, B, n, V, hist.data_ptr(), hist_len.data_ptr(),
+              prompt_len.data_ptr(), cap_h, tail.data_ptr() if n > 1 else None, float(penalty), int(ngram), int(min_new),
+              eos.data_ptr() if counts[0] else None, counts[0], suppress.data_ptr() if counts[1] else None, counts[1], out.data_ptr(), ld_out)
+    return out
+
+
+def history_append(hist: Tensor, hist_len: Tensor, emitted: Tensor, len_max: int, m: Optional[Tensor] = None) -> None:
+    """hist[b, hist_len[b]:] = emitted[b, :m[b]] and hist_len[b] += m[b], in place, one launch (hist (B, cap_h) int64, hist_len (B,) int32, emitted
+    (B, n_emit <= 64) int64, m (B,) int32 or None = every row appends n_emit entries).  len_max: the caller's bound on max_b (hist_len[b] + m[b]);
+    a bound above cap_h is refused, and the kernel never writes behind a row."""
+    if hist.dim() != 2 or emitted.dim() != 2:
+        raise ValueError(f"history_append: hist must be (B, cap_h) and emitted (B, n_emit), got {tuple(hist.shape)} and {tuple(emitted.shape)}")
+    B, cap_h = hist.shape
+    n_emit = emitted.shape[1]
+    if n_emit > SPEC_MAX_K + 1:
+        raise ValueError(f"history_append: emitted must be (B, 0 .. {SPEC_MAX_K + 1}), got {tuple(emitted.shape)}")
+    if cap_h < 1 or not 0 <= len_max <= cap_h:
+        raise ValueError(f"history_append: hist_len + m > cap_h (the history may reach {len_max} entries, a row holds {cap_h})")
+    _i(hist, torch.int64, (B, cap_h), "history_append: hist"); _i(hist_len, torch.int32, (B,), "history_append: hist_len")
+    _i(emitted, torch.int64, (B, n_emit), "history_append: emitted")
+    if m is not None:
+        _i(m, torch.int32, (B,), "history_append: m")
+    _lib.call("setok_history_append", _stream(), hist.data_ptr(), hist_len.data_ptr(), B, cap_h, int(len_max), emitted.data_ptr() if n_emit else None,
+              None if m is None else m.data_ptr(), n_emit)
+
+
 # ---- beam search (csrc/beam.hip) -----------------------------------------------------------------------------------------------------------------
 BEAM_MAX_C = 64                                   # candidates per sequence: C = max(2, 1 + n_eos) * num_beams
 BEAM_MAX_N = 16                                   # beams per sequence
