@@ -868,6 +868,60 @@ int setok_attention_decode_gqa_fp8kv(void* stream, int dtype, const void* q, int
                                      const uint8_t* v_q, const int8_t* v_e, const uint8_t* key_mask, void* out, int B, int H, int Hkv, int Dh,
                                      int cap, int len, float scale, float* ws, int64_t ws_floats);
 
+/* ---- MXFP4 KV cache (csrc/attn_decode.hip, csrc/attn_extend.hip): the cache STORED by the rule of "MXFP4 weight-only decode", one cache row —
+ * the Dh post-rotary elements of one (sequence, key / value head, slot), of K or of V — taking the place of a weight row.  Per layer:
+ *     k_q, v_q (B, Hkv, cap, Dh/2) uint8     element 2j of a row in the low nibble of byte j, element 2j+1 in the high one
+ *     k_s, v_s (B, Hkv, cap, Dh/32) uint8    e8m0 scale bytes, one per 32 elements of a row
+ * meaning exactly value_e2m1(nibble[d]) * 2^(s[d / 32] - 127).  The quantiser is setok_quantize_mxfp4_rows' rule per block of 32: a non-finite
+ * entry -> scale byte 0xFF and nibbles 0; a block of zeros -> scale byte 127; otherwise e = floor(log2 amax) - 2 clamped to [-13, 13], nibbles
+ * rounded to nearest with ties to the even code, saturating at +-6, the sign bit the value's own.  The stored K', V' are exactly representable in
+ * fp32, bf16 and fp16, so an attention over the cache is an ordinary attention over K', V'.  Dh % 32 == 0 is required by every entry point
+ * below; the cache takes 2 * layers * B * Hkv * cap * (Dh/2 + Dh/32) bytes (a row at Dh = 128: 68 bytes; an fp8 row 129, a bf16 row 256).
+ * A slot that does not count (masked, or at / past `len`) may hold ANY nibbles and ANY scale byte, 0xFF included: it is discarded by selection.
+ * A slot that counts and holds a 0xFF block gives NaN, as a NaN in a native cache would.  Only the cache is quantised: an unchunked prefill
+ * attends over its own unquantised q | k | v, an extend (a window of a chunked prefill, a turn, a verify pass) over the stored slots.
+ * Unlike the fp8 cache this format can be extended by several tokens.  Pure additions: the ABI version stays 9. */
+
+/* Keys of one chunk of the decode attention over the MXFP4 cache.  A lane holds 16 elements of a row (8 nibble bytes and the scale byte it shares
+ * with its neighbour), so at Dh = 128 a row is spread over 8 lanes as in the fp8 kernel and a wave streams 64 rows per chunk in 8 + 8 loads.
+ * fp8's bytes-in-flight argument would ask for 512 (8-byte pieces: twice the rows for the same bytes), but the kernel keeps one fp32 score per
+ * (load step, query head of the group) in registers until the wave's maximum is known, and at 8 query heads 16 steps of them do not fit next to
+ * the group's q and accumulators without scratch.  256 keeps the fp8 kernel's register budget and its partition of a sequence's keys; the
+ * constant depends on the format alone, so every summation order depends on `len` alone. */
+#define SETOK_DECODE_CHUNK_MXFP4KV 256
+
+/* setok_kv_append with the MXFP4 quantiser: the post-rotary k and v columns of B*T rows of a fused [q: H | k: Hkv | v: Hkv] buffer in `dtype`
+ * are quantised block by block (the rule above) into slots [pos0, pos0 + T) of k_q / k_s and v_q / v_s; T >= 1 rows per sequence (a prefill
+ * appends the whole prompt), T == 0 does nothing.  One pass, a row in the registers of the lanes that hold it (a block of 32 is four lanes); no
+ * LDS, no atomics; no byte outside those slots is written.  Dh % 32 == 0 and Dh <= 512; qkv, k_q and v_q 16-byte aligned. */
+int setok_kv_append_mxfp4(void* stream, int dtype, const void* qkv, uint8_t* k_q, uint8_t* k_s, uint8_t* v_q, uint8_t* v_s, int B, int T, int H,
+                          int Hkv, int Dh, int cap, int pos0);
+
+/* setok_attention_decode_gqa over the MXFP4 cache: q and out in `dtype`, the keys / values K', V' as stored.  Everything that call states holds
+ * here — which keys count, zeros for a sequence without one, fp32 scores and softmax, the probabilities rounded to the 16-bit element type
+ * before they multiply V, one read of each cache byte per group of query heads, chunk partials merged in chunk order by a second launch, output
+ * bits that depend on the sequence's own operands and `len` alone — with SETOK_DECODE_CHUNK_MXFP4KV in the place of SETOK_DECODE_CHUNK:
+ * ws_floats >= B * H * ceil(len / SETOK_DECODE_CHUNK_MXFP4KV) * (Dh + 2).  The block scale is applied by the hardware converter when a lane's
+ * piece is decoded, so the decoded floats are exactly K', V' and the arithmetic from there on is the native kernel's.  Dh % 32 == 0; Dh in
+ * {32, 64, 128} take the lane-layout kernel, the others (96, ...) a generic one.  q, k_q and v_q 16-byte aligned. */
+int setok_attention_decode_gqa_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                       const uint8_t* v_q, const uint8_t* v_s, const uint8_t* key_mask, void* out, int B, int H, int Hkv, int Dh,
+                                       int cap, int len, float scale, float* ws, int64_t ws_floats);
+
+/* Floats of workspace setok_attention_extend_gqa_mxfp4kv needs: B * Tn * H * ceil((len0 + Tn) / SETOK_EXTEND_CHUNK) * (Dh + 2), whatever the
+ * element type (one partial per chunk; setok_attention_extend_gqa's span rule does not apply).  0 for arguments the call would refuse. */
+int64_t setok_attention_extend_mxfp4kv_workspace(int B, int Tn, int H, int Dh, int len0);
+
+/* setok_attention_extend_gqa over the MXFP4 cache: Tn >= 1 query rows per (sequence, query head) against slots [0, len0 + Tn), which already
+ * hold the new rows' quantised keys / values; query i of sequence b counts slot j iff j <= len0 + i and key_mask[b][j] != 0, a query without a
+ * counted key gets zeros.  That call's semantics and refusals, with Dh % 32 == 0.  One wave per (query row, query head, chunk of
+ * SETOK_EXTEND_CHUNK slots), a key per lane, then the shared merge in chunk order, for every head dim and element type: this is a FUNCTIONAL
+ * path — it reads the cache once per query row and query head and uses no MFMA; an MFMA extend over nibbles is a follow-up (DESIGN.md §7 f16 has
+ * the measurements that say where it stops being worth it).  q, k_q and v_q 16-byte aligned. */
+int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                       const uint8_t* v_q, const uint8_t* v_s, const uint8_t* key_mask, void* out, int B, int Tn, int H, int Hkv,
+                                       int Dh, int cap, int len0, float scale, float* workspace, int64_t workspace_floats);
+
 /* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
  * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest
  * (csrc/diffusion.hip).  Every entry is asynchronous on `stream`, allocates nothing, synchronises nothing, accepts rows == 0, uses 16-byte

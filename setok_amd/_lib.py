@@ -36,7 +36,7 @@ class SetokConfig(C.Structure):
 
 
 RESTYPES = {"setok_last_error": C.c_char_p, "setok_ctx_error": C.c_char_p, "setok_encode_workspace_bytes": _i64, "setok_destroy": None,
-            "setok_attention_extend_workspace": _i64, "setok_linear_skinny_workspace": _i64}
+            "setok_attention_extend_workspace": _i64, "setok_linear_skinny_workspace": _i64, "setok_attention_extend_mxfp4kv_workspace": _i64}
 
 # name -> argtypes; mirrors include/setok_hip.h declaration by declaration
 SIGNATURES = {
@@ -126,6 +126,10 @@ SIGNATURES = {
     "setok_linear_mxfp4w_wgs": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i],
     "setok_kv_append_fp8": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa_fp8kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_kv_append_mxfp4": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
+    "setok_attention_decode_gqa_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_attention_extend_mxfp4kv_workspace": [_i, _i, _i, _i, _i],
+    "setok_attention_extend_gqa_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_linear_skinny_workspace": [_i, _i, _i],
     "setok_linear_skinny": [_vp, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _f, _vp, _i64],
     "setok_timestep_embedding": [_vp, _i, _vp, _vp, _i, _i, _f],

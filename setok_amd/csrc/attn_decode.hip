@@ -5,6 +5,8 @@
 //   setok_argmax_rows           greedy selection on the device (lowest index of the row maximum)
 //   setok_kv_append_fp8, setok_attention_decode_gqa_fp8kv   the same two over a cache stored as e4m3fn rows with a power-of-two exponent per row
 //                               (the same decode kernel over the KvFp8 format of attn_partials.h)
+//   setok_kv_append_mxfp4, setok_attention_decode_gqa_mxfp4kv   and over a cache stored as OCP MXFP4 rows: e2m1 nibbles with one e8m0 scale byte per
+//                               32 elements (the same decode kernel over the KvMxfp4 format)
 //
 // The decode attention is bound by the K / V bytes it reads.  Its structure:
 //   - work is cut over (key chunk of SETOK_DECODE_CHUNK slots, key / value head, sequence); the chunk length is a constant, so the partition of a
@@ -20,7 +22,9 @@
 // A key counts iff its slot is < len and its mask byte is non-zero; a sequence without such a key gets zeros (the prefill kernel's convention).
 #include "common.h"
 #include "fp8.h"
+#include "mx4.h"
 #include "attn_partials.h"
+#include <type_traits>
 
 namespace {
 
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const T* __restrict__ qk
 // grid (chunks, Hkv * (G / GT), B); GT query heads of one group per workgroup (G itself for G in {1, 2, 4, 8}).  ws: per (sequence, query head,
 // chunk) Dh + 2 floats [max, sum, accumulators].  F is the cache's format (attn_partials.h): a lane holds F::VEC elements of a row, so a load
 // instruction covers 64 / LPR keys and a wave's slice is F::CHUNK / 4 keys — 32 native, 64 over e4m3 rows: 8 + 8 loads of 16 bytes per lane at head
-// dim 128 either way.  Scaling of an e4m3 row: 2^e of a K row multiplies the FINISHED dot product (before `scale`), 2^e of a V row is folded into
+// dim 128 either way; over nibble rows 64 keys again, 8 + 8 loads of 8 bytes and as many scale bytes (the lane budget: DESIGN.md §7 f16).  Scaling of an e4m3 row: 2^e of a K row multiplies the FINISHED dot product (before `scale`), 2^e of a V row is folded into
 // the ROUNDED probability — both exact, so every product and sum equals the one over K', V'.  A slot that does not count is discarded by selection:
 // its exponent byte is replaced by 0 before a scale is built.
 template <typename T, typename F, int LPR, int GT>
@@ -111,12 +115,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            kr[i] = *reinterpret_cast<const V16*>(kv.k + (rowbase + jc) * DH + cc * VEC);
+            kr[i] = F::load(kv.k, (rowbase + jc) * DH + cc * VEC);
         }
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            vr[i] = *reinterpret_cast<const V16*>(kv.v + (rowbase + jc) * DH + cc * VEC);
+            vr[i] = F::load(kv.v, (rowbase + jc) * DH + cc * VEC);
         }
         float qf[GT][VEC];
         int cq = cc;
@@ -258,14 +262,22 @@ void launch_decode(hipStream_t s, const T* q, int64_t ldq, F kv, const uint8_t* 
 }
 
 // Both entry points (`name`: the entry point's, for its messages).  A head dim with a lane layout takes the chunk kernel — over e4m3 rows head dims
-// 16 / 32 / 64 / 128, native every LPR = Dh / VEC in {2, ..., 32} — and every other one the wave-per-chunk kernel of attn_partials.h.
+// 16 / 32 / 64 / 128, over nibble rows 32 / 64 / 128, native every LPR = Dh / VEC in {2, ..., 32} — and every other one the wave-per-chunk kernel
+// of attn_partials.h.
 template <typename T, typename F>
 int decode_t(const char* name, hipStream_t s, const T* q, int64_t ldq, F kv, const uint8_t* km, T* out, float* ws, int B, int H, int Hkv, int Dh, int cap,
              int len, float scale) {
     const int nch = cdiv(len, F::CHUNK);
     auto any = [&] { attn_chunk_any_kernel<T, F, F::CHUNK, false><<<dim3(nch, H, B), 64, 0, s>>>(q, ldq, kv, km, ws, 1, H, Hkv, Dh, cap, len - 1, scale); };
 #define DEC_LPR(N) launch_decode<T, F, N>(s, q, ldq, kv, km, ws, B, H, Hkv, cap, len, scale); break
-    if constexpr (F::SCALED) {
+    if constexpr (std::is_same<F, KvMxfp4>::value) {                   // 16 elements per lane
+        switch (Dh) {
+            case 32: DEC_LPR(2);
+            case 64: DEC_LPR(4);
+            case 128: DEC_LPR(8);
+            default: any(); break;
+        }
+    } else if constexpr (F::SCALED) {
         switch (Dh) {
             case 16: DEC_LPR(1);
             case 32: DEC_LPR(2);
@@ -386,6 +398,70 @@ void launch_append_fp8(hipStream_t s, const T* qkv, uint8_t* kq, int8_t* ke, uin
 #undef F8_APPEND
 }
 
+// ==== filling the MXFP4 KV cache (include/setok_hip.h, "MXFP4 KV cache") ==========================================================================
+// A cache row is Dh / 2 bytes of e2m1 nibbles + Dh / 32 e8m0 scale bytes and means value(nibble[d]) * 2^(s[d / 32] - 127) (mx4.h: the rule of
+// the weight path).  kv_append_fp8_kernel's arrangement: one pass, a row in the registers of GL lanes, 8 elements each, so a block of 32 is an
+// aligned quad of lanes and its amax two quad_perm exchanges; a lane writes its 8 nibbles as one dword, the quad's first lane the scale byte.
+// Dh % 32 == 0, so a row is a whole number of quads and a lane without a piece shares a quad with no live lane.
+template <typename T, int GL>
+__global__ __launch_bounds__(256) void kv_append_mxfp4_kernel(const T* __restrict__ qkv, uint8_t* __restrict__ kq, uint8_t* __restrict__ ks,
+                                                              uint8_t* __restrict__ vq, uint8_t* __restrict__ vs, int B, int Tn, int H, int Hkv, int Dh,
+                                                              int cap, int pos0) {
+    constexpr int RPB = 256 / GL;                                      // rows per workgroup and trip
+    const int vpr = Dh / 8, sub = threadIdx.x % GL;
+    const int64_t rows = (int64_t)B * Tn * 2 * Hkv, ld = (int64_t)(H + 2 * Hkv) * Dh;
+    for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < rows; r0 += (int64_t)gridDim.x * RPB) {
+        const int64_t row = r0 + threadIdx.x / GL;
+        const bool live = row < rows && sub < vpr;
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = 0.f;
+        int which = 0;
+        int64_t slot = 0;
+        if (live) {
+            const int hk = (int)(row % Hkv);
+            which = (int)((row / Hkv) & 1);                            // 0 = k, 1 = v
+            const int64_t bt = row / (2 * Hkv);
+            const T* src = qkv + bt * ld + (int64_t)(H + which * Hkv + hk) * Dh + sub * 8;
+#pragma unroll
+            for (int u = 0; u < 8 / Elem<T>::VEC; ++u) ld_vec<T>(src + u * Elem<T>::VEC, f + u * Elem<T>::VEC);
+            slot = ((bt / Tn) * Hkv + hk) * cap + pos0 + bt % Tn;
+        }
+        float amax = 0.f, bad = 0.f;                                   // bad: the block holds a non-finite entry (it becomes scale byte 0xFF, nibbles 0)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float a = fabsf(f[e]);
+            if (a <= 3.402823466e38f) amax = fmaxf(amax, a);
+            else bad = 1.f;
+        }
+        amax = row_max<4>(amax);
+        bad = row_max<4>(bad);
+        const int ex = mx4_exponent(amax);
+        const float inv = mx4_inv_scale(ex);
+        if (live) {
+            unsigned w = 0u;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w |= mx4_encode(f[e] * inv) << (4 * e);
+            *reinterpret_cast<unsigned*>((which ? vq : kq) + slot * (Dh / 2) + sub * 4) = bad != 0.f ? 0u : w;
+            if ((sub & 3) == 0) (which ? vs : ks)[slot * (Dh / 32) + (sub >> 2)] = (uint8_t)(bad != 0.f ? 0xff : 127 + ex);
+        }
+    }
+}
+
+template <typename T>
+void launch_append_mxfp4(hipStream_t s, const T* qkv, uint8_t* kq, uint8_t* ks, uint8_t* vq, uint8_t* vs, int B, int Tn, int H, int Hkv, int Dh,
+                         int cap, int pos0) {
+    const int vpr = Dh / 8;
+    const int64_t rows = (int64_t)B * Tn * 2 * Hkv;
+#define MX4_APPEND(GL)                                                                                                           \
+    if (vpr <= GL) {                                                                                                             \
+        const int64_t wgs = (rows + 256 / GL - 1) / (256 / GL);                                                                  \
+        kv_append_mxfp4_kernel<T, GL><<<(int)(wgs > 65536 ? 65536 : wgs), 256, 0, s>>>(qkv, kq, ks, vq, vs, B, Tn, H, Hkv, Dh, cap, pos0); \
+        return;                                                                                                                  \
+    }
+    MX4_APPEND(4) MX4_APPEND(8) MX4_APPEND(16) MX4_APPEND(32) MX4_APPEND(64)
+#undef MX4_APPEND
+}
 
 }  // namespace
 
@@ -415,6 +491,37 @@ extern "C" int setok_attention_decode_gqa_fp8kv(void* stream, int dtype, const v
     if (B == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;
     const KvFp8 kv{k_q, k_e, v_q, v_e};
+    if (dtype == SETOK_BF16) return decode_t<bf16>(name, s, (const bf16*)q, ldq, kv, key_mask, (bf16*)out, ws, B, H, Hkv, Dh, cap, len, scale);
+    return decode_t<float>(name, s, (const float*)q, ldq, kv, key_mask, (float*)out, ws, B, H, Hkv, Dh, cap, len, scale);
+}
+
+extern "C" int setok_kv_append_mxfp4(void* stream, int dtype, const void* qkv, uint8_t* k_q, uint8_t* k_s, uint8_t* v_q, uint8_t* v_s, int B, int T, int H,
+                                     int Hkv, int Dh, int cap, int pos0) {
+    SETOK_CHECK_ARG(qkv && k_q && k_s && v_q && v_s, "setok_kv_append_mxfp4: null operand");
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_kv_append_mxfp4: bad dtype %d", dtype);
+    SETOK_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "setok_kv_append_mxfp4: bad shape B=%d T=%d H=%d Hkv=%d", B, T, H, Hkv);
+    SETOK_CHECK_ARG(Dh > 0 && Dh % 32 == 0 && Dh <= 512, "setok_kv_append_mxfp4: unsupported head dim %d (a multiple of 32, the MX block, at most 512)", Dh);
+    SETOK_CHECK_ARG(cap > 0 && pos0 >= 0 && (int64_t)pos0 + T <= cap, "setok_kv_append_mxfp4: slots [%d, %d + %d) exceed the cache (len > cap = %d)", pos0, pos0, T, cap);
+    SETOK_CHECK_ARG(aligned16(qkv) && aligned16(k_q) && aligned16(v_q), "setok_kv_append_mxfp4: qkv, k_q and v_q must be 16-byte aligned");
+    if (B == 0 || T == 0) return SETOK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH_T("setok_kv_append_mxfp4", (launch_append_mxfp4<bf16>(s, (const bf16*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, cap, pos0)),
+               (launch_append_mxfp4<float>(s, (const float*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, cap, pos0)));
+    SETOK_CHECK_LAUNCH("setok_kv_append_mxfp4");
+    return SETOK_OK;
+}
+
+extern "C" int setok_attention_decode_gqa_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                                  const uint8_t* v_q, const uint8_t* v_s, const uint8_t* key_mask, void* out, int B, int H, int Hkv,
+                                                  int Dh, int cap, int len, float scale, float* ws, int64_t ws_floats) {
+    const char* name = "setok_attention_decode_mxfp4kv";
+    SETOK_CHECK_ARG(Dh > 0 && Dh % 32 == 0, "%s: unsupported head dim %d (a multiple of 32, the MX block)", name, Dh);
+    if (int e = check_decode(name, "nibble caches", q && k_q && k_s && v_q && v_s && key_mask && out && ws, aligned16(q) && aligned16(k_q) && aligned16(v_q),
+                             dtype, ldq, B, H, Hkv, Dh, cap, len, KvMxfp4::CHUNK, ws_floats))
+        return e;
+    if (B == 0) return SETOK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const KvMxfp4 kv{{k_q, k_s}, {v_q, v_s}};
     if (dtype == SETOK_BF16) return decode_t<bf16>(name, s, (const bf16*)q, ldq, kv, key_mask, (bf16*)out, ws, B, H, Hkv, Dh, cap, len, scale);
     return decode_t<float>(name, s, (const float*)q, ldq, kv, key_mask, (float*)out, ws, B, H, Hkv, Dh, cap, len, scale);
 }

@@ -19,6 +19,9 @@
 // its scores are replaced by selection and its V row is zeroed in LDS before the tile is used (0 * NaN would reach the accumulators otherwise).
 // Everything else (fp32, other head dims) is one wave per (query row, query head, chunk) on a grid (B * Tn, H, chunks): attn_chunk_any_kernel of
 // attn_partials.h, the decode path's fallback, with the row's own limit len0 + i + 1.
+//   setok_attention_extend_gqa_mxfp4kv   the same over a cache stored as MXFP4 rows (include/setok_hip.h, "MXFP4 KV cache"): that wave-per-chunk
+//                                        kernel over the KvMxfp4 format for every head dim and element type — the functional path; an MFMA
+//                                        kernel over nibbles is a follow-up
 #include "common.h"
 #include "lds_mma.h"
 #include "attn_partials.h"
@@ -221,6 +224,17 @@ int extend_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, c
     return SETOK_OK;
 }
 
+template <typename T>
+int extend_mxfp4_t(hipStream_t s, const T* q, int64_t ldq, KvMxfp4 kv, const uint8_t* km, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh, int cap,
+                   int len0, float scale) {
+    const int nch = cdiv(len0 + Tn, EXT_CHUNK);
+    attn_chunk_any_kernel<T, KvMxfp4, EXT_CHUNK, true><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kv, km, ws, Tn, H, Hkv, Dh, cap, len0, scale);
+    SETOK_CHECK_LAUNCH("setok_attention_extend_mxfp4kv(chunks)");
+    attn_decode_merge_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, nch, H, Dh);
+    SETOK_CHECK_LAUNCH("setok_attention_extend_mxfp4kv(merge)");
+    return SETOK_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t setok_attention_extend_workspace(int dtype, int B, int Tn, int H, int Hkv, int Dh, int len0) {
@@ -252,4 +266,33 @@ extern "C" int setok_attention_extend_gqa(void* stream, int dtype, const void* q
                               scale);
     return extend_t<float>(s, (const float*)q, ldq, (const float*)k_cache, (const float*)v_cache, key_mask, (float*)out, workspace, B, Tn, H, Hkv, Dh, cap, len0,
                            scale);
+}
+
+extern "C" int64_t setok_attention_extend_mxfp4kv_workspace(int B, int Tn, int H, int Dh, int len0) {
+    if (B < 0 || Tn < 1 || H < 1 || Dh < 1 || len0 < 0) return 0;
+    return (int64_t)B * Tn * H * (((int64_t)len0 + Tn + EXT_CHUNK - 1) / EXT_CHUNK) * (Dh + 2);
+}
+
+extern "C" int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                                  const uint8_t* v_q, const uint8_t* v_s, const uint8_t* key_mask, void* out, int B, int Tn, int H,
+                                                  int Hkv, int Dh, int cap, int len0, float scale, float* workspace, int64_t workspace_floats) {
+    SETOK_CHECK_ARG(q && k_q && k_s && v_q && v_s && key_mask && out && workspace, "setok_attention_extend_mxfp4kv: null operand");
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_attention_extend_mxfp4kv: bad dtype %d", dtype);
+    SETOK_CHECK_ARG(B >= 0 && B <= 65535 && Tn >= 1 && H > 0 && H <= 65535 && Hkv > 0 && H % Hkv == 0,
+                    "setok_attention_extend_mxfp4kv: bad shape B=%d Tn=%d H=%d Hkv=%d", B, Tn, H, Hkv);
+    SETOK_CHECK_ARG(Dh > 0 && Dh % 32 == 0, "setok_attention_extend_mxfp4kv: unsupported head dim %d (a multiple of 32, the MX block)", Dh);
+    SETOK_CHECK_ARG(cap > 0 && len0 >= 0 && (int64_t)len0 + Tn <= cap,
+                    "setok_attention_extend_mxfp4kv: slots [%d, %d + %d) exceed the cache (len0 + Tn > cap = %d)", len0, len0, Tn, cap);
+    SETOK_CHECK_ARG((int64_t)B * Tn <= 0x7fffffffll && cdiv(len0 + Tn, EXT_CHUNK) <= 65535,
+                    "setok_attention_extend_mxfp4kv: B=%d Tn=%d H=%d len0=%d exceed the launch grid", B, Tn, H, len0);
+    SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_q) && aligned16(v_q),
+                    "setok_attention_extend_mxfp4kv: q rows (stride %lld) and the nibble caches must be 16-byte aligned", (long long)ldq);
+    const int64_t need = setok_attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, len0);
+    SETOK_CHECK_ARG(workspace_floats >= need, "setok_attention_extend_mxfp4kv: workspace of %lld floats, %lld needed", (long long)workspace_floats,
+                    (long long)need);
+    if (B == 0) return SETOK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const KvMxfp4 kv{{k_q, k_s}, {v_q, v_s}};
+    if (dtype == SETOK_BF16) return extend_mxfp4_t<bf16>(s, (const bf16*)q, ldq, kv, key_mask, (bf16*)out, workspace, B, Tn, H, Hkv, Dh, cap, len0, scale);
+    return extend_mxfp4_t<float>(s, (const float*)q, ldq, kv, key_mask, (float*)out, workspace, B, Tn, H, Hkv, Dh, cap, len0, scale);
 }

@@ -1,11 +1,12 @@
 // attn_partials.h — what the attention kernels that cut a sequence's keys into chunks share (attn_decode.hip, attn_extend.hip): every chunk leaves
 // fp32 partials — per (sequence, query head, chunk) Dh + 2 floats [max, sum, Dh accumulators] — in the caller's workspace, and a second launch merges a
 // query head's chunks in chunk order.  ONE definition of the merge and of the exponential both sides of it use: a partial is only meaningful to the
-// merge that rescales it.  Also here, once: the two cache formats as the kernels see them, and the wave-per-chunk kernel every head dim without a
+// merge that rescales it.  Also here, once: the cache formats (native, fp8, MXFP4) as the kernels see them, and the wave-per-chunk kernel every head dim without a
 // lane layout falls back to, whichever entry point it came through.
 #pragma once
 #include "common.h"
 #include "fp8.h"
+#include "mx4.h"
 
 namespace {
 
@@ -22,14 +23,15 @@ template <> struct Raw16<float> { typedef f32x4 type; };
 template <> struct Raw16<bf16> { typedef bf16x8 type; };
 
 // ---- the cache formats: one layer's cache as a kernel argument (by value) and what a kernel must know to read it ------------------------------
-// VEC elements per 16-byte load, CHUNK slots per decode chunk, Raw the 16 bytes in registers, decode() Raw -> VEC floats, at() one element (the
-// fallback's read).  SCALED: a row carries a power-of-two exponent byte (ke / ve), whose 2^e multiplies the finished dot product and the rounded
-// probability.
+// VEC elements per lane and load (16 bytes of a native or e4m3 row, 8 bytes of a nibble row), CHUNK slots per decode chunk, Raw the lane's piece in
+// registers, load() elements [i, i + VEC) of the K or V operand -> Raw, decode() Raw -> VEC floats, at() one element (the fallback's read).  SCALED:
+// a row carries a power-of-two exponent byte (ke / ve), whose 2^e multiplies the finished dot product and the rounded probability.
 template <typename T> struct KvNative {
     static constexpr int VEC = Elem<T>::VEC, CHUNK = SETOK_DECODE_CHUNK;
     static constexpr bool SCALED = false;
     typedef typename Raw16<T>::type Raw;
     const T *k, *v;
+    __device__ static inline Raw load(const T* p, int64_t i) { return *reinterpret_cast<const Raw*>(p + i); }
     __device__ static inline void decode(const Raw& r, float* f) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) f[e] = (float)r[e];
@@ -44,8 +46,37 @@ struct KvFp8 {                                                         // e4m3fn
     const int8_t* ke;
     const uint8_t* v;
     const int8_t* ve;
+    __device__ static inline Raw load(const uint8_t* p, int64_t i) { return *reinterpret_cast<const Raw*>(p + i); }
     __device__ static inline void decode(const Raw& r, float* f) { fp8w_decode16(r, f); }      // v_cvt_pk_f32_fp8: exact
     __device__ static inline float at(const uint8_t* p, int64_t i) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)p[i], false)[0]; }
+};
+// OCP MXFP4 rows (include/setok_hip.h, "MXFP4 KV cache"): Dh / 2 bytes of e2m1 nibbles + Dh / 32 e8m0 scale bytes per row.  An operand is the pair
+// (nibbles, scales); element i of it is nibble i under scale byte i / 32 (Dh % 32 == 0, so blocks never straddle rows).  A lane holds 16
+// elements — 8 nibble bytes and the scale byte it shares with its neighbour — and the hardware converter applies the scale, so decode() gives
+// exactly K', V' and nothing is left to scale afterwards.  A 0xFF scale byte makes the operand a NaN: 16 NaNs, which a slot that does not count
+// loses by selection like any other value.
+struct Mx4Rows {
+    const uint8_t* q;
+    const uint8_t* s;
+};
+struct Mx4Piece {
+    uint2 w;
+    unsigned s;
+};
+struct KvMxfp4 {
+    static constexpr int VEC = 16, CHUNK = SETOK_DECODE_CHUNK_MXFP4KV;
+    static constexpr bool SCALED = false;
+    typedef Mx4Piece Raw;
+    Mx4Rows k, v;
+    __device__ static inline Raw load(const Mx4Rows& p, int64_t i) { return Raw{*reinterpret_cast<const uint2*>(p.q + (i >> 1)), p.s[i >> 5]}; }
+    __device__ static inline void decode(const Raw& r, float* f) {
+        const float sc = mx4_scale(r.s);
+        mx4_f32x8(r.w.x, sc, f);
+        mx4_f32x8(r.w.y, sc, f + 8);
+    }
+    __device__ static inline float at(const Mx4Rows& p, int64_t i) {
+        return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4((unsigned)p.q[i >> 1], mx4_scale(p.s[i >> 5]), 0)[i & 1];
+    }
 };
 
 // ---- any head dim (Dh % 8 == 0): one wave per (query row, query head, chunk of CHUNK slots), a key per lane ------------------------------------

@@ -22,12 +22,15 @@ from . import ops
 class _KVFormat:
     """What differs between the cache formats, chosen once in `KVCache.__init__`: the per-layer tensor lists in the order both ops take them,
     `append(qkv, *tensors, T, H, pos0)`, `attend(q, *tensors, key_mask, H, length, scale, ws=, out=)`, the decode attention's slots per partial,
-    and whether the format can be extended by several tokens (`extend_attend`, `grown`)."""
+    whether the format can be extended by several tokens (`extend_attend`, `grown`) and, if so, the extend attention
+    `extend(q, *tensors, key_mask, H, Tn, len0, scale, ws=, out=)` with its workspace rule `extend_ws(B, Tn, H, Dh, len0, Hkv, dtype)`."""
     tensors: Tuple[List[torch.Tensor], ...]
     append: Callable
     attend: Callable
     chunk: int
     extendable: bool
+    extend: Optional[Callable] = None
+    extend_ws: Optional[Callable] = None
 
 
 class KVCache:
@@ -37,14 +40,23 @@ class KVCache:
     slots are filled and masked).  Memory: 2 * layers * B * Hkv * cap * Dh elements.
 
     `kv_format="fp8"` stores a row as Dh e4m3fn bytes + one int8 power-of-two exponent instead (`k_q`, `v_q` (B, Hkv, cap, Dh) uint8 and `k_e`, `v_e`
-    (B, Hkv, cap) int8 per layer; `k` and `v` are then empty): 2 * layers * B * Hkv * cap * (Dh + 1) bytes.  What differs between the formats is
-    one `_KVFormat` record."""
+    (B, Hkv, cap) int8 per layer; `k` and `v` are then empty): 2 * layers * B * Hkv * cap * (Dh + 1) bytes.
 
-    FORMATS = ("native", "fp8")
+    `kv_format="mxfp4"` stores a row as OCP MXFP4 (include/setok_hip.h, "MXFP4 KV cache"): `k_q`, `v_q` (B, Hkv, cap, Dh/2) uint8 — two e2m1 nibbles
+    per byte — and `k_s`, `v_s` (B, Hkv, cap, Dh/32) uint8 — one e8m0 scale byte per 32 elements; 2 * layers * B * Hkv * cap * (Dh/2 + Dh/32)
+    bytes, 68 per row at head dim 128 against fp8's 129 and 256 in 16 bits.  The kernels need Dh % 32 == 0 (`for_model` and `generate` refuse
+    anything else; the constructor allocates ceil(Dh/2) and ceil(Dh/32) columns and leaves the check to them).  Unlike the fp8 format it can be
+    extended by several tokens (`extend_attend`, `grown`), so it works with `LlamaModel.extend`, drafting, chunked prefill and turns.  Only the
+    cache is quantised: an unchunked prefill attends over its own unquantised q | k | v and only then stores them, while an `extend` — a window of
+    a chunked prefill — attends over the stored, quantised slots; so `prefill_chunk=N` over a quantised cache is not the unchunked function.
+
+    What differs between the formats is one `_KVFormat` record."""
+
+    FORMATS = ("native", "fp8", "mxfp4")
 
     def __init__(self, num_layers: int, B: int, Hkv: int, cap: int, Dh: int, dtype: torch.dtype, device, kv_format: str = "native"):
         if kv_format not in self.FORMATS:
-            raise ValueError(f"KVCache: kv_format={kv_format!r} is not one of 'native', 'fp8'")
+            raise ValueError(f"KVCache: kv_format={kv_format!r} is not one of 'native', 'fp8', 'mxfp4'")
         self.B, self.Hkv, self.cap, self.Dh = B, Hkv, cap, Dh
         self.num_layers, self.dtype, self.kv_format = num_layers, dtype, kv_format
         # zero-filled: the decode kernel reads masked slots below `len` before it discards them, so they must hold initialised memory
@@ -56,9 +68,18 @@ class KVCache:
             self.k_q, self.v_q = zeros((B, Hkv, cap, Dh), torch.uint8), zeros((B, Hkv, cap, Dh), torch.uint8)
             self.k_e, self.v_e = zeros((B, Hkv, cap), torch.int8), zeros((B, Hkv, cap), torch.int8)
             self._fmt = _KVFormat((self.k_q, self.k_e, self.v_q, self.v_e), ops.kv_append_fp8, ops.attention_decode_fp8kv, ops.DECODE_CHUNK_FP8KV, False)
+        elif kv_format == "mxfp4":
+            # a row is Dh / 2 nibble bytes + Dh / 32 e8m0 scale bytes (include/setok_hip.h, "MXFP4 KV cache"); zero bytes mean 0.0 * 2^-127
+            nq, ns = (Dh + 1) // 2, (Dh + 31) // 32
+            self.k_q, self.v_q = zeros((B, Hkv, cap, nq), torch.uint8), zeros((B, Hkv, cap, nq), torch.uint8)
+            self.k_s, self.v_s = zeros((B, Hkv, cap, ns), torch.uint8), zeros((B, Hkv, cap, ns), torch.uint8)
+            self._fmt = _KVFormat((self.k_q, self.k_s, self.v_q, self.v_s), ops.kv_append_mxfp4, ops.attention_decode_mxfp4kv,
+                                  ops.DECODE_CHUNK_MXFP4KV, True, ops.attention_extend_mxfp4kv,
+                                  lambda B, Tn, H, Dh, len0, Hkv, dtype: ops.attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, len0))
         else:
             self.k, self.v = zeros((B, Hkv, cap, Dh), dtype), zeros((B, Hkv, cap, Dh), dtype)
-            self._fmt = _KVFormat((self.k, self.v), ops.kv_append, ops.attention_decode, ops.DECODE_CHUNK, True)
+            self._fmt = _KVFormat((self.k, self.v), ops.kv_append, ops.attention_decode, ops.DECODE_CHUNK, True, ops.attention_extend,
+                                  ops.attention_extend_workspace)
         self.key_mask = torch.zeros((B, cap), dtype=torch.uint8, device=device)
         self.next_pos = torch.zeros(B, dtype=torch.int64, device=device)
         self.len = 0
@@ -67,8 +88,12 @@ class KVCache:
 
     @classmethod
     def for_model(cls, model, B: int, cap: int, device=None, kv_format: str = "native") -> "KVCache":
-        """A cache for `model` (a LlamaModel) with room for `cap` slots per sequence."""
+        """A cache for `model` (a LlamaModel) with room for `cap` slots per sequence.  ValueError, before anything is allocated, for
+        `kv_format="mxfp4"` on a head dim that is no multiple of 32 (the MX block)."""
         w = model.norm.weight
+        if kv_format == "mxfp4" and model.head_dim % 32 != 0:
+            raise ValueError(f"KVCache.for_model: kv_format='mxfp4' needs a head dim that is a multiple of 32 (the MX block), the model's is "
+                             f"{model.head_dim}; use kv_format='native' or 'fp8'")
         return cls(len(model.layers), B, model.num_kv_heads, cap, model.head_dim, w.dtype, device if device is not None else w.device, kv_format)
 
     def append(self, li: int, qkv: torch.Tensor, T: int, H: int, pos0: int) -> None:
@@ -81,12 +106,12 @@ class KVCache:
 
     def extend_attend(self, li: int, q: torch.Tensor, H: int, Tn: int, len0: int, scale: float, ws: torch.Tensor,
                       out: Optional[torch.Tensor]) -> torch.Tensor:
-        """Layer `li`: Tn query rows per (sequence, query head) against slots [0, len0 + Tn), causal inside the new rows (ops.attention_extend).  The
-        native format only: reading several query rows over e4m3 rows is a second kernel."""
+        """Layer `li`: Tn query rows per (sequence, query head) against slots [0, len0 + Tn), causal inside the new rows, in the cache's own format
+        (ops.attention_extend, ops.attention_extend_mxfp4kv).  Not the fp8 format: reading several query rows over e4m3 rows is a second kernel."""
         if not self._fmt.extendable:
             raise NotImplementedError("KVCache.extend_attend: extending an fp8 KV cache by several tokens is not implemented (the extend attention "
                                       "over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
-        return ops.attention_extend(q, self.k[li], self.v[li], self.key_mask, H, Tn, len0, scale, ws=ws, out=out)
+        return self._fmt.extend(q, *(t[li] for t in self._fmt.tensors), self.key_mask, H, Tn, len0, scale, ws=ws, out=out)
 
     def grown(self, cap: int) -> "KVCache":
         """A cache of capacity `cap` >= self.len holding the same filled slots, mask and positions (`cap` is part of the layout, so growing copies)."""
@@ -94,9 +119,9 @@ class KVCache:
             raise NotImplementedError("KVCache.grown: an fp8 KV cache cannot be extended by several tokens, so it is never grown")
         if cap < self.len:
             raise ValueError(f"KVCache.grown: cap={cap} is below the {self.len} filled slots")
-        new = KVCache(self.num_layers, self.B, self.Hkv, cap, self.Dh, self.dtype, self.key_mask.device)
+        new = KVCache(self.num_layers, self.B, self.Hkv, cap, self.Dh, self.dtype, self.key_mask.device, self.kv_format)
         n = self.len
-        for dst, src in ((new.k, self.k), (new.v, self.v)):
+        for dst, src in zip(new._fmt.tensors, self._fmt.tensors):
             for d, t in zip(dst, src):
                 d[:, :, :n].copy_(t[:, :, :n])
         new.key_mask[:, :n].copy_(self.key_mask[:, :n])
@@ -144,7 +169,7 @@ class KVCache:
         extend of Tn rows behind len0 slots needs."""
         need = ops.attention_decode_workspace(self.B, H, self.Dh, self.cap, self._fmt.chunk)
         if Tn > 0:
-            need = max(need, ops.attention_extend_workspace(self.B, Tn, H, self.Dh, len0, self.Hkv, self.dtype))
+            need = max(need, self._fmt.extend_ws(self.B, Tn, H, self.Dh, len0, self.Hkv, self.dtype))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1), dtype=torch.float32, device=self.key_mask.device)
         return self._ws

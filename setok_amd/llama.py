@@ -388,7 +388,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
             y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
             qkv = lin8(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
             ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
-            cache.append(li, qkv, 1, H, slot)                                       # (native or fp8: the cache's format decides these two calls)
+            cache.append(li, qkv, 1, H, slot)                                       # (native, fp8 or mxfp4: the cache's format decides these two calls)
             o = cache.attend(li, qkv, H, slot + 1, dh ** -0.5, ws, o)
             if fp8:                                                                 # the same step on the fp8 bytes (mxfp4 nibbles): four weight-streaming GEMMs
                 lin8(o, *L["wo"], residual=x, out=x, scratch=big)
@@ -412,6 +412,8 @@ class LlamaModel(PackCacheMixin, nn.Module):
         1 = attended (None = all): row i of sequence b is rotated to cache.next_pos[b] + (the attended rows before i in the chunk); a masked row's slot
         stays masked and its hidden state means nothing.  HF LlamaDecoderLayer.forward with `past_key_values` on a Tn-token input; the GEMMs are the
         prefill's at M = B * Tn (fp8 weights: `decode_step`'s streaming GEMM up to FP8W_MAX_M rows, the dequantise scratch above).
+        Over an mxfp4 KV cache the rows are quantised on append and the attention reads the stored slots, the new rows' own included
+        (ops.attention_extend_mxfp4kv: the functional kernel, every head dim).
         Refused with the cache untouched: an fp8 KV cache (NotImplementedError), a wrong B, Tn == 0 on an empty cache, len + Tn > cap (ValueError)."""
         self._refuse_unmerged("LlamaModel.extend")
         B, Tn, D = inputs_embeds.shape
@@ -668,6 +670,14 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         cache): the prefill is unchanged, a decode step quantises the new token's k / v on append and attends over the stored values.  It is
         independent of `quantize_fp8_()`.  "native" (the default) is the cache in the model's element type.
 
+        `kv_cache="mxfp4"` keeps the cache as OCP MXFP4 rows — e2m1 nibbles with one e8m0 scale byte per 32 elements, 68 bytes per row at head
+        dim 128 against fp8's 129 and 256 in 16 bits; the head dim must be a multiple of 32 (ValueError before any device call).  Only the cache
+        is quantised: an unchunked prefill attends over its own unquantised q | k | v (`prefill` with an mxfp4 cache stays `torch.equal` to
+        `_forward`) and stores the quantised rows; every later step attends over the stored values.  Unlike the fp8 cache it works with `draft=`,
+        `prefill_chunk=`, `past=` / `return_past` and `LlamaModel.extend`.  A window of a chunked prefill attends over the stored, quantised
+        slots — its own rows included — so `prefill_chunk=N` over a quantised cache is NOT the unchunked function (over the native cache it is).
+        The extend attention over nibbles is a functional kernel without MFMA: long windows and turns are slow.
+
         `sampler=` (a generation.Sampler: temperature, top_k, top_p and the uniforms, given or drawn from a generator) replaces the step's argmax
         by one `setok_sample_rows` launch; everything else in the loop is the same, and `sampler=None` is the greedy path bit for bit.  A row
         whose logits hold a NaN or +inf (HF: "probability tensor contains either inf, nan") raises RuntimeError naming the sequence and the step:
@@ -742,7 +752,10 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         if max_new_tokens < 1:
             raise ValueError("SetokimLlamaPrefill.generate: max_new_tokens must be at least 1")
         if kv_cache not in KVCache.FORMATS:
-            raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8'")
+            raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8', 'mxfp4'")
+        if kv_cache == "mxfp4" and self.model.head_dim % 32 != 0:
+            raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache='mxfp4' needs a head dim that is a multiple of 32 (the MX block), the "
+                             f"model's is {self.model.head_dim}; use kv_cache='native' or 'fp8'")
         if sampler is not None and not isinstance(sampler, Sampler):
             raise TypeError(f"SetokimLlamaPrefill.generate: sampler must be a generation.Sampler or None, got {type(sampler).__name__}")
         K = 0

@@ -862,6 +862,63 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tens
     return out
 
 
+# ---- the MXFP4 KV cache (csrc/attn_decode.hip, csrc/attn_extend.hip; include/setok_hip.h, "MXFP4 KV cache") --------------------------------------
+DECODE_CHUNK_MXFP4KV = 256                        # SETOK_DECODE_CHUNK_MXFP4KV of include/setok_hip.h
+
+
+def _mxfp4kv_shapes(k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor) -> Tuple[int, int, int, int]:
+    B, Hkv, cap, half = k_q.shape
+    Dh = 2 * half
+    if Dh % MXFP4_BLOCK != 0:
+        raise ValueError(f"the MXFP4 KV cache needs a head dim that is a multiple of {MXFP4_BLOCK}, the MX block; the nibble rows hold {Dh} elements")
+    assert v_q.shape == k_q.shape and k_q.dtype == v_q.dtype == torch.uint8 and k_q.is_contiguous() and v_q.is_contiguous()
+    assert k_s.shape == v_s.shape == (B, Hkv, cap, Dh // MXFP4_BLOCK) and k_s.dtype == v_s.dtype == torch.uint8
+    assert k_s.is_contiguous() and v_s.is_contiguous()
+    return B, Hkv, cap, Dh
+
+
+def kv_append_mxfp4(qkv: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, T: int, H: int, pos0: int) -> None:
+    """kv_append into an MXFP4 cache: the post-rotary k / v rows of qkv are quantised (e2m1 nibbles + one e8m0 scale byte per 32 elements, the
+    rule of quantize_mxfp4_rows) into slots [pos0, pos0 + T) of k_q / v_q (B, Hkv, cap, Dh/2) uint8 and k_s / v_s (B, Hkv, cap, Dh/32) uint8."""
+    B, Hkv, cap, Dh = _mxfp4kv_shapes(k_q, k_s, v_q, v_s)
+    assert qkv.shape == (B * T, (H + 2 * Hkv) * Dh) and qkv.is_contiguous()
+    _lib.call("setok_kv_append_mxfp4", _stream(), _code(qkv.dtype), _p(qkv), _p(k_q), _p(k_s), _p(v_q), _p(v_s), B, T, H, Hkv, Dh, cap, pos0)
+
+
+def attention_decode_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, key_mask: Tensor, H: int, length: int, scale: float,
+                             ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """attention_decode over an MXFP4 cache (the keys / values are value(nibble) * 2^(scale byte - 127), exactly); q and the result in q.dtype."""
+    B, Hkv, cap, Dh = _mxfp4kv_shapes(k_q, k_s, v_q, v_s)
+    return _attention_decode("setok_attention_decode_gqa_mxfp4kv", q, (_p(k_q), _p(k_s), _p(v_q), _p(v_s)), key_mask, B, H, Hkv, Dh, cap, length, scale,
+                             DECODE_CHUNK_MXFP4KV, ws, out)
+
+
+def attention_extend_mxfp4kv_workspace(B: int, Tn: int, H: int, Dh: int, len0: int) -> int:
+    """Floats of workspace setok_attention_extend_gqa_mxfp4kv needs: B * Tn * H * ceil((len0 + Tn) / EXTEND_CHUNK) * (Dh + 2), whatever the
+    element type (one partial per chunk: attention_extend_workspace's span rule does not apply)."""
+    return B * Tn * H * ((len0 + Tn + EXTEND_CHUNK - 1) // EXTEND_CHUNK) * (Dh + 2)
+
+
+def attention_extend_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, key_mask: Tensor, H: int, Tn: int, len0: int,
+                             scale: float, ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """attention_extend over an MXFP4 cache, which already holds the new rows' quantised keys / values in slots [len0, len0 + Tn).  The
+    functional path: one wave per (query row, query head, chunk) for every head dim and element type, no MFMA."""
+    B, Hkv, cap, Dh = _mxfp4kv_shapes(k_q, k_s, v_q, v_s)
+    assert Tn >= 1 and len0 >= 0 and len0 + Tn <= cap, f"attention_extend_mxfp4kv: slots [{len0}, {len0} + {Tn}) exceed the cache (cap = {cap})"
+    assert q.shape[0] == B * Tn and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, cap)
+    need = attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, len0)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B * Tn, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B * Tn, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_extend_gqa_mxfp4kv", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_q), _p(k_s), _p(v_q), _p(v_s),
+              _p(key_mask), _p(out), B, Tn, H, Hkv, Dh, cap, len0, scale, _p(ws), ws.numel())
+    return out
+
+
 def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """int64 (rows,): the lowest index of each row's maximum; x (rows, V) with any row stride."""
     rows, V = x.shape

@@ -7,7 +7,8 @@ to produce token n + 1 before: the whole prefill again over the sequence grown b
     python tools/bench_generate.py --weights fp8 ...                    # any of the above with the stack in fp8 storage (quantize_fp8_); mxfp4: quantize_mxfp4_
     python tools/bench_generate.py --compare-weights [--rounds 3]       # native, fp8 and mxfp4 arms alternated in one process: decode step + the four GEMMs
     python tools/bench_generate.py --compare-bands [--rounds 3]         # linear_fp8w's 16 / 32 / 64-column bands alternated in one process, four GEMMs
-    python tools/bench_generate.py --compare-kv [--attention-only]      # native and fp8 KV caches alternated in one process: the decode step, or the attention pair alone
+    python tools/bench_generate.py --compare-kv [--attention-only]      # native, fp8 and mxfp4 KV caches alternated in one process: the decode step (and two
+                                                                        # `extend` calls, native against mxfp4), or the attention pair alone
 
 Prints one JSON line.  Per batch size, in one process:
   (a) ms per token the old way: forward(inputs_embeds of T' + 1 positions, last_token_only=True);
@@ -194,11 +195,66 @@ def _fp8_twin(c):
     return f
 
 
+def _mxfp4_twin(c):
+    """The mxfp4 cache that holds what the native cache `c` holds, quantised block by block (the library's own quantiser: the same rule)."""
+    from setok_amd import ops
+    from setok_amd.generation import KVCache
+    f = KVCache(len(c.k), c.B, c.Hkv, c.cap, c.Dh, c.dtype, c.key_mask.device, kv_format="mxfp4")
+    for li in range(len(c.k)):
+        for src, q, sc in ((c.k[li], f.k_q[li], f.k_s[li]), (c.v[li], f.v_q[li], f.v_s[li])):
+            ops.quantize_mxfp4_rows(src.view(-1, c.Dh), q=q.view(-1, c.Dh // 2), s=sc.view(-1, c.Dh // 32))
+    f.key_mask.copy_(c.key_mask)
+    f.next_pos.copy_(c.next_pos)
+    f.len = c.len
+    return f
+
+
+def _versus(r, a, b):
+    """Arm `a` against arm `b` of one cell: the ratio of the medians, and whether the medians differ by more than the larger of the two arms'
+    spreads (max - min over the rounds)."""
+    gap = abs(r[a]["median"] - r[b]["median"])
+    return dict(ratio=round(r[a]["median"] / r[b]["median"], 3),
+                exceeds_the_larger_spread=gap > max(r[a]["max"] - r[a]["min"], r[b]["max"] - r[b]["min"]))
+
+
+def _compare_extend(a, llm, g, dev, dt, rnd):
+    """One `LlamaModel.extend` of Tn rows behind len0 filled slots at B = 1, over the native cache and over its mxfp4 twin, alternated round by
+    round: 8 rows behind 2048 slots (a verify-shaped call) and 512 rows behind 512 (a window of a chunked prefill, a turn)."""
+    from setok_amd.generation import KVCache
+    res = {}
+    for len0, Tn in ((2048, 8), (512, 512)):
+        native = KVCache(a.layers, 1, H, len0 + Tn, DH, dt, dev)
+        for t in native.k + native.v:
+            t.normal_(0.0, 1.0, generator=g)
+        _set_len(native, len0)
+        caches = {"native": native, "mxfp4": _mxfp4_twin(native)}
+        x = rnd(1, Tn, D)
+
+        def fn(k):
+            _set_len(caches[k], len0)
+            return llm.model.extend(x, caches[k])
+
+        for k in caches:
+            _time(lambda: fn(k), 1)
+        runs = {k: [] for k in caches}
+        for _ in range(a.rounds):
+            for k in caches:
+                runs[k].append(_time(lambda: fn(k), a.reps))
+        r = {k: _spread(v) for k, v in runs.items()}
+        r["mxfp4_vs_native"] = _versus(r, "mxfp4", "native")
+        res[f"len0_{len0}_Tn{Tn}"] = r
+        del caches, native
+        torch.cuda.empty_cache()
+    return res
+
+
 def _compare_kv(a, g, dev, dt, rnd):
-    """The native and the fp8 KV cache in ONE process, alternated round by round after a warm-up, every timing ended by a device synchronise,
-    `--rounds` runs of `--reps` steps per arm: the decode step of one model over the two caches — or, with --attention-only, the decode-attention
-    launch pair over every layer's cache — at cache lengths prompt + 1 and prompt + new, with the pair's rate in TB/s of LIVE cache bytes (codes
-    + exponents in the fp8 arm).  The fp8 cache holds the native cache's random rows, quantised.  Every run is appended to `--out`."""
+    """The native, the fp8 and the mxfp4 KV cache in ONE process, alternated round by round after a warm-up, every timing ended by a device
+    synchronise, `--rounds` runs of `--reps` steps per arm: the decode step of one model over the three caches — or, with --attention-only, the
+    decode-attention launch pair over every layer's cache — at cache lengths prompt + 1 and prompt + new, with the pair's rate in TB/s of LIVE
+    cache bytes (codes + exponents in the fp8 arm, nibbles + scale bytes in the mxfp4 arm).  The quantised caches hold the native cache's random
+    rows, quantised.  Without --attention-only the run also times two `extend` calls over the native and the mxfp4 cache (_compare_extend).
+    Every run is appended to `--out`."""
     from setok_amd import ops
     from setok_amd.generation import KVCache
     T, N = a.prompt, a.new
@@ -209,7 +265,7 @@ def _compare_kv(a, g, dev, dt, rnd):
         for t in native.k + native.v:
             t.normal_(0.0, 1.0, generator=g)
         _set_len(native, T)
-        caches = {"native": native, "fp8": _fp8_twin(native)}
+        caches = {"native": native, "fp8": _fp8_twin(native), "mxfp4": _mxfp4_twin(native)}
         e1, q = rnd(B, D), rnd(B, 3 * D)
         out = torch.empty(B, H * DH, dtype=dt, device=dev)
         rb = dict(kv_cache_gb={k: round(c.nbytes() / 1e9, 3) for k, c in caches.items()})
@@ -235,9 +291,10 @@ def _compare_kv(a, g, dev, dt, rnd):
             r = {k: _spread(v) for k, v in runs.items()}
             r["fp8_over_native_median"] = round(r["fp8"]["median"] / r["native"]["median"], 3)
             r["faster_by_more_than_the_spread"] = r["fp8"]["max"] < r["native"]["min"]
+            r["mxfp4_vs_native"], r["mxfp4_vs_fp8"] = _versus(r, "mxfp4", "native"), _versus(r, "mxfp4", "fp8")
             if a.attention_only:
                 rows = 2.0 * a.layers * B * H * length                   # K and V rows the pair reads (Hkv = H)
-                for k, per_row in (("native", DH * 2), ("fp8", DH + 1)):
+                for k, per_row in (("native", DH * 2), ("fp8", DH + 1), ("mxfp4", DH // 2 + DH // 32)):
                     r[k]["live_cache_gb"] = round(rows * per_row / 1e9, 3)
                     r[k]["tb_per_s"] = round(rows * per_row / (r[k]["median"] * 1e-3) / 1e12, 3)
             rb[f"len{length}"] = r
@@ -245,11 +302,15 @@ def _compare_kv(a, g, dev, dt, rnd):
         del caches, native
         torch.cuda.empty_cache()
     what = "decode-attention launch pair (chunks + merge) over all layers' caches" if a.attention_only else "decode step"
+    extend = None if a.attention_only else _compare_extend(a, llm, g, dev, dt, rnd)
     run = dict(workload=f"cfg5 LLM decode, Llama at Vicuna-7B dims, bf16: the KV cache native (bf16) against fp8 e4m3 rows + a power-of-two exponent "
-                        f"per row; ms per {what}, arms alternated in one process",
+                        f"per row and against MXFP4 rows (e2m1 nibbles + an e8m0 scale byte per 32 elements); ms per {what}, arms alternated in "
+                        f"one process",
                measured="attention_pair" if a.attention_only else "decode_step", layers=a.layers, prompt=T, new_tokens=N, reps=a.reps, rounds=a.rounds,
-               decode_chunk=dict(native=ops.DECODE_CHUNK, fp8=ops.DECODE_CHUNK_FP8KV), device=torch.cuda.get_device_name(0), results=res,
-               peak_bytes=torch.cuda.max_memory_allocated())
+               decode_chunk=dict(native=ops.DECODE_CHUNK, fp8=ops.DECODE_CHUNK_FP8KV, mxfp4=ops.DECODE_CHUNK_MXFP4KV),
+               device=torch.cuda.get_device_name(0), results=res, peak_bytes=torch.cuda.max_memory_allocated())
+    if extend is not None:
+        run["extend_B1_ms"] = extend
     runs = []
     if os.path.isfile(a.out):
         with open(a.out) as f:
