@@ -2,14 +2,16 @@
 keeps between steps as HF's `past_key_values` (:99,133,189), and what it returns.
 
 `KVCache` is allocated once per `generate` call; `LlamaModel.prefill` fills slots [0, T') of every layer, every `LlamaModel.decode_step` appends
-one slot for all sequences, `LlamaModel.extend` appends Tn >= 1 slots (chunked prefill, the next turn of a conversation).  The loop itself is
-`SetokimLlamaPrefill.generate` (llama.py); `GenerationState` is what it hands back so that a later call can continue from the same cache.
+one slot for all sequences, `LlamaModel.extend` appends Tn >= 1 slots (chunked prefill, the next turn of a conversation).  The loop is here too, as
+the plain functions `SetokimLlamaPrefill.generate` (llama.py) calls in turn: `check_request` (every refusal that needs no device call), `feed_prompt`,
+then `loop_plain`, `loop_beams` or `loop_speculative`; `GenerationState` is what it hands back so that a later call can continue from the same cache.
 `Drafter` / `LookupDrafter` are the sources of proposals for `generate(draft=...)`, which verifies K drafted tokens per `extend`.  `BeamSearch` is the
 setting of `generate(beams=...)`, which decodes on `KVCache.expanded(num_beams)` and re-points the beams' slots with `KVCache.reorder` every step.
 `LogitsProcessors` is the setting of `generate(processors=...)`, which changes a step's logits before a token is selected."""
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Tuple
 
@@ -21,16 +23,22 @@ from . import ops
 @dataclass
 class _KVFormat:
     """What differs between the cache formats, chosen once in `KVCache.__init__`: the per-layer tensor lists in the order both ops take them,
-    `append(qkv, *tensors, T, H, pos0)`, `attend(q, *tensors, key_mask, H, length, scale, ws=, out=)`, the decode attention's slots per partial,
-    whether the format can be extended by several tokens (`extend_attend`, `grown`) and, if so, the extend attention
+    `append(qkv, *tensors, T, H, pos0)`, `attend(q, *tensors, key_mask, H, length, scale, ws=, out=)`, the decode attention's slots per partial
+    and, where the format can be extended by several tokens (`KVCache.extendable`), the extend attention
     `extend(q, *tensors, key_mask, H, Tn, len0, scale, ws=, out=)` with its workspace rule `extend_ws(B, Tn, H, Dh, len0, Hkv, dtype)`."""
     tensors: Tuple[List[torch.Tensor], ...]
     append: Callable
     attend: Callable
     chunk: int
-    extendable: bool
     extend: Optional[Callable] = None
     extend_ws: Optional[Callable] = None
+
+
+def check_kv_head_dim(kv_format: str, head_dim: int, who: str, arg: str) -> None:
+    """The one head-dim rule of the cache formats: the mxfp4 kernels need whole MX blocks.  ValueError naming the caller `who` and its argument `arg`."""
+    if kv_format == "mxfp4" and head_dim % 32 != 0:
+        raise ValueError(f"{who}: {arg}='mxfp4' needs a head dim that is a multiple of 32 (the MX block), the model's is {head_dim}; "
+                         f"use {arg}='native' or 'fp8'")
 
 
 class KVCache:
@@ -53,6 +61,7 @@ class KVCache:
     What differs between the formats is one `_KVFormat` record."""
 
     FORMATS = ("native", "fp8", "mxfp4")
+    EXTENDABLE = ("native", "mxfp4")                       # the formats with an extend attention; reading several query rows over e4m3 rows is a follow-up kernel
 
     def __init__(self, num_layers: int, B: int, Hkv: int, cap: int, Dh: int, dtype: torch.dtype, device, kv_format: str = "native"):
         if kv_format not in self.FORMATS:
@@ -67,18 +76,18 @@ class KVCache:
             # a row is Dh e4m3fn bytes + one int8 exponent and means value(code) * 2^exponent (include/setok_hip.h, "FP8 KV cache")
             self.k_q, self.v_q = zeros((B, Hkv, cap, Dh), torch.uint8), zeros((B, Hkv, cap, Dh), torch.uint8)
             self.k_e, self.v_e = zeros((B, Hkv, cap), torch.int8), zeros((B, Hkv, cap), torch.int8)
-            self._fmt = _KVFormat((self.k_q, self.k_e, self.v_q, self.v_e), ops.kv_append_fp8, ops.attention_decode_fp8kv, ops.DECODE_CHUNK_FP8KV, False)
+            self._fmt = _KVFormat((self.k_q, self.k_e, self.v_q, self.v_e), ops.kv_append_fp8, ops.attention_decode_fp8kv, ops.DECODE_CHUNK_FP8KV)
         elif kv_format == "mxfp4":
             # a row is Dh / 2 nibble bytes + Dh / 32 e8m0 scale bytes (include/setok_hip.h, "MXFP4 KV cache"); zero bytes mean 0.0 * 2^-127
             nq, ns = (Dh + 1) // 2, (Dh + 31) // 32
             self.k_q, self.v_q = zeros((B, Hkv, cap, nq), torch.uint8), zeros((B, Hkv, cap, nq), torch.uint8)
             self.k_s, self.v_s = zeros((B, Hkv, cap, ns), torch.uint8), zeros((B, Hkv, cap, ns), torch.uint8)
             self._fmt = _KVFormat((self.k_q, self.k_s, self.v_q, self.v_s), ops.kv_append_mxfp4, ops.attention_decode_mxfp4kv,
-                                  ops.DECODE_CHUNK_MXFP4KV, True, ops.attention_extend_mxfp4kv,
+                                  ops.DECODE_CHUNK_MXFP4KV, ops.attention_extend_mxfp4kv,
                                   lambda B, Tn, H, Dh, len0, Hkv, dtype: ops.attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, len0))
         else:
             self.k, self.v = zeros((B, Hkv, cap, Dh), dtype), zeros((B, Hkv, cap, Dh), dtype)
-            self._fmt = _KVFormat((self.k, self.v), ops.kv_append, ops.attention_decode, ops.DECODE_CHUNK, True, ops.attention_extend,
+            self._fmt = _KVFormat((self.k, self.v), ops.kv_append, ops.attention_decode, ops.DECODE_CHUNK, ops.attention_extend,
                                   ops.attention_extend_workspace)
         self.key_mask = torch.zeros((B, cap), dtype=torch.uint8, device=device)
         self.next_pos = torch.zeros(B, dtype=torch.int64, device=device)
@@ -91,10 +100,13 @@ class KVCache:
         """A cache for `model` (a LlamaModel) with room for `cap` slots per sequence.  ValueError, before anything is allocated, for
         `kv_format="mxfp4"` on a head dim that is no multiple of 32 (the MX block)."""
         w = model.norm.weight
-        if kv_format == "mxfp4" and model.head_dim % 32 != 0:
-            raise ValueError(f"KVCache.for_model: kv_format='mxfp4' needs a head dim that is a multiple of 32 (the MX block), the model's is "
-                             f"{model.head_dim}; use kv_format='native' or 'fp8'")
+        check_kv_head_dim(kv_format, model.head_dim, "KVCache.for_model", "kv_format")
         return cls(len(model.layers), B, model.num_kv_heads, cap, model.head_dim, w.dtype, device if device is not None else w.device, kv_format)
+
+    @property
+    def extendable(self) -> bool:
+        """Can the cache take several tokens per sequence at once (`extend_attend`, `grown`: extend, chunked prefill, turns, drafting)?  Not fp8."""
+        return self.kv_format in self.EXTENDABLE
 
     def append(self, li: int, qkv: torch.Tensor, T: int, H: int, pos0: int) -> None:
         """Layer `li`: the post-rotary k / v columns of the fused qkv buffer -> slots [pos0, pos0 + T), in the cache's own format."""
@@ -108,14 +120,14 @@ class KVCache:
                       out: Optional[torch.Tensor]) -> torch.Tensor:
         """Layer `li`: Tn query rows per (sequence, query head) against slots [0, len0 + Tn), causal inside the new rows, in the cache's own format
         (ops.attention_extend, ops.attention_extend_mxfp4kv).  Not the fp8 format: reading several query rows over e4m3 rows is a second kernel."""
-        if not self._fmt.extendable:
+        if not self.extendable:
             raise NotImplementedError("KVCache.extend_attend: extending an fp8 KV cache by several tokens is not implemented (the extend attention "
                                       "over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
         return self._fmt.extend(q, *(t[li] for t in self._fmt.tensors), self.key_mask, H, Tn, len0, scale, ws=ws, out=out)
 
     def grown(self, cap: int) -> "KVCache":
         """A cache of capacity `cap` >= self.len holding the same filled slots, mask and positions (`cap` is part of the layout, so growing copies)."""
-        if not self._fmt.extendable:
+        if not self.extendable:
             raise NotImplementedError("KVCache.grown: an fp8 KV cache cannot be extended by several tokens, so it is never grown")
         if cap < self.len:
             raise ValueError(f"KVCache.grown: cap={cap} is below the {self.len} filled slots")
@@ -227,7 +239,7 @@ class Sampler:
 
     def select(self, logits: torch.Tensor, step: int) -> torch.Tensor:
         """int64 (B,): the step's tokens, -1 for a row whose logits hold a NaN or +inf or no finite entry."""
-        return ops.sample_rows(logits, self.uniforms(step, logits.shape[0], logits.device), self.temperature, self.top_k, self.top_p)
+        return _select(logits, self, self.uniforms(step, logits.shape[0], logits.device))
 
 
 class BeamSearch:
@@ -344,6 +356,21 @@ class GenerationState:
     cache: KVCache
     pending: torch.Tensor
 
+    @classmethod
+    def after_plain_loop(cls, cache: KVCache, seq: torch.Tensor, eos: Optional[torch.Tensor], fed0: int) -> "GenerationState":
+        """The state behind the plain loop: of the n emitted tokens seq (B, n) the stack has consumed the first n - 1 (slots fed0 .. fed0 + n - 2).  A
+        sequence's real tokens end with its first eos: the pads behind it that were fed are masked out and its next position is set back by their
+        number; its last real token is pending iff it was never fed (the sequence did not finish before the last step)."""
+        B, n = seq.shape
+        real = torch.full((B,), n, dtype=torch.int64, device=seq.device)
+        if eos is not None:
+            hit = torch.isin(seq, eos)
+            real = torch.where(hit.any(dim=1), hit.long().argmax(dim=1) + 1, real)
+        j = torch.arange(n - 1, device=seq.device)[None]
+        cache.key_mask[:, fed0:fed0 + n - 1] = (j < real[:, None]).to(torch.uint8)
+        cache.next_pos = cache.next_pos - (n - 1 - real).clamp_min(0)
+        return cls(cache=cache, pending=torch.where(real == n, seq[:, -1], torch.full_like(real, -1)))
+
 
 @dataclass
 class GenerateOutput:
@@ -441,3 +468,342 @@ class LookupDrafter(Drafter):
 
     def propose(self, pending):
         return self._launch()
+
+
+# ---- the parts of `SetokimLlamaPrefill.generate` (llama.py): the refusals, feeding the prompt, and the three loops -----------------------------------
+_SAMPLING_ARGS = ("temperature", "top_p", "top_k", "num_beams", "penalty_alpha", "repetition_penalty")      # generate(): named so that they are refused by name
+
+
+# A `generate` call once `check_request` has let it through: `eos_ids` a list or None, K drafts per round and C beam candidates per step (0 without).
+Request = namedtuple("Request", "comp_images max_new eos_ids pad_token_id kv_cache sampler prefill_chunk cache_capacity past draft K beams C processors "
+                                "as_dict want_hidden want_logits want_scores want_past")
+
+
+def check_request(lm, *, comp_images, images, position_ids, max_new_tokens, eos_token_id, pad_token_id, do_sample, return_dict_in_generate,
+                  output_hidden_states, output_logits, kv_cache, sampler, prefill_chunk, return_past, past, cache_capacity, draft, beams, processors,
+                  output_scores, unsupported) -> Request:
+    """Every refusal of `lm.generate` (lm: a SetokimLlamaPrefill) that needs no device call, in the order they have always fired, and the request
+    the rest of the call works from."""
+    who = "SetokimLlamaPrefill.generate"
+    lm.model._refuse_unmerged(who)
+    sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
+    if do_sample or sampling:
+        raise NotImplementedError(f"{who}: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "
+                                  "is the implemented mode; sampling and beam search are not implemented on the HIP path")
+    unknown = [k for k in unsupported if k not in _SAMPLING_ARGS]
+    if unknown:
+        raise TypeError(f"{who}: unexpected arguments {unknown}")
+    if images is not None:
+        if comp_images is not None:
+            raise ValueError(f"{who}: pass the images as `comp_images` or as `images`, not both")
+        comp_images = images
+    if max_new_tokens < 1:
+        raise ValueError(f"{who}: max_new_tokens must be at least 1")
+    if kv_cache not in KVCache.FORMATS:
+        raise ValueError(f"{who}: kv_cache={kv_cache!r} is not one of 'native', 'fp8', 'mxfp4'")
+    check_kv_head_dim(kv_cache, lm.model.head_dim, who, "kv_cache")
+    if sampler is not None and not isinstance(sampler, Sampler):
+        raise TypeError(f"{who}: sampler must be a generation.Sampler or None, got {type(sampler).__name__}")
+    K = 0
+    if draft is not None:
+        if not isinstance(draft, Drafter):
+            raise TypeError(f"{who}: draft must be a generation.Drafter or None, got {type(draft).__name__}")
+        K = draft.K
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPEC_MAX_K:
+            raise ValueError(f"{who}: draft.K={K!r} must be an int in [1, {ops.SPEC_MAX_K}]")
+        if kv_cache not in KVCache.EXTENDABLE:
+            raise NotImplementedError(f"{who}: draft= with kv_cache='fp8' is not implemented (a round extends the cache by "
+                                      "K + 1 tokens, and the extend attention over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
+    if beams is not None:
+        if not isinstance(beams, BeamSearch):
+            raise TypeError(f"{who}: beams must be a generation.BeamSearch or None, got {type(beams).__name__}")
+        for name, given in (("sampler=", sampler is not None), ("draft=", draft is not None), ("past=", past is not None),
+                            ("return_past=True", bool(return_past))):
+            if given:
+                raise NotImplementedError(f"{who}: beams= with {name} is not implemented (beam sampling, drafting into beams and continuing a beam state are not built)")
+    eos_ids = None if eos_token_id is None else [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
+    n_eos = 0 if eos_ids is None else len(eos_ids)
+    C = 0 if beams is None else beams.candidates(n_eos, lm.lm_head.weight.shape[0])
+    if processors is not None:
+        if not isinstance(processors, LogitsProcessors):
+            raise TypeError(f"{who}: processors must be a generation.LogitsProcessors or None, got {type(processors).__name__}")
+        if beams is not None:
+            raise NotImplementedError(f"{who}: processors= with beams= is not implemented (HF applies its processors to the beams' log-probabilities, which is a different rule)")
+        if past is not None:
+            raise NotImplementedError(f"{who}: processors= with past= is not implemented (a GenerationState keeps no history of the earlier turns)")
+        if processors.min_new_tokens > 0 and n_eos > ops.LOGITS_MAX_IDS:
+            raise ValueError(f"{who}: min_new_tokens with {n_eos} eos ids exceeds the {ops.LOGITS_MAX_IDS} a step bans")
+    if output_scores and (processors is None or not return_dict_in_generate):
+        raise ValueError(f"{who}: output_scores=True needs processors= (the scores are the processed logits) and return_dict_in_generate=True (they are GenerateOutput.scores)")
+    for name, v in (("prefill_chunk", prefill_chunk), ("cache_capacity", cache_capacity)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+            raise ValueError(f"{who}: {name}={v!r} must be an integer >= 1 (or None)")
+    if return_past and not return_dict_in_generate:
+        raise ValueError(f"{who}: return_past=True needs return_dict_in_generate=True (the state is GenerateOutput.past)")
+    if past is not None:
+        if not isinstance(past, GenerationState):
+            raise TypeError(f"{who}: past must be a generation.GenerationState (GenerateOutput.past), got {type(past).__name__}")
+        if position_ids is not None:
+            raise ValueError(f"{who}: with past= the new turn's positions continue from the cache; position_ids must be None")
+        if not past.cache.extendable:
+            raise NotImplementedError(f"{who}: continuing from an fp8 KV cache is not implemented (the extend attention "
+                                      "over e4m3fn rows is a follow-up kernel); generate the first turn with kv_cache='native'")
+        if past.cache.dtype != lm.model.norm.weight.dtype or past.cache.num_layers != len(lm.model.layers):
+            raise ValueError(f"{who}: past holds a {past.cache.dtype} cache of {past.cache.num_layers} layers, the model "
+                             f"runs {len(lm.model.layers)} layers in {lm.model.norm.weight.dtype}")
+    return Request(comp_images, max_new_tokens, eos_ids, pad_token_id, kv_cache, sampler, prefill_chunk, cache_capacity, past, draft, K, beams, C,
+                   processors, bool(return_dict_in_generate), bool(output_hidden_states), bool(output_logits), bool(output_scores), bool(return_past))
+
+
+def feed_prompt(lm, req: Request, w_e, embeds, am, pos, sliding_window, dev):
+    """The spliced prompt `embeds` (B, T, D), mask and positions (`lm._embed`'s result) - with `req.past` the new turn behind the pending tokens' column -
+    into a filled cache.  Returns (h (B, D): every sequence's last attended state, the cache, the eos ids on the device or None, the pad id or None)."""
+    who = "SetokimLlamaPrefill.generate"
+    B, T, D = embeds.shape
+    past, len0 = req.past, 0
+    if past is not None:
+        if past.cache.B != B or past.pending.shape != (B,):
+            raise ValueError(f"{who}: past holds {past.cache.B} sequences, the new turn {B}")
+        len0 = past.cache.len
+        pend = past.pending.to(dev)
+        front = ops.splice_rows(pend.clamp_min(0).to(torch.int32).reshape(B, 1), w_e, None)       # the pending tokens' embedding rows, one column
+        embeds = torch.cat([front, embeds.to(device=dev, dtype=front.dtype)], dim=1)
+        turn = torch.ones((B, T), dtype=torch.int64, device=dev) if am is None else am.to(dev).long()
+        am = torch.cat([(pend >= 0).long()[:, None], turn], dim=1)
+        T += 1
+    if sliding_window is not None and int(sliding_window) < len0 + T + req.max_new:
+        raise NotImplementedError(f"{who}: sliding_window={sliding_window} is shorter than prompt + max_new_tokens "
+                                  f"({len0 + T} + {req.max_new} positions): windowed attention is not implemented on the HIP path")
+    windows = req.prefill_chunk is not None and req.prefill_chunk < T             # the prompt is really cut (N >= T is the unchunked path)
+    if windows and pos is not None:
+        raise ValueError(f"{who}: prefill_chunk windows take their positions from the cache; position_ids must be None")
+    if windows and req.kv_cache not in KVCache.EXTENDABLE:
+        raise NotImplementedError(f"{who}: prefill_chunk with kv_cache='fp8' is not implemented (the extend attention over e4m3fn rows is a follow-up kernel)")
+    if am is not None:
+        am = am.to(dev)
+        if pos is None and past is None:                                       # HF generate's rule for a padded prompt without position_ids
+            pos = (am.long().cumsum(-1) - 1).masked_fill(am == 0, 1)
+    eos = pad = None
+    if req.eos_ids is not None:
+        eos = torch.as_tensor(req.eos_ids, dtype=torch.int64, device=dev)
+        pad = int(eos[0]) if req.pad_token_id is None else int(req.pad_token_id)
+    need = len0 + T + req.max_new + req.K                                      # (K = 0 without a draft: a round may fill K slots it gives back)
+    if past is None:
+        cache = KVCache.for_model(lm.model, B, max(need, req.cache_capacity or 0), dev, kv_format=req.kv_cache)
+    else:
+        cache = past.cache if past.cache.cap >= need else past.cache.grown(max(need, req.cache_capacity or 0))
+    # windows of the prompt (the whole prompt or new turn is the one-window case): the first window of a fresh prompt is a prefill, everything else
+    # extends the cache; each sequence's last attended row is looked up in the window that holds it
+    N = req.prefill_chunk if windows else max(T, 1)
+    embeds = embeds.to(dev)
+    h = None
+    for c0 in range(0, T, N):
+        c1 = min(c0 + N, T)
+        amw = None if am is None else am[:, c0:c1]
+        if past is None and c0 == 0:
+            hidden = lm.model.prefill(embeds[:, c0:c1], amw, None if pos is None else pos[:, c0:c1], cache)
+        else:
+            hidden = lm.model.extend(embeds[:, c0:c1], cache, amw)
+        if amw is None:
+            h = hidden[:, -1].contiguous()
+            continue
+        last = (amw.bool() * torch.arange(c1 - c0, device=dev)[None]).max(dim=1).values
+        hw = hidden[torch.arange(B, device=dev), last]
+        h = hw.contiguous() if h is None else torch.where(amw.bool().any(dim=1)[:, None], hw, h)
+    return h, cache, eos, pad
+
+
+def _raise_undrawable(raws) -> None:
+    """generate(sampler=...): `raws` holds every step's tokens as drawn, (B,) each, -1 where a row's logits could not be drawn from."""
+    if not raws:
+        return
+    bad = (torch.stack(raws, dim=1) < 0).nonzero().cpu().tolist()                  # (sequence, step) pairs, sequence-major
+    if bad:
+        b, s = min(bad, key=lambda bs: (bs[1], bs[0]))                             # the first step, its first sequence
+        raise RuntimeError(f"SetokimLlamaPrefill.generate: the logits of sequence {b} at step {s} contain a NaN or +inf, or no finite entry: "
+                           f"no token can be drawn ((sequence, step) pairs affected: {bad[:8]}{' ...' if len(bad) > 8 else ''})")
+
+
+def _select(scores: torch.Tensor, sampler: Optional[Sampler], u: Optional[torch.Tensor]) -> torch.Tensor:
+    """scores (rows, V) -> the rows' tokens, int64: the argmax, or ONE `setok_sample_rows` launch on the uniforms u (rows,): -1 = the row cannot be drawn from."""
+    if sampler is None:
+        return ops.argmax_rows(scores)
+    return ops.sample_rows(scores, u, sampler.temperature, sampler.top_k, sampler.top_p)
+
+
+def _decode_ids(lm, w_e, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    # ids (rows,) int64 -> embed_tokens' rows -> one `decode_step`: the states (rows, D) the next tokens are selected from
+    e = ops.splice_rows(ids.to(torch.int32).reshape(-1, 1), w_e, None)
+    return lm.model.decode_step(e.reshape(ids.shape[0], -1), cache)
+
+
+def loop_plain(lm, req: Request, w_lm, w_e, h, cache, eos, pad, prompt_ids, prompt_mask):
+    """One token per step from the last attended state `h` (B, D) on: lm_head, the processors, `_select`, `_decode_ids`; with an eos one host read per step."""
+    B, dev, sampler = h.shape[0], h.device, req.sampler
+    proc = None if req.processors is None else req.processors.begin(B, dev, prompt_ids, prompt_mask, req.max_new, eos)
+    fed0 = cache.len                                                           # the first slot a decode step of this call fills
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    toks, hids, lgs, scs = [], [], [], []
+    raws = []                                                                  # sampler only: the tokens as drawn, -1 where a row could not be drawn from
+    for step in range(req.max_new):
+        logits = ops.linear(h, w_lm)                                           # (B, V): never copied to the host
+        scores = logits if proc is None else proc.process(logits)              # (B, V) fp32 with processors: what the token is selected from
+        tok = raw = _select(scores, sampler, None if sampler is None else sampler.uniforms(step, B, dev))
+        if sampler is not None:
+            raws.append(raw)
+            tok = raw.clamp_min(0)                                             # a valid row for the embedding lookup; the error is raised below
+        if eos is not None:
+            tok = torch.where(finished, torch.full_like(tok, pad), tok)
+            finished = finished | torch.isin(tok, eos)
+        toks.append(tok)
+        if proc is not None:
+            proc.append(tok.reshape(B, 1))
+        if req.want_hidden:
+            hids.append(h)
+        if req.want_logits:
+            lgs.append(logits)
+        if req.want_scores:
+            scs.append(scores)
+        if step + 1 == req.max_new:
+            break
+        if eos is not None:
+            stop = finished.all() if sampler is None else finished.all() | (raw < 0).any()
+            if bool(stop):                                                     # the one host read per step
+                _raise_undrawable(raws)                                        # raises iff a row could not be drawn; else every sequence has finished
+                break
+        h = _decode_ids(lm, w_e, tok, cache)
+    _raise_undrawable(raws)
+    seq = torch.stack(toks, dim=1)
+    if not req.as_dict:
+        return seq
+    return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if req.want_hidden else None,
+                          logits=torch.stack(lgs, dim=1) if req.want_logits else None,
+                          past=GenerationState.after_plain_loop(cache, seq, eos, fed0) if req.want_past else None,
+                          scores=torch.stack(scs, dim=1) if req.want_scores else None)
+
+
+def loop_beams(lm, req: Request, w_lm, w_e, h, cache, eos, pad):
+    """The loop with beam search, from the last attended state `h` (B, D) on.  The running scores, the finished set and the back-pointers live on
+    the device (ops.BeamState); the host reads `setok_beam_advance`'s 2-int summary once per step, and the hypotheses are materialised from the
+    back-pointers once at the end."""
+    beams, max_new = req.beams, req.max_new
+    B, n, R, dev = h.shape[0], beams.num_beams, beams.num_return_sequences, h.device
+    state = ops.BeamState(B, n, max_new, dev)
+    cache = cache.expanded(n)
+    fed0 = cache.len                                                           # the first slot a decode step of this call fills: what `reorder` moves starts here
+    running0 = torch.zeros((B, 1), dtype=torch.float32, device=dev)            # step 0: one row per sequence, score 0
+    ws = torch.empty(B * n * (2 * ops.BEAM_MAX_C + 1), dtype=torch.int32, device=dev)
+    hids, lgs = [], []
+    for step in range(max_new):
+        logits = ops.linear(h, w_lm)                                           # (B, V) at step 0, then (B * n, V)
+        cand = ops.beam_topk(logits, running0 if step == 0 else state.run_score, req.C, ws)
+        tok, src_row, summary = ops.beam_advance(*cand, state, eos, step, beams.length_penalty, beams.early_stopping)
+        if req.want_hidden:
+            hids.append(h.repeat_interleave(n, dim=0) if step == 0 else h)
+        if req.want_logits:
+            lgs.append(logits.repeat_interleave(n, dim=0) if step == 0 else logits)
+        go_on, bad = summary.tolist()                                          # the step's one host read
+        if bad:
+            rows = torch.nonzero(cand[3]).flatten().tolist()
+            raise RuntimeError(f"SetokimLlamaPrefill.generate: the logits of sequence(s) {rows} hold a NaN or +inf at beam-search step {step}")
+        if not go_on:
+            break
+        cache.reorder(src_row, fed0, n)
+        h = _decode_ids(lm, w_e, tok, cache)
+    # the returned hypotheses: the first R entries of every finished set, walked back through the parents
+    length = state.fin_len[:, :R].reshape(B * R).long().clamp_min(1)
+    beam = state.fin_parent[:, :R].reshape(B * R).long()
+    n_new = int(length.max())
+    base = (torch.arange(B, device=dev) * n).repeat_interleave(R)
+    rows = torch.arange(B * R, device=dev)
+    seq = torch.full((B * R, n_new), pad, dtype=torch.int64, device=dev)
+    anc = torch.full((B * R, n_new), -1, dtype=torch.int64, device=dev)
+    seq[rows, length - 1] = state.fin_token[:, :R].reshape(B * R)
+    anc[rows, length - 1] = base + beam
+    for j in range(n_new - 2, -1, -1):
+        live = j <= length - 2                                                 # token j of these hypotheses belongs to running beam `beam` after step j
+        at = base + beam
+        parent = state.bp_parent[j][at].long()
+        seq[:, j] = torch.where(live, state.bp_token[j][at], seq[:, j])
+        anc[:, j] = torch.where(live, base + parent, anc[:, j])
+        beam = torch.where(live, parent, beam)
+    if not req.as_dict:
+        return seq
+
+    def along(kept):                                                           # (steps, B * n, X) -> (B * R, n_new, X): row j from the state that produced token j
+        got = torch.stack(kept[:n_new], dim=0)[torch.arange(n_new, device=dev)[None], anc.clamp_min(0)]
+        return got * (anc >= 0)[..., None].to(got.dtype)
+
+    return GenerateOutput(sequences=seq, hidden_states=along(hids) if req.want_hidden else None, logits=along(lgs) if req.want_logits else None,
+                          sequences_scores=state.fin_score[:, :R].reshape(B * R).clone(), beam_indices=anc.to(torch.int32))
+
+
+def loop_speculative(lm, req: Request, w_lm, w_e, h, cache, eos, pad, prompt_ids, prompt_mask):
+    """The loop with a drafter, from the last attended state `h` (B, D) on.  Between rounds the state lives on the device: pending (B,) int64,
+    count (B,) int32, finished (B,) uint8 and seq (B, max_new) int64; `setok_spec_accept` advances it, and the host reads the kernel's 3-int
+    summary once per round.  With processors the K + 1 rows of a round are processed in one launch (row i sees the history plus drafts
+    0 .. i - 1) before the selection, and the emitted tokens join the history behind the accept rule."""
+    draft, K, sampler, max_new = req.draft, req.K, req.sampler, req.max_new
+    (B, D), dev = h.shape, h.device
+    seq = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
+    count = torch.zeros(B, dtype=torch.int32, device=dev)
+    finished = torch.zeros(B, dtype=torch.uint8, device=dev)
+    pending = torch.zeros(B, dtype=torch.int64, device=dev)
+    summary = torch.zeros(3, dtype=torch.int32, device=dev)
+    u = None if sampler is None else sampler.uniform_matrix(max_new, B, dev)
+    steps = torch.arange(K + 1, device=dev, dtype=torch.int64)[None]
+    rows_b = torch.arange(B, device=dev)[:, None]
+    outs = {}                                                                  # "hidden" / "logits" / "scores": (B, max_new + 1, X); column max_new takes the rows no sequence emitted
+    proc = None if req.processors is None else req.processors.begin(B, dev, prompt_ids, prompt_mask, max_new, eos)
+
+    def verify(hidden, d, tail, slot):
+        # hidden (B * n, D), the states behind the pending token and the n - 1 drafts d: select, accept, keep rows -> (longest acceptance, live sequences)
+        n = d.shape[1] + 1
+        logits = ops.linear(hidden, w_lm)
+        scores = logits if proc is None else proc.process(logits, tail)
+        ur = None if sampler is None else u[(count.long()[:, None] + steps[:, :n]).clamp_max(max_new - 1), rows_b].reshape(B * n).contiguous()
+        sel = _select(scores, sampler, ur).reshape(B, n)
+        before = count.clone()
+        emitted, m, _ = ops.spec_accept(d, sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, slot, summary=summary)
+        cols = torch.where(steps[:, :n] < m.long()[:, None], before.long()[:, None] + steps[:, :n], torch.full_like(steps[:, :n], max_new))
+        for name, want, rows in (("hidden", req.want_hidden, hidden), ("logits", req.want_logits, logits), ("scores", req.want_scores, scores)):
+            if want:                                                           # row i < m[b] of sequence b -> column before[b] + i
+                if name not in outs:
+                    outs[name] = torch.zeros((B, max_new + 1, rows.shape[-1]), dtype=rows.dtype, device=dev)
+                outs[name][rows_b, cols] = rows.reshape(B, n, -1)
+        if proc is not None:
+            proc.append(emitted, m)
+        draft.update(emitted, m)
+        mx, live, bad = summary.tolist()                                       # the round's one host read
+        if bad:
+            c = int(count.max())
+            drawn = torch.where((seq[:, :c] < 0) & (torch.arange(c, device=dev)[None] < count[:, None]), -1, 0)
+            _raise_undrawable(list(drawn.unbind(dim=1)))
+        return mx, live
+
+    cache.next_pos = cache.next_pos.contiguous()
+    draft.begin(B, dev, prompt_ids, prompt_mask, max_new)
+    # step 0: the token selected from the last attended state, put into the loop state by the accept rule with no drafts
+    _, live = verify(h, torch.empty((B, 0), dtype=torch.int64, device=dev), None, cache.len)
+    cache.key_mask[:, cache.len] = 0                                           # (nothing was fed: the slot the rule marked is not filled yet)
+    while live > 0:
+        if cache.len + K + 1 > cache.cap:
+            cache = cache.grown(2 * cache.cap)
+        d = draft.propose(pending)
+        if not (isinstance(d, torch.Tensor) and d.dtype == torch.int64 and tuple(d.shape) == (B, K)):
+            raise TypeError(f"SetokimLlamaPrefill.generate: draft.propose must return a (B, K) = ({B}, {K}) int64 tensor")
+        d = d.to(dev).contiguous()
+        live_b = finished == 0
+        am = torch.cat([live_b[:, None], ((d >= 0).long().cummin(dim=1).values > 0) & live_b[:, None]], dim=1)
+        ids = torch.cat([pending[:, None], d], dim=1).clamp_min(0).to(torch.int32)
+        len0 = cache.len
+        hidden = lm.model.extend(ops.splice_rows(ids, w_e, None), cache, am)   # (B, K + 1, D): one pass over the weights
+        mx, live = verify(hidden.reshape(B * (K + 1), D), d, d, len0)
+        cache.truncate(len0 + mx)
+    n = int(count.max())
+    out = seq[:, :n].contiguous()
+    if not req.as_dict:
+        return out
+    kept = lambda name, want: outs[name][:, :n].contiguous() if want else None
+    return GenerateOutput(sequences=out, hidden_states=kept("hidden", req.want_hidden), logits=kept("logits", req.want_logits),
+                          past=GenerationState(cache=cache, pending=pending) if req.want_past else None, scores=kept("scores", req.want_scores))

@@ -18,7 +18,8 @@ reads key / value head h // (H // Hkv), HF's `repeat_kv` without the copies.
 
 Generation (`SetokimLlamaForCausalLM.generate`, setokim_llama.py:329-396) is greedy decoding with a KV cache: `LlamaModel.prefill` is the same
 prefill that also fills a `generation.KVCache`, `LlamaModel.decode_step` runs one token per sequence against it (csrc/attn_decode.hip), and
-`SetokimLlamaPrefill.generate` is the loop.  `LlamaModel.extend` adds Tn >= 1 tokens per sequence to a cache that already holds
+`SetokimLlamaPrefill.generate` calls the parts of the loop, which live in generation.py.  The three entry points run the stack through
+one layer loop, `LlamaModel._run_layers`, and differ in its attention step.  `LlamaModel.extend` adds Tn >= 1 tokens per sequence to a cache that already holds
 some (csrc/attn_extend.hip): `generate(prefill_chunk=)` feeds a prompt in windows through it and `generate(past=)` continues a conversation from the
 state an earlier call returned.
 
@@ -233,19 +234,13 @@ class LlamaModel(PackCacheMixin, nn.Module):
         return super().state_dict(*args, **kwargs)
 
     def _w(self, w):
-        """A packed operand as `linear` takes it: itself, or — quantised storage, a (q, e) or (q, s) pair — dequantised into the one scratch
-        buffer (stream order makes the reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
-        if not isinstance(w, tuple):
-            return w
-        fmt = self._quant["fmt"]
-        N, K = fmt.shape(w)
-        return fmt.dequantize(*w, out=self._dequant_scratch()[:N * K].view(N, K))
-
-    def _dequant_scratch(self):
+        """A quantised operand - a (q, e) or (q, s) pair - as `linear` takes it: dequantised into the one scratch buffer (stream order makes the
+        reuse safe: the GEMM that reads it is enqueued before the next dequantisation)."""
         f = self._quant
         if f["scratch"] is None:
             f["scratch"] = torch.empty(f["largest"], dtype=f["key"][0], device=self.norm.weight.device)
-        return f["scratch"]
+        N, K = f["fmt"].shape(w)
+        return f["fmt"].dequantize(*w, out=f["scratch"][:N * K].view(N, K))
 
     def _pack(self):
         w = self.norm.weight
@@ -305,6 +300,34 @@ class LlamaModel(PackCacheMixin, nn.Module):
         """Does any parameter of the decoder stack (layers.*, norm — not embed_tokens, whose gradient comes from the splice) require a gradient?"""
         return any(p.requires_grad for p in self.layers.parameters()) or self.norm.weight.requires_grad
 
+    def _projections(self, M: int, stream: bool = True):
+        """(linear(a, w, residual=, out=), gate_up(a, w): the gate|up Linear with SwiGLU) for a pass of M rows over packed operands `w`.  The one choice
+        between the native operand, the weight-streaming GEMM on the stored pair (up to `max_m` rows where the entry point streams: decode_step,
+        extend) and dequantise-into-scratch + `linear` (more rows, and every prefill)."""
+        fmt = None if self._quant is None else self._quant["fmt"]
+        if fmt is None:
+            return ops.linear, ops.linear_swiglu
+        if stream and M <= fmt.max_m:
+            return (lambda a, w, **kw: fmt.linear(a, *w, **kw)), (lambda a, w: ops.swiglu_pairs(fmt.linear(a, *w)))
+        return (lambda a, w, **kw: ops.linear(a, self._w(w), **kw)), (lambda a, w: ops.linear_swiglu(a, self._w(w)))
+
+    def _run_layers(self, x, layers, pos, attend, stream: bool = True):
+        """The decoder stack over x (M, D), in place; `attend(li, qkv) -> o` is the entry point's attention step with its own `cache.append`, the
+        only thing that differs between prefill, decode_step and extend.  Returns the norm's scratch rows for the caller's final norm."""
+        H, Hkv, dh, eps, theta = self.num_heads, self.num_kv_heads, self.head_dim, self.eps, self.rope_theta
+        linear, gate_up = self._projections(x.shape[0], stream)
+        rmsnorm, rope_ = ops.rmsnorm, ops.rope_                               # (looked up once: a decode step is launch-bound, and the host pays per layer)
+        y = None
+        for li, L in enumerate(layers):
+            y = rmsnorm(x, L["n1"], eps, out=y)
+            qkv = linear(y, L["wqkv"])
+            rope_(qkv, pos, H, dh, theta, Hkv)
+            o = attend(li, qkv)
+            linear(o, L["wo"], residual=x, out=x)
+            y = rmsnorm(x, L["n2"], eps, out=y)
+            linear(gate_up(y, L["wgu"]), L["wd"], residual=x, out=x)          # (gate_up: SwiGLU in the GEMM's epilogue in the 16-bit modes; the unfused pair otherwise: same bits)
+        return y
+
     def _forward(self, inputs_embeds, attention_mask=None, position_ids=None, cache=None):
         """The prefill.  With `cache` (a generation.KVCache, empty) every layer's post-rotary keys / values are also copied to its slots [0, T):
         one more launch per layer, nothing else changes."""
@@ -322,18 +345,12 @@ class LlamaModel(PackCacheMixin, nn.Module):
             position_ids = torch.arange(T, device=dev)[None].expand(B, T)
         pos = position_ids.to(device=dev, dtype=torch.int64).reshape(B * T).contiguous()
         km = None if attention_mask is None else attention_mask.to(device=dev).bool().to(torch.uint8).reshape(B * T).contiguous()
-        y = None
-        for li, L in enumerate(pk["layers"]):
-            y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = ops.linear(y, self._w(L["wqkv"]))                      # (_w: the operand itself; fp8 storage dequantises it into the scratch buffer first)
-            ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
+
+        def attend(li, qkv):
             if cache is not None:
                 cache.append(li, qkv, T, H, 0)                                  # (the cache's own format; the prefill attends over qkv itself)
-            o = ops.attention_causal(qkv, km, B, T, H, dh, dh ** -0.5, Hkv)
-            ops.linear(o, self._w(L["wo"]), residual=x, out=x)
-            y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-            g = ops.linear_swiglu(y, self._w(L["wgu"]))                  # gate|up Linear with SwiGLU in its epilogue (16-bit modes; the unfused pair otherwise: same bits)
-            ops.linear(g, self._w(L["wd"]), residual=x, out=x)
+            return ops.attention_causal(qkv, km, B, T, H, dh, dh ** -0.5, Hkv)
+        y = self._run_layers(x, pk["layers"], pos, attend, stream=False)        # (quantised storage: dequantised at every M, `linear`'s summation order)
         if cache is not None:
             # every sequence's next rotary position: the position of its last attended token + 1 (HF extends `cumsum(attention_mask) - 1` the same way)
             p2 = pos.reshape(B, T)
@@ -374,32 +391,18 @@ class LlamaModel(PackCacheMixin, nn.Module):
             raise ValueError(f"LlamaModel.decode_step: cache of B={cache.B} with {slot} of {cache.cap} slots filled cannot take a step of B={B} "
                              "(prefill first; cap = prompt length + max_new_tokens)")
         pk = self._pack()
-        H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
+        H, dh = self.num_heads, self.head_dim
         x = inputs_embeds.to(self.norm.weight.dtype).contiguous().clone()
         pos = cache.next_pos
         cache.key_mask[:, slot] = 1
-        ws = cache.workspace(H)
-        y = o = None
-        fmt = None if self._quant is None else self._quant["fmt"]                   # quantised storage: (q, e) pairs, or mxfp4's (q, s) pairs
-        fp8 = fmt is not None
-        lin8 = fmt.linear if fp8 else None
-        big = self._dequant_scratch() if fp8 and B > fmt.max_m else None            # more rows than the streaming kernel takes: dequantise, then `linear`
-        for li, L in enumerate(pk["layers"]):
-            y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = lin8(y, *L["wqkv"], scratch=big) if fp8 else ops.linear(y, L["wqkv"])
-            ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
+        ws, scale, o = cache.workspace(H), dh ** -0.5, None
+
+        def attend(li, qkv):
+            nonlocal o
             cache.append(li, qkv, 1, H, slot)                                       # (native, fp8 or mxfp4: the cache's format decides these two calls)
-            o = cache.attend(li, qkv, H, slot + 1, dh ** -0.5, ws, o)
-            if fp8:                                                                 # the same step on the fp8 bytes (mxfp4 nibbles): four weight-streaming GEMMs
-                lin8(o, *L["wo"], residual=x, out=x, scratch=big)
-                y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-                g = ops.swiglu_pairs(lin8(y, *L["wgu"], scratch=big))
-                lin8(g, *L["wd"], residual=x, out=x, scratch=big)
-                continue
-            ops.linear(o, L["wo"], residual=x, out=x)
-            y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-            g = ops.linear_swiglu(y, L["wgu"])
-            ops.linear(g, L["wd"], residual=x, out=x)
+            o = cache.attend(li, qkv, H, slot + 1, scale, ws, o)
+            return o
+        y = self._run_layers(x, pk["layers"], pos, attend)
         cache.len = slot + 1
         cache.next_pos = pos + 1
         return ops.rmsnorm(x, pk["norm"], self.eps, out=y)
@@ -418,7 +421,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         self._refuse_unmerged("LlamaModel.extend")
         B, Tn, D = inputs_embeds.shape
         len0 = cache.len
-        if cache.kv_format == "fp8":
+        if not cache.extendable:
             raise NotImplementedError("LlamaModel.extend: extending an fp8 KV cache by several tokens is not implemented (the extend attention over "
                                       "e4m3fn rows is a follow-up kernel); use kv_cache='native'")
         if (B != cache.B or (Tn == 0 and len0 == 0) or len0 + Tn > cache.cap or cache.num_layers != len(self.layers)
@@ -431,7 +434,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
         if Tn == 0:
             return inputs_embeds.to(self.norm.weight.dtype).reshape(B, 0, D)
         pk = self._pack()
-        H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
+        H, dh = self.num_heads, self.head_dim
         M = B * Tn
         x = inputs_embeds.to(self.norm.weight.dtype).reshape(M, D).contiguous().clone()
         if attention_mask is None:
@@ -440,44 +443,17 @@ class LlamaModel(PackCacheMixin, nn.Module):
             am = attention_mask.to(device=dev).bool().long()
         pos = (cache.next_pos[:, None] + am.cumsum(1) - am).reshape(M).contiguous()     # attended rows before i; a masked row gets the next row's (valid) position
         cache.key_mask[:, len0:len0 + Tn] = am.to(torch.uint8)
-        ws = cache.workspace(H, Tn, len0)
-        y = o = None
-        fmt = None if self._quant is None else self._quant["fmt"]
-        lin8 = fmt.linear if fmt is not None else None
-        stream8 = fmt is not None and M <= fmt.max_m                            # few rows: the weight-streaming GEMM on the fp8 bytes (mxfp4 nibbles), as in decode_step
-        for li, L in enumerate(pk["layers"]):
-            y = ops.rmsnorm(x, L["n1"], self.eps, out=y)
-            qkv = lin8(y, *L["wqkv"]) if stream8 else ops.linear(y, self._w(L["wqkv"]))
-            ops.rope_(qkv, pos, H, dh, self.rope_theta, Hkv)
+        ws, scale, o = cache.workspace(H, Tn, len0), dh ** -0.5, None
+
+        def attend(li, qkv):
+            nonlocal o
             cache.append(li, qkv, Tn, H, len0)
-            o = cache.extend_attend(li, qkv, H, Tn, len0, dh ** -0.5, ws, o)
-            if stream8:
-                lin8(o, *L["wo"], residual=x, out=x)
-                y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-                g = ops.swiglu_pairs(lin8(y, *L["wgu"]))
-                lin8(g, *L["wd"], residual=x, out=x)
-                continue
-            ops.linear(o, self._w(L["wo"]), residual=x, out=x)
-            y = ops.rmsnorm(x, L["n2"], self.eps, out=y)
-            g = ops.linear_swiglu(y, self._w(L["wgu"]))
-            ops.linear(g, self._w(L["wd"]), residual=x, out=x)
+            o = cache.extend_attend(li, qkv, H, Tn, len0, scale, ws, o)
+            return o
+        y = self._run_layers(x, pk["layers"], pos, attend)
         cache.len = len0 + Tn
         cache.next_pos = cache.next_pos + am.sum(1)
         return ops.rmsnorm(x, pk["norm"], self.eps, out=y).reshape(B, Tn, D)
-
-
-_SAMPLING_ARGS = ("temperature", "top_p", "top_k", "num_beams", "penalty_alpha", "repetition_penalty")      # generate(): named so that they are refused by name
-
-
-def _raise_undrawable(raws) -> None:
-    """generate(sampler=...): `raws` holds every step's tokens as drawn, (B,) each, -1 where a row's logits could not be drawn from."""
-    if not raws:
-        return
-    bad = (torch.stack(raws, dim=1) < 0).nonzero().cpu().tolist()                  # (sequence, step) pairs, sequence-major
-    if bad:
-        b, s = min(bad, key=lambda bs: (bs[1], bs[0]))                             # the first step, its first sequence
-        raise RuntimeError(f"SetokimLlamaPrefill.generate: the logits of sequence {b} at step {s} contain a NaN or +inf, or no finite entry: "
-                           f"no token can be drawn ((sequence, step) pairs affected: {bad[:8]}{' ...' if len(bad) > 8 else ''})")
 
 
 def _refuse_unsupported_llama_fields(g) -> None:
@@ -736,367 +712,19 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         defaults, temperature=0.1 and top_p=10.0, are not valid HF arguments, and torch's Philox multinomial cannot be reproduced here: pass a
         `sampler=`, whose uniforms are an input).  A
         `sliding_window` shorter than prompt + max_new_tokens is refused like every field `_refuse_unsupported_llama_fields` names."""
-        from .generation import BeamSearch, Drafter, GenerateOutput, GenerationState, KVCache, LogitsProcessors, Sampler
-        self.model._refuse_unmerged("SetokimLlamaPrefill.generate")
-        sampling = [k for k in _SAMPLING_ARGS if unsupported.get(k) is not None]
-        if do_sample or sampling:
-            raise NotImplementedError(f"SetokimLlamaPrefill.generate: greedy decoding (do_sample=False, no {', '.join(sampling) or 'sampling arguments'}) "
-                                      "is the implemented mode; sampling and beam search are not implemented on the HIP path")
-        unknown = [k for k in unsupported if k not in _SAMPLING_ARGS]
-        if unknown:
-            raise TypeError(f"SetokimLlamaPrefill.generate: unexpected arguments {unknown}")
-        if images is not None:
-            if comp_images is not None:
-                raise ValueError("SetokimLlamaPrefill.generate: pass the images as `comp_images` or as `images`, not both")
-            comp_images = images
-        if max_new_tokens < 1:
-            raise ValueError("SetokimLlamaPrefill.generate: max_new_tokens must be at least 1")
-        if kv_cache not in KVCache.FORMATS:
-            raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache={kv_cache!r} is not one of 'native', 'fp8', 'mxfp4'")
-        if kv_cache == "mxfp4" and self.model.head_dim % 32 != 0:
-            raise ValueError(f"SetokimLlamaPrefill.generate: kv_cache='mxfp4' needs a head dim that is a multiple of 32 (the MX block), the "
-                             f"model's is {self.model.head_dim}; use kv_cache='native' or 'fp8'")
-        if sampler is not None and not isinstance(sampler, Sampler):
-            raise TypeError(f"SetokimLlamaPrefill.generate: sampler must be a generation.Sampler or None, got {type(sampler).__name__}")
-        K = 0
-        if draft is not None:
-            if not isinstance(draft, Drafter):
-                raise TypeError(f"SetokimLlamaPrefill.generate: draft must be a generation.Drafter or None, got {type(draft).__name__}")
-            K = draft.K
-            if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPEC_MAX_K:
-                raise ValueError(f"SetokimLlamaPrefill.generate: draft.K={K!r} must be an int in [1, {ops.SPEC_MAX_K}]")
-            if kv_cache == "fp8":
-                raise NotImplementedError("SetokimLlamaPrefill.generate: draft= with kv_cache='fp8' is not implemented (a round extends the cache by "
-                                          "K + 1 tokens, and the extend attention over e4m3fn rows is a follow-up kernel); use kv_cache='native'")
-        C = 0
+        from . import generation as G
+        req = G.check_request(self, comp_images=comp_images, images=images, position_ids=position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                              pad_token_id=pad_token_id, do_sample=do_sample, return_dict_in_generate=return_dict_in_generate, output_hidden_states=output_hidden_states,
+                              output_logits=output_logits, kv_cache=kv_cache, sampler=sampler, prefill_chunk=prefill_chunk, return_past=return_past, past=past,
+                              cache_capacity=cache_capacity, draft=draft, beams=beams, processors=processors, output_scores=output_scores, unsupported=unsupported)
+        embeds, am, pos, _ = self._embed(inputs, attention_mask, position_ids, inputs_embeds, None, req.comp_images)
+        w_lm, w_e = self.lm_head.weight.detach().contiguous(), self.model.embed_tokens.weight.detach().contiguous()      # the call's one fetch
+        h, cache, eos, pad = G.feed_prompt(self, req, w_e, embeds, am, pos, config_get(self.config, "sliding_window"), w_lm.device)
         if beams is not None:
-            if not isinstance(beams, BeamSearch):
-                raise TypeError(f"SetokimLlamaPrefill.generate: beams must be a generation.BeamSearch or None, got {type(beams).__name__}")
-            for name, given in (("sampler=", sampler is not None), ("draft=", draft is not None), ("past=", past is not None),
-                                ("return_past=True", bool(return_past))):
-                if given:
-                    raise NotImplementedError(f"SetokimLlamaPrefill.generate: beams= with {name} is not implemented (beam sampling, drafting "
-                                              "into beams and continuing a beam state are not built)")
-            n_eos = 0 if eos_token_id is None else 1 if isinstance(eos_token_id, int) else len(list(eos_token_id))
-            C = beams.candidates(n_eos, self.lm_head.weight.shape[0])
-        if processors is not None:
-            if not isinstance(processors, LogitsProcessors):
-                raise TypeError(f"SetokimLlamaPrefill.generate: processors must be a generation.LogitsProcessors or None, got {type(processors).__name__}")
-            if beams is not None:
-                raise NotImplementedError("SetokimLlamaPrefill.generate: processors= with beams= is not implemented (HF applies its processors to "
-                                          "the beams' log-probabilities, which is a different rule)")
-            if past is not None:
-                raise NotImplementedError("SetokimLlamaPrefill.generate: processors= with past= is not implemented (a GenerationState keeps no "
-                                          "history of the earlier turns)")
-            n_eos = 0 if eos_token_id is None else 1 if isinstance(eos_token_id, int) else len(list(eos_token_id))
-            if processors.min_new_tokens > 0 and n_eos > ops.LOGITS_MAX_IDS:
-                raise ValueError(f"SetokimLlamaPrefill.generate: min_new_tokens with {n_eos} eos ids exceeds the {ops.LOGITS_MAX_IDS} a step bans")
-        if output_scores and (processors is None or not return_dict_in_generate):
-            raise ValueError("SetokimLlamaPrefill.generate: output_scores=True needs processors= (the scores are the processed logits) and "
-                             "return_dict_in_generate=True (they are GenerateOutput.scores)")
-        for name, v in (("prefill_chunk", prefill_chunk), ("cache_capacity", cache_capacity)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
-                raise ValueError(f"SetokimLlamaPrefill.generate: {name}={v!r} must be an integer >= 1 (or None)")
-        if return_past and not return_dict_in_generate:
-            raise ValueError("SetokimLlamaPrefill.generate: return_past=True needs return_dict_in_generate=True (the state is GenerateOutput.past)")
-        if past is not None:
-            if not isinstance(past, GenerationState):
-                raise TypeError(f"SetokimLlamaPrefill.generate: past must be a generation.GenerationState (GenerateOutput.past), got {type(past).__name__}")
-            if position_ids is not None:
-                raise ValueError("SetokimLlamaPrefill.generate: with past= the new turn's positions continue from the cache; position_ids must be None")
-            if past.cache.kv_format == "fp8":
-                raise NotImplementedError("SetokimLlamaPrefill.generate: continuing from an fp8 KV cache is not implemented (the extend attention "
-                                          "over e4m3fn rows is a follow-up kernel); generate the first turn with kv_cache='native'")
-            if past.cache.dtype != self.model.norm.weight.dtype or past.cache.num_layers != len(self.model.layers):
-                raise ValueError(f"SetokimLlamaPrefill.generate: past holds a {past.cache.dtype} cache of {past.cache.num_layers} layers, the model "
-                                 f"runs {len(self.model.layers)} layers in {self.model.norm.weight.dtype}")
-        embeds, am, pos, _ = self._embed(inputs, attention_mask, position_ids, inputs_embeds, None, comp_images)
-        B, T, D = embeds.shape
-        dev = self.lm_head.weight.device
-        w_lm = self.lm_head.weight.detach().contiguous()
-        w_e = self.model.embed_tokens.weight.detach().contiguous()
-        len0 = 0
-        if past is not None:
-            if past.cache.B != B or past.pending.shape != (B,):
-                raise ValueError(f"SetokimLlamaPrefill.generate: past holds {past.cache.B} sequences, the new turn {B}")
-            len0 = past.cache.len
-            pend = past.pending.to(dev)
-            front = ops.splice_rows(pend.clamp_min(0).to(torch.int32).reshape(B, 1), w_e, None)       # the pending tokens' embedding rows, one column
-            embeds = torch.cat([front, embeds.to(device=dev, dtype=front.dtype)], dim=1)
-            turn = torch.ones((B, T), dtype=torch.int64, device=dev) if am is None else am.to(dev).long()
-            am = torch.cat([(pend >= 0).long()[:, None], turn], dim=1)
-            T += 1
-        sw = config_get(self.config, "sliding_window")
-        if sw is not None and int(sw) < len0 + T + max_new_tokens:
-            raise NotImplementedError(f"SetokimLlamaPrefill.generate: sliding_window={sw} is shorter than prompt + max_new_tokens "
-                                      f"({len0 + T} + {max_new_tokens} positions): windowed attention is not implemented on the HIP path")
-        windows = prefill_chunk is not None and prefill_chunk < T             # the prompt is really cut (N >= T is the unchunked path)
-        if windows and pos is not None:
-            raise ValueError("SetokimLlamaPrefill.generate: prefill_chunk windows take their positions from the cache; position_ids must be None")
-        if windows and kv_cache == "fp8":
-            raise NotImplementedError("SetokimLlamaPrefill.generate: prefill_chunk with kv_cache='fp8' is not implemented (the extend attention over "
-                                      "e4m3fn rows is a follow-up kernel)")
-        if am is not None:
-            am = am.to(dev)
-            if pos is None and past is None:                                       # HF generate's rule for a padded prompt without position_ids
-                pos = (am.long().cumsum(-1) - 1).masked_fill(am == 0, 1)
-        eos = None
-        if eos_token_id is not None:
-            eos = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), dtype=torch.int64, device=dev)
-            pad = int(eos[0]) if pad_token_id is None else int(pad_token_id)
-        need = len0 + T + max_new_tokens + K                                       # (K = 0 without a draft: a round may fill K slots it gives back)
-        if past is None:
-            cache = KVCache.for_model(self.model, B, max(need, cache_capacity or 0), dev, kv_format=kv_cache)
-        else:
-            cache = past.cache if past.cache.cap >= need else past.cache.grown(max(need, cache_capacity or 0))
-        if past is None and not windows:
-            hidden = self.model.prefill(embeds.to(dev), am, pos, cache)
-            if am is None:
-                h = hidden[:, -1].contiguous()
-            else:
-                last = (am.bool() * torch.arange(T, device=dev)[None]).max(dim=1).values
-                h = hidden[torch.arange(B, device=dev), last].contiguous()
-        else:
-            # windows of the prompt (or the whole new turn): the first window of a fresh prompt is a prefill, everything else extends the cache;
-            # each sequence's last attended row is looked up in the window that holds it
-            N = prefill_chunk if windows else T
-            embeds = embeds.to(dev)
-            h = None
-            for c0 in range(0, T, N):
-                c1 = min(c0 + N, T)
-                amw = None if am is None else am[:, c0:c1]
-                if past is None and c0 == 0:
-                    hidden = self.model.prefill(embeds[:, c0:c1], amw, None if pos is None else pos[:, c0:c1], cache)
-                else:
-                    hidden = self.model.extend(embeds[:, c0:c1], cache, amw)
-                if amw is None:
-                    h = hidden[:, -1].contiguous()
-                    continue
-                last = (amw.bool() * torch.arange(c1 - c0, device=dev)[None]).max(dim=1).values
-                hw = hidden[torch.arange(B, device=dev), last]
-                h = hw.contiguous() if h is None else torch.where(amw.bool().any(dim=1)[:, None], hw, h)
-        if beams is not None:
-            return self._generate_beams(beams, C, h, cache, max_new_tokens, eos, (pad if eos is not None else int(pad_token_id or 0)),
-                                        return_dict_in_generate, output_hidden_states, output_logits)
+            return G.loop_beams(self, req, w_lm, w_e, h, cache, eos, pad if eos is not None else int(pad_token_id or 0))
         if draft is not None:
-            return self._generate_speculative(draft, h, cache, inputs, attention_mask, max_new_tokens, eos, pad if eos is not None else 0, sampler,
-                                              return_dict_in_generate, output_hidden_states, output_logits, return_past, processors, output_scores)
-        proc = None if processors is None else processors.begin(B, dev, inputs, attention_mask, max_new_tokens, eos)
-        fed0 = cache.len                                                           # the first slot a decode step of this call fills
-        finished = torch.zeros(B, dtype=torch.bool, device=dev)
-        toks, hids, lgs, scs = [], [], [], []
-        raws = []                                                                  # sampler only: the tokens as drawn, -1 where a row could not be drawn from
-        for step in range(max_new_tokens):
-            logits = ops.linear(h, w_lm)                                           # (B, V): never copied to the host
-            scores = logits if proc is None else proc.process(logits)              # (B, V) fp32 with processors: what the token is selected from
-            if sampler is None:
-                tok = ops.argmax_rows(scores)
-            else:
-                raw = sampler.select(scores, step)
-                raws.append(raw)
-                tok = raw.clamp_min(0)                                             # a valid row for the embedding lookup; the error is raised below
-            if eos is not None:
-                tok = torch.where(finished, torch.full_like(tok, pad), tok)
-                finished = finished | torch.isin(tok, eos)
-            toks.append(tok)
-            if proc is not None:
-                proc.append(tok.reshape(B, 1))
-            if output_hidden_states:
-                hids.append(h)
-            if output_logits:
-                lgs.append(logits)
-            if output_scores:
-                scs.append(scores)
-            if step + 1 == max_new_tokens:
-                break
-            if eos is not None:
-                stop = finished.all() if sampler is None else finished.all() | (raw < 0).any()
-                if bool(stop):                                                     # the one host read per step
-                    _raise_undrawable(raws)                                        # raises iff a row could not be drawn; else every sequence has finished
-                    break
-            e = ops.splice_rows(tok.to(torch.int32).reshape(B, 1), w_e, None)      # embed_tokens on the new ids
-            h = self.model.decode_step(e.reshape(B, D), cache)
-        _raise_undrawable(raws)
-        seq = torch.stack(toks, dim=1)
-        if not return_dict_in_generate:
-            return seq
-        state = None
-        if return_past:
-            # Of the n emitted tokens the stack has consumed the first n - 1 (slots fed0 .. fed0 + n - 2).  A sequence's real tokens end with its first
-            # eos: the pads behind it that were fed are masked out and its next position is set back by their number; its last real token is pending
-            # iff it was never fed (the sequence did not finish before the last step).
-            n = seq.shape[1]
-            real = torch.full((B,), n, dtype=torch.int64, device=dev)
-            if eos is not None:
-                hit = torch.isin(seq, eos)
-                real = torch.where(hit.any(dim=1), hit.long().argmax(dim=1) + 1, real)
-            j = torch.arange(n - 1, device=dev)[None]
-            cache.key_mask[:, fed0:fed0 + n - 1] = (j < real[:, None]).to(torch.uint8)
-            cache.next_pos = cache.next_pos - (n - 1 - real).clamp_min(0)
-            state = GenerationState(cache=cache, pending=torch.where(real == n, seq[:, -1], torch.full_like(real, -1)))
-        return GenerateOutput(sequences=seq, hidden_states=torch.stack(hids, dim=1) if output_hidden_states else None,
-                              logits=torch.stack(lgs, dim=1) if output_logits else None, past=state,
-                              scores=torch.stack(scs, dim=1) if output_scores else None)
-
-    def _generate_beams(self, beams, C, h, cache, max_new, eos, pad, as_dict, want_hidden, want_logits):
-        """generate()'s loop with beam search, from the last attended state `h` (B, D) on.  The running scores, the finished set and the back-pointers
-        live on the device (ops.BeamState); the host reads `setok_beam_advance`'s 2-int summary once per step, and the hypotheses are materialised
-        from the back-pointers once at the end."""
-        from .generation import GenerateOutput
-        B, D = h.shape
-        n, R, dev = beams.num_beams, beams.num_return_sequences, h.device
-        w_lm = self.lm_head.weight.detach().contiguous()
-        w_e = self.model.embed_tokens.weight.detach().contiguous()
-        state = ops.BeamState(B, n, max_new, dev)
-        cache = cache.expanded(n)
-        fed0 = cache.len                                                           # the first slot a decode step of this call fills: what `reorder` moves starts here
-        running0 = torch.zeros((B, 1), dtype=torch.float32, device=dev)            # step 0: one row per sequence, score 0
-        ws = torch.empty(B * n * (2 * ops.BEAM_MAX_C + 1), dtype=torch.int32, device=dev)
-        hids, lgs = [], []
-        for step in range(max_new):
-            logits = ops.linear(h, w_lm)                                           # (B, V) at step 0, then (B * n, V)
-            cand = ops.beam_topk(logits, running0 if step == 0 else state.run_score, C, ws)
-            tok, src_row, summary = ops.beam_advance(*cand, state, eos, step, beams.length_penalty, beams.early_stopping)
-            if want_hidden:
-                hids.append(h.repeat_interleave(n, dim=0) if step == 0 else h)
-            if want_logits:
-                lgs.append(logits.repeat_interleave(n, dim=0) if step == 0 else logits)
-            go_on, bad = summary.tolist()                                          # the step's one host read
-            if bad:
-                rows = torch.nonzero(cand[3]).flatten().tolist()
-                raise RuntimeError(f"SetokimLlamaPrefill.generate: the logits of sequence(s) {rows} hold a NaN or +inf at beam-search step {step}")
-            if not go_on:
-                break
-            cache.reorder(src_row, fed0, n)
-            e = ops.splice_rows(tok.to(torch.int32).reshape(B * n, 1), w_e, None)
-            h = self.model.decode_step(e.reshape(B * n, D), cache)
-        # the returned hypotheses: the first R entries of every finished set, walked back through the parents
-        length = state.fin_len[:, :R].reshape(B * R).long().clamp_min(1)
-        beam = state.fin_parent[:, :R].reshape(B * R).long()
-        n_new = int(length.max())
-        base = (torch.arange(B, device=dev) * n).repeat_interleave(R)
-        rows = torch.arange(B * R, device=dev)
-        seq = torch.full((B * R, n_new), pad, dtype=torch.int64, device=dev)
-        anc = torch.full((B * R, n_new), -1, dtype=torch.int64, device=dev)
-        seq[rows, length - 1] = state.fin_token[:, :R].reshape(B * R)
-        anc[rows, length - 1] = base + beam
-        for j in range(n_new - 2, -1, -1):
-            live = j <= length - 2                                                 # token j of these hypotheses belongs to running beam `beam` after step j
-            at = base + beam
-            parent = state.bp_parent[j][at].long()
-            seq[:, j] = torch.where(live, state.bp_token[j][at], seq[:, j])
-            anc[:, j] = torch.where(live, base + parent, anc[:, j])
-            beam = torch.where(live, parent, beam)
-        if not as_dict:
-            return seq
-
-        def along(kept):                                                           # (steps, B * n, X) -> (B * R, n_new, X): row j from the state that produced token j
-            got = torch.stack(kept[:n_new], dim=0)[torch.arange(n_new, device=dev)[None], anc.clamp_min(0)]
-            return got * (anc >= 0)[..., None].to(got.dtype)
-
-        return GenerateOutput(sequences=seq, hidden_states=along(hids) if want_hidden else None, logits=along(lgs) if want_logits else None,
-                              sequences_scores=state.fin_score[:, :R].reshape(B * R).clone(), beam_indices=anc.to(torch.int32))
-
-    def _generate_speculative(self, draft, h, cache, prompt_ids, prompt_mask, max_new, eos, pad, sampler, as_dict, want_hidden, want_logits, want_past,
-                              processors=None, want_scores=False):
-        """generate()'s loop with a drafter, from the last attended state `h` (B, D) on.  Between rounds the state lives on the device: pending
-        (B,) int64, count (B,) int32, finished (B,) uint8 and seq (B, max_new) int64; `setok_spec_accept` advances it, and the host reads the
-        kernel's 3-int summary once per round.  With `processors` the K + 1 rows of a round are processed in one launch (row i sees the history plus
-        drafts 0 .. i - 1) before the selection, and the emitted tokens join the history behind the accept rule."""
-        from .generation import GenerateOutput, GenerationState
-        B, D = h.shape
-        K, dev = draft.K, h.device
-        w_lm = self.lm_head.weight.detach().contiguous()
-        w_e = self.model.embed_tokens.weight.detach().contiguous()
-        seq = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
-        count = torch.zeros(B, dtype=torch.int32, device=dev)
-        finished = torch.zeros(B, dtype=torch.uint8, device=dev)
-        pending = torch.zeros(B, dtype=torch.int64, device=dev)
-        summary = torch.zeros(3, dtype=torch.int32, device=dev)
-        u = None if sampler is None else sampler.uniform_matrix(max_new, B, dev)
-        steps = torch.arange(K + 1, device=dev, dtype=torch.int64)[None]
-        rows_b = torch.arange(B, device=dev)[:, None]
-        # outputs: column max_new takes the rows no sequence emitted and is cut off at the end
-        hid_out = torch.zeros((B, max_new + 1, D), dtype=h.dtype, device=dev) if want_hidden else None
-        lg_out, sc_out = None, None
-        proc = None if processors is None else processors.begin(B, dev, prompt_ids, prompt_mask, max_new, eos)
-
-        def select(logits, n):                                                     # logits (B * n, V) -> (B, n) int64
-            if sampler is None:
-                return ops.argmax_rows(logits).reshape(B, n)
-            ur = u[(count.long()[:, None] + steps[:, :n]).clamp_max(max_new - 1), rows_b].reshape(B * n).contiguous()
-            return ops.sample_rows(logits, ur, sampler.temperature, sampler.top_k, sampler.top_p).reshape(B, n)
-
-        def keep(hidden, logits, scores, before, m, n):                            # row i < m[b] of sequence b -> column before[b] + i
-            nonlocal lg_out, sc_out
-            if not (want_hidden or want_logits or want_scores):
-                return
-            cols = torch.where(steps[:, :n] < m.long()[:, None], before.long()[:, None] + steps[:, :n], torch.full_like(steps[:, :n], max_new))
-            if want_hidden:
-                hid_out[rows_b, cols] = hidden.reshape(B, n, D)
-            if want_logits:
-                if lg_out is None:
-                    lg_out = torch.zeros((B, max_new + 1, logits.shape[-1]), dtype=logits.dtype, device=dev)
-                lg_out[rows_b, cols] = logits.reshape(B, n, -1)
-            if want_scores:
-                if sc_out is None:
-                    sc_out = torch.zeros((B, max_new + 1, scores.shape[-1]), dtype=scores.dtype, device=dev)
-                sc_out[rows_b, cols] = scores.reshape(B, n, -1)
-
-        def after_round():
-            mx, live, bad = summary.tolist()                                       # the round's one host read
-            if bad:
-                n = int(count.max())
-                drawn = torch.where((seq[:, :n] < 0) & (torch.arange(n, device=dev)[None] < count[:, None]), -1, 0)
-                _raise_undrawable(list(drawn.unbind(dim=1)))
-            return mx, live
-
-        cache.next_pos = cache.next_pos.contiguous()
-        draft.begin(B, dev, prompt_ids, prompt_mask, max_new)
-        # step 0: the token selected from the last attended state, put into the loop state by the accept rule with no drafts
-        logits = ops.linear(h, w_lm)
-        scores = logits if proc is None else proc.process(logits)
-        sel = select(scores, 1)
-        before = count.clone()
-        emitted, m, _ = ops.spec_accept(sel[:, :0].contiguous(), sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, cache.len,
-                                        summary=summary)
-        cache.key_mask[:, cache.len] = 0                                           # (nothing was fed: the slot the rule marked is not filled yet)
-        keep(h, logits, scores, before, m, 1)
-        if proc is not None:
-            proc.append(emitted, m)
-        draft.update(emitted, m)
-        _, live = after_round()
-        while live > 0:
-            if cache.len + K + 1 > cache.cap:
-                cache = cache.grown(2 * cache.cap)
-            d = draft.propose(pending)
-            if not (isinstance(d, torch.Tensor) and d.dtype == torch.int64 and tuple(d.shape) == (B, K)):
-                raise TypeError(f"SetokimLlamaPrefill.generate: draft.propose must return a (B, K) = ({B}, {K}) int64 tensor")
-            d = d.to(dev).contiguous()
-            live_b = finished == 0
-            am = torch.cat([live_b[:, None], ((d >= 0).long().cummin(dim=1).values > 0) & live_b[:, None]], dim=1)
-            ids = torch.cat([pending[:, None], d], dim=1).clamp_min(0).to(torch.int32)
-            len0 = cache.len
-            hidden = self.model.extend(ops.splice_rows(ids, w_e, None), cache, am)         # (B, K + 1, D): one pass over the weights
-            logits = ops.linear(hidden.reshape(B * (K + 1), D), w_lm)
-            scores = logits if proc is None else proc.process(logits, d)
-            sel = select(scores, K + 1)
-            before = count.clone()
-            emitted, m, _ = ops.spec_accept(d, sel, eos, seq, count, finished, pending, cache.key_mask, cache.next_pos, len0, summary=summary)
-            keep(hidden, logits, scores, before, m, K + 1)
-            if proc is not None:
-                proc.append(emitted, m)
-            draft.update(emitted, m)
-            mx, live = after_round()
-            cache.truncate(len0 + mx)
-        n = int(count.max())
-        out = seq[:, :n].contiguous()
-        if not as_dict:
-            return out
-        state = GenerationState(cache=cache, pending=pending) if want_past else None
-        return GenerateOutput(sequences=out, hidden_states=hid_out[:, :n].contiguous() if want_hidden else None,
-                              logits=lg_out[:, :n].contiguous() if want_logits else None, past=state,
-                              scores=sc_out[:, :n].contiguous() if want_scores else None)
+            return G.loop_speculative(self, req, w_lm, w_e, h, cache, eos, pad if eos is not None else 0, inputs, attention_mask)
+        return G.loop_plain(self, req, w_lm, w_e, h, cache, eos, pad, inputs, attention_mask)
 
     def _head(self, inputs_embeds, attention_mask, position_ids, new_labels, last_token_only, return_loss):
         hidden = self.model._forward(inputs_embeds, attention_mask, position_ids)  # setokim_llama.py:130-140
