@@ -922,6 +922,41 @@ int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const void* q, i
                                        const uint8_t* v_q, const uint8_t* v_s, const uint8_t* key_mask, void* out, int B, int Tn, int H, int Hkv,
                                        int Dh, int cap, int len0, float scale, float* workspace, int64_t workspace_floats);
 
+/* ---- Paged KV cache (csrc/attn_paged.hip): the native-format cache without a capacity per sequence.  One layer's keys / values live in two
+ * pools, k_pool and v_pool (num_pages, Hkv, SETOK_KV_PAGE, Dh) in `dtype` - the rows of one (page, key / value head) are contiguous, as the rows
+ * of one (sequence, key / value head) are in the dense cache.  A sequence is row b of block_table, (B, max_pages) int32 on the device - entry p
+ * is the page that holds its slots [SETOK_KV_PAGE * p, SETOK_KV_PAGE * (p + 1)) - and an int32 length on the device: sequences of one batch
+ * have lengths of their own, a compact sequence has no dead slots (there is no key_mask), and pages go back to a pool when a sequence ends.
+ * A page id outside [0, num_pages) means "no page" to both entries: nothing is written to it, no key of it counts, and no address is formed from
+ * it - a bad table is defined behaviour, never a fault.  Greedy decoding over the element type only: quantised pools and a paged extend
+ * attention are follow-ups.  Pure additions: the ABI version stays 9. */
+
+/* Slots per page.  Equal to SETOK_DECODE_CHUNK (a static_assert in csrc/attn_paged.hip): a chunk's workgroup reads exactly one page, so where a
+ * page lies cannot change a bit of the output. */
+#define SETOK_KV_PAGE 128
+
+/* setok_kv_append through a block table: the post-rotary k and v columns of rows b * T + t of a fused [q: H | k: Hkv | v: Hkv] buffer go to slot
+ * slot0[b] + t of sequence b - page block_table[b][slot / SETOK_KV_PAGE], row slot % SETOK_KV_PAGE of that page.  slot0: (B,) int32 on the
+ * device; a sequence with slot0[b] < 0 is skipped entirely (an idle row of a running batch).  One call serves a prefill (T rows from slot 0; T may
+ * cross page boundaries) and a decode step (T = 1).  Nothing is written for a slot past the table's max_pages entries or whose table entry is no
+ * page; no other byte of the pools is written.  16-byte accesses (qkv and the pools 16-byte aligned); Dh as for the attention below. */
+int setok_kv_append_paged(void* stream, int dtype, const void* qkv, void* k_pool, void* v_pool, const int32_t* block_table, int max_pages,
+                          int num_pages, const int32_t* slot0, int B, int T, int H, int Hkv, int Dh);
+
+/* setok_attention_decode_gqa over the pools: query row b of q (row stride ldq elements, H heads of Dh) against slots [0, lens[b]) of sequence b,
+ * found through its row of the table.  lens: (B,) int32 on the device; slot j counts iff j < lens[b]; lens[b] == 0 gives zeros (the convention for
+ * a sequence without a key).  max_len is the host's upper bound on lens (lens[b] <= max_len <= max_pages * SETOK_KV_PAGE): the grid's chunk
+ * dimension and the workspace come from it, ws_floats >= B * H * ceil(max_len / SETOK_KV_PAGE) * (Dh + 2).  A chunk at or past a sequence's own
+ * length writes the empty partial without loading from the pools or reading the table entry; the merge takes each sequence's chunk count from
+ * lens[b].  Sequence b's output bits are those of setok_attention_decode_gqa at B = 1 on its slots gathered into a dense cache, with an
+ * all-ones mask and len = lens[b]: the same arithmetic in the same order, so they depend on its own q, keys, values and length alone - not on the
+ * table, the pool, B, max_len or the run.  Slots at or past lens[b] and pages no sequence owns may hold anything, NaN included.
+ * Dh / (elements per 16 bytes) in {2, 4, 8, 16, 32} - Dh 16 ... 256 in the 16-bit type, 8 ... 128 in fp32 -; any other head dim is refused (the
+ * generic wave-per-chunk kernel has no paged twin).  q and the pools 16-byte aligned, ldq % 8 == 0. */
+int setok_attention_decode_gqa_paged(void* stream, int dtype, const void* q, int64_t ldq, const void* k_pool, const void* v_pool,
+                                     const int32_t* block_table, int max_pages, int num_pages, const int32_t* lens, void* out, int B, int H, int Hkv,
+                                     int Dh, int max_len, float scale, float* ws, int64_t ws_floats);
+
 /* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
  * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest
  * (csrc/diffusion.hip).  Every entry is asynchronous on `stream`, allocates nothing, synchronises nothing, accepts rows == 0, uses 16-byte

@@ -128,6 +128,8 @@ SIGNATURES = {
     "setok_attention_decode_gqa_fp8kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_kv_append_mxfp4": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i],
     "setok_attention_decode_gqa_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_kv_append_paged": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i],
+    "setok_attention_decode_gqa_paged": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_attention_extend_mxfp4kv_workspace": [_i, _i, _i, _i, _i],
     "setok_attention_extend_gqa_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_linear_skinny_workspace": [_i, _i, _i],

@@ -31,22 +31,6 @@ namespace {
 constexpr int DEC_CHUNK = SETOK_DECODE_CHUNK;
 constexpr int DEC_WAVES = 4;                              // a wave's slice is CHUNK / 4 keys: 32 native (NSTEP = LPR / 2 below), 64 over e4m3 rows
 
-// Sum over aligned groups of N lanes (N a power of two), every lane of a group ending with the same bits: an xor butterfly.  Inside a row of 16 lanes the
-// exchanges are DPP modifiers on the add (quad_perm for xor 1 and 2; once a quad's lanes agree, row_half_mirror and row_mirror pair the same partial sums
-// as xor 4 and xor 8) instead of ds_bpermute round trips through the LDS crossbar.
-template <int CTRL> __device__ inline float dpp_add(float a) {
-    return a + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), CTRL, 0xf, 0xf, false));
-}
-template <int N> __device__ inline float row_sum(float a) {
-    if constexpr (N >= 2) a = dpp_add<0xB1>(a);          // quad_perm [1, 0, 3, 2]
-    if constexpr (N >= 4) a = dpp_add<0x4E>(a);          // quad_perm [2, 3, 0, 1]
-    if constexpr (N >= 8) a = dpp_add<0x141>(a);         // row_half_mirror
-    if constexpr (N >= 16) a = dpp_add<0x140>(a);        // row_mirror
-#pragma unroll
-    for (int o = 16; o < N; o <<= 1) a += __shfl_xor(a, o, 64);
-    return a;
-}
-
 // ---- kv_append ---------------------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void kv_append_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, int B, int Tn, int H, int Hkv,

@@ -1,8 +1,8 @@
-// attn_partials.h — what the attention kernels that cut a sequence's keys into chunks share (attn_decode.hip, attn_extend.hip): every chunk leaves
+// attn_partials.h — what the attention kernels that cut a sequence's keys into chunks share (attn_decode.hip, attn_paged.hip, attn_extend.hip): every chunk leaves
 // fp32 partials — per (sequence, query head, chunk) Dh + 2 floats [max, sum, Dh accumulators] — in the caller's workspace, and a second launch merges a
 // query head's chunks in chunk order.  ONE definition of the merge and of the exponential both sides of it use: a partial is only meaningful to the
 // merge that rescales it.  Also here, once: the cache formats (native, fp8, MXFP4) as the kernels see them, and the wave-per-chunk kernel every head dim without a
-// lane layout falls back to, whichever entry point it came through.
+// lane layout falls back to, whichever entry point it came through; and row_sum, the lane-group reduction of the lane-layout kernels (dense and paged).
 #pragma once
 #include "common.h"
 #include "fp8.h"
@@ -17,6 +17,22 @@ template <typename T> __device__ inline float dec_exp(float x) {
 }
 
 template <typename T> __device__ inline float rnd(float v) { return (float)(T)v; }
+
+// Sum over aligned groups of N lanes (N a power of two), every lane of a group ending with the same bits: an xor butterfly.  Inside a row of 16 lanes the
+// exchanges are DPP modifiers on the add (quad_perm for xor 1 and 2; once a quad's lanes agree, row_half_mirror and row_mirror pair the same partial sums
+// as xor 4 and xor 8) instead of ds_bpermute round trips through the LDS crossbar.
+template <int CTRL> __device__ inline float dpp_add(float a) {
+    return a + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), CTRL, 0xf, 0xf, false));
+}
+template <int N> __device__ inline float row_sum(float a) {
+    if constexpr (N >= 2) a = dpp_add<0xB1>(a);          // quad_perm [1, 0, 3, 2]
+    if constexpr (N >= 4) a = dpp_add<0x4E>(a);          // quad_perm [2, 3, 0, 1]
+    if constexpr (N >= 8) a = dpp_add<0x141>(a);         // row_half_mirror
+    if constexpr (N >= 16) a = dpp_add<0x140>(a);        // row_mirror
+#pragma unroll
+    for (int o = 16; o < N; o <<= 1) a += __shfl_xor(a, o, 64);
+    return a;
+}
 
 template <typename T> struct Raw16;
 template <> struct Raw16<float> { typedef f32x4 type; };
@@ -129,26 +145,32 @@ __global__ __launch_bounds__(64) void attn_chunk_any_kernel(const T* __restrict_
 }
 
 // ---- merge: one workgroup per (sequence, query head), the chunks in chunk order ----------------------------------------------------------------
+// `part`: the query head's partials, chunk c at c * (Dh + 2); `n` of them count (0: zeros).  The ONE loop behind the dense merge, where n is the launch's
+// chunk count, and the paged one (attn_paged.hip), where n comes from the sequence's own length.
 template <typename T>
-__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* __restrict__ ws, T* __restrict__ out, int nch, int H, int Dh) {
-    const int64_t bh = blockIdx.x;                                     // b * H + h; out rows are H * Dh wide
-    const float* part = ws + bh * nch * (Dh + 2);
+__device__ inline void merge_chunks(const float* __restrict__ part, T* __restrict__ out, int n, int Dh) {
     float M = -INFINITY;
-    for (int c = 0; c < nch; ++c) M = fmaxf(M, part[(int64_t)c * (Dh + 2)]);
+    for (int c = 0; c < n; ++c) M = fmaxf(M, part[(int64_t)c * (Dh + 2)]);
     float L = 0.f;
-    for (int c = 0; c < nch; ++c) {
+    for (int c = 0; c < n; ++c) {
         const float mc = part[(int64_t)c * (Dh + 2)];
         L = fmaf(mc == -INFINITY ? 0.f : dec_exp<T>(mc - M), part[(int64_t)c * (Dh + 2) + 1], L);
     }
     const float inv = L > 0.f ? 1.0f / L : 0.f;
     for (int d = threadIdx.x; d < Dh; d += 64) {
         float o = 0.f;
-        for (int c = 0; c < nch; ++c) {
+        for (int c = 0; c < n; ++c) {
             const float mc = part[(int64_t)c * (Dh + 2)];
             o = fmaf(mc == -INFINITY ? 0.f : dec_exp<T>(mc - M), part[(int64_t)c * (Dh + 2) + 2 + d], o);
         }
-        out[bh * Dh + d] = (T)(o * inv);
+        out[d] = (T)(o * inv);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* __restrict__ ws, T* __restrict__ out, int nch, int H, int Dh) {
+    const int64_t bh = blockIdx.x;                                     // b * H + h; out rows are H * Dh wide
+    merge_chunks<T>(ws + bh * nch * (Dh + 2), out + bh * Dh, nch, Dh);
 }
 
 }  // namespace

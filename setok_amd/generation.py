@@ -187,6 +187,123 @@ class KVCache:
         return self._ws
 
 
+def _count(v, name: str, who: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"{who}: {name}={v!r} must be an int >= 1")
+    return v
+
+
+class PagedKVCache:
+    """The native-format cache without a capacity per sequence (include/setok_hip.h, "Paged KV cache"): per layer two pools `k[li]`, `v[li]` of
+    shape (num_pages, Hkv, ops.KV_PAGE, Dh) in the model's element type, shared by `rows` sequences.  A sequence is row r of `block_table`
+    ((rows, max_pages_per_seq) int32 on the device, -1 = no page; entry p holds slots [128 p, 128 p + 128)) and `lens[r]` ((rows,) int32 on the device):
+    every row has a length of its own, a compact sequence has no dead slots (there is no key mask; position == slot), and a finished sequence's
+    pages go back to the pool.  Memory: 2 * layers * num_pages * Hkv * 128 * Dh elements, whatever `rows` is.
+
+    `table_host` / `lens_host` mirror both on the host and `_free` is the host's free list.  The scheduler (this class's methods, called by
+    `LlamaModel.prefill_paged` / `decode_step_paged` and `ContinuousBatcher`) is the only writer, so the mirrors are exact without any device read.
+    The pools are `torch.empty`: nothing depends on their initial contents - a slot is written before the sequence's length covers it."""
+
+    def __init__(self, num_layers: int, rows: int, Hkv: int, Dh: int, dtype: torch.dtype, device, num_pages: int, max_pages_per_seq: int):
+        who = "PagedKVCache"
+        for name, v in (("num_layers", num_layers), ("rows", rows), ("Hkv", Hkv), ("Dh", Dh), ("num_pages", num_pages),
+                        ("max_pages_per_seq", max_pages_per_seq)):
+            _count(v, name, who)
+        self.num_layers, self.rows, self.Hkv, self.Dh, self.dtype = num_layers, rows, Hkv, Dh, dtype
+        self.num_pages, self.max_pages_per_seq = num_pages, max_pages_per_seq
+        pool = lambda: [torch.empty((num_pages, Hkv, ops.KV_PAGE, Dh), dtype=dtype, device=device) for _ in range(num_layers)]
+        self.k: List[torch.Tensor] = pool()
+        self.v: List[torch.Tensor] = pool()
+        self.block_table = torch.full((rows, max_pages_per_seq), -1, dtype=torch.int32, device=device)
+        self.lens = torch.zeros(rows, dtype=torch.int32, device=device)
+        self.table_host: List[List[int]] = [[-1] * max_pages_per_seq for _ in range(rows)]
+        self.lens_host: List[int] = [0] * rows
+        self._free: List[int] = list(range(num_pages))                             # handed out from the front, returned to the back
+        self._zero = torch.zeros(1, dtype=torch.int32, device=device)              # a prefill's slot0
+        self._ws: Optional[torch.Tensor] = None
+
+    @classmethod
+    def for_model(cls, model, rows: int, num_pages: int, max_pages_per_seq: int, device=None) -> "PagedKVCache":
+        """Pools for `model` (a LlamaModel): `rows` sequences at a time, `num_pages` pages of 128 slots per layer, at most `max_pages_per_seq` per sequence."""
+        w = model.norm.weight
+        return cls(len(model.layers), rows, model.num_kv_heads, model.head_dim, w.dtype, device if device is not None else w.device, num_pages,
+                   max_pages_per_seq)
+
+    @property
+    def pages_free(self) -> int:
+        return len(self._free)
+
+    @property
+    def page_nbytes(self) -> int:
+        """Bytes one page takes over all layers, keys and values."""
+        return 2 * self.num_layers * self.Hkv * ops.KV_PAGE * self.Dh * self.k[0].element_size()
+
+    def pages_of(self, row: int) -> List[int]:
+        return [p for p in self.table_host[row] if p >= 0]
+
+    def _row(self, row, who: str) -> int:
+        if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < self.rows:
+            raise ValueError(f"PagedKVCache.{who}: row={row!r} is outside [0, {self.rows})")
+        return row
+
+    def assign(self, row: int, n_slots: int) -> bool:
+        """Give the idle row `row` the ceil(n_slots / 128) pages that hold its slots [0, n_slots): they come off the free list and into the row's
+        table entries.  False, with nothing changed, if the pool cannot supply them.  ValueError for a row that already owns pages, n_slots < 1 or
+        more pages than a table row has entries."""
+        self._row(row, "assign")
+        n = (_count(n_slots, "n_slots", "PagedKVCache.assign") + ops.KV_PAGE - 1) // ops.KV_PAGE
+        if self.pages_of(row):
+            raise ValueError(f"PagedKVCache.assign: row {row} already owns pages (release it first)")
+        if n > self.max_pages_per_seq:
+            raise ValueError(f"PagedKVCache.assign: {n_slots} slots need {n} pages, a sequence has at most max_pages_per_seq = {self.max_pages_per_seq}")
+        if n > len(self._free):
+            return False
+        pages, self._free = self._free[:n], self._free[n:]
+        self.table_host[row] = pages + [-1] * (self.max_pages_per_seq - n)
+        self.block_table[row] = torch.tensor(self.table_host[row], dtype=torch.int32)
+        return True
+
+    def release(self, row: int) -> None:
+        """Return the row's pages to the pool; its table entries become -1 and its length 0.  ValueError for an idle row."""
+        self._row(row, "release")
+        pages = self.pages_of(row)
+        if not pages:
+            raise ValueError(f"PagedKVCache.release: row {row} is idle (it owns no pages)")
+        self._free.extend(pages)
+        self.table_host[row] = [-1] * self.max_pages_per_seq
+        self.lens_host[row] = 0
+        self.block_table[row] = -1
+        self.lens[row] = 0
+
+    def set_len(self, row: int, n: int) -> None:
+        """The row's slots [0, n) are filled (a prefill's last act)."""
+        self.lens_host[row] = n
+        self.lens[row] = n
+
+    def append(self, li: int, qkv: torch.Tensor, T: int, H: int, slot0: torch.Tensor, row: Optional[int] = None) -> None:
+        """Layer `li`: the post-rotary k / v columns of the fused qkv buffer -> slots [slot0[b], slot0[b] + T) of every row (qkv: rows * T rows; a row
+        with slot0 < 0 is skipped), or - with `row` - of that one row (qkv: T rows, slot0 (1,))."""
+        table = self.block_table if row is None else self.block_table[row:row + 1]
+        ops.kv_append_paged(qkv, self.k[li], self.v[li], table, slot0, T, H)
+
+    def attend(self, li: int, q: torch.Tensor, H: int, max_len: int, scale: float, ws: torch.Tensor, out: Optional[torch.Tensor],
+               lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Layer `li`: one query row per (row, query head) against the row's own slots [0, lens[row]) (`lens`: the cache's, or the caller's (rows,)
+        int32 - a decode step attends over the lengths it is about to commit); `max_len` is the host's upper bound on them."""
+        return ops.attention_decode_paged(q, self.k[li], self.v[li], self.block_table, self.lens if lens is None else lens, H, max_len, scale, ws=ws,
+                                          out=out)
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for layers in (self.k, self.v) for t in layers)
+
+    def workspace(self, H: int) -> torch.Tensor:
+        """The decode attention's fp32 partials, sized once for the longest sequence a table row can describe."""
+        need = ops.attention_decode_paged_workspace(self.rows, H, self.Dh, self.max_pages_per_seq * ops.KV_PAGE)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 1), dtype=torch.float32, device=self.lens.device)
+        return self._ws
+
+
 class Sampler:
     """Sampled token selection for `SetokimLlamaPrefill.generate(sampler=...)`: temperature, then top-k, then top-p (HF's order), one launch of
     `setok_sample_rows` per step (include/setok_hip.h, "Sampling", states the rule).  The draw is one uniform number per row per step and that
@@ -807,3 +924,172 @@ def loop_speculative(lm, req: Request, w_lm, w_e, h, cache, eos, pad, prompt_ids
     kept = lambda name, want: outs[name][:, :n].contiguous() if want else None
     return GenerateOutput(sequences=out, hidden_states=kept("hidden", req.want_hidden), logits=kept("logits", req.want_logits),
                           past=GenerationState(cache=cache, pending=pending) if req.want_past else None, scores=kept("scores", req.want_scores))
+
+
+# ---- continuous batching over the paged cache ---------------------------------------------------------------------------------------------------
+@dataclass
+class _Running:
+    ticket: int
+    max_new: int
+    tokens: List[int]
+
+
+class ContinuousBatcher:
+    """Greedy decoding of many requests of different lengths on `rows` rows of one PagedKVCache: a request joins the running batch as soon as a row is
+    idle and the pool can reserve the pages for ALL of its prompt + max_new_tokens slots, and leaves - its pages back in the pool - the step it emits
+    an eos id or its last token.  Because a request's pages are reserved up front, a running request never runs out of pages: nothing is preempted.
+
+    `submit(prompt, max_new_tokens)` queues a request (spliced embeddings (T, D) or token ids (T,)) and returns its ticket; `step()` is one round of
+    the loop and returns the (ticket, tokens) pairs that finished in it; `run(requests)` submits (prompt, max_new_tokens) pairs, steps until drained
+    and returns the token tensors in submit order.  A request's tokens are `lm.generate(inputs_embeds=x[None], max_new_tokens=n, eos_token_id=...)`'s
+    for that request alone - the new tokens, an eos included and nothing behind it: the paged attention gives the dense kernel's bits
+    (include/setok_hip.h, "Paged KV cache") and every other kernel of a step computes a row from that row's operands alone.
+
+    One step: admissions in FIFO order (nothing overtakes the queue's head) - `assign`, `LlamaModel.prefill_paged`, lm_head on the last state,
+    argmax: the first token -, then ONE `LlamaModel.decode_step_paged` over all rows, lm_head at M = rows, argmax, and one host read of the step's
+    tokens.  `stats`: steps, row_steps_active / row_steps_total (the occupancy of the decode steps), pages_high_water, admitted, admitted_midflight
+    (requests that joined while others were running), page_waits (steps in which a row was idle but the head of the queue had to wait for pages),
+    pages_reused (pages handed to a request after another one released them).
+
+    Greedy over the native element type only; refused by name (NotImplementedError): sampler=, beams=, draft=, processors=, prefill_chunk= and a
+    quantised kv_cache=."""
+
+    def __init__(self, lm, rows: int, num_pages: int, max_pages_per_seq: Optional[int] = None, eos_token_id=None, pad_token_id=None, *, sampler=None,
+                 beams=None, draft=None, processors=None, prefill_chunk=None, kv_cache: str = "native"):
+        who = "ContinuousBatcher"
+        for name, given, why in (("sampler=", sampler is not None, "the batcher selects by argmax"),
+                                 ("beams=", beams is not None, "a beam's pages would have to be shared between rows"),
+                                 ("draft=", draft is not None, "a verify pass needs a paged extend attention"),
+                                 ("processors=", processors is not None, "the rows' histories are not kept"),
+                                 ("prefill_chunk=", prefill_chunk is not None, "a window needs a paged extend attention")):
+            if given:
+                raise NotImplementedError(f"{who}: {name} is not implemented over the paged cache ({why}); use SetokimLlamaPrefill.generate")
+        if kv_cache != "native":
+            if kv_cache in KVCache.FORMATS:
+                raise NotImplementedError(f"{who}: kv_cache={kv_cache!r} is not implemented over the paged cache (quantised rows in pages are a follow-up); "
+                                          "the pools hold the model's element type")
+            raise ValueError(f"{who}: kv_cache={kv_cache!r} is not one of 'native', 'fp8', 'mxfp4'")
+        lm.model._refuse_unmerged(who)
+        _count(rows, "rows", who)
+        _count(num_pages, "num_pages", who)
+        if max_pages_per_seq is None:
+            max_pages_per_seq = num_pages
+        _count(max_pages_per_seq, "max_pages_per_seq", who)
+        self.lm, self.rows = lm, rows
+        self.w_lm, self.w_e = lm.lm_head.weight.detach().contiguous(), lm.model.embed_tokens.weight.detach().contiguous()
+        self.device = self.w_lm.device
+        self.cache = PagedKVCache.for_model(lm.model, rows, num_pages, max_pages_per_seq, self.device)
+        self.eos_ids = None if eos_token_id is None else [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
+        self.pad_token_id = pad_token_id                                           # (kept for HF's signature: a finished request leaves, nothing is padded)
+        self.queue: List[Tuple[int, torch.Tensor, int]] = []                       # (ticket, prompt, max_new) in submit order
+        self.running: List[Optional[_Running]] = [None] * rows
+        self.cur = torch.zeros(rows, dtype=torch.int64, device=self.device)        # every row's latest token: the next decode step's input
+        self._tickets = 0
+        self._released: set = set()                                                # pages that went back to the pool at least once
+        self.stats = dict(steps=0, row_steps_active=0, row_steps_total=0, pages_high_water=0, admitted=0, admitted_midflight=0, page_waits=0,
+                          pages_reused=0)
+
+    @property
+    def occupancy(self) -> float:
+        return self.stats["row_steps_active"] / max(self.stats["row_steps_total"], 1)
+
+    def submit(self, inputs_embeds=None, max_new_tokens: int = 1, input_ids=None) -> int:
+        """Queue one request: its spliced prompt embeddings (T, D), or its token ids (T,) (as `input_ids=`, or an integer tensor in the first place).
+        Returns the ticket.  ValueError - the queue and the cache untouched - if T + max_new_tokens slots cannot fit in max_pages_per_seq pages, or
+        could never fit in the pool."""
+        who = "ContinuousBatcher.submit"
+        if (inputs_embeds is None) == (input_ids is None):
+            raise ValueError(f"{who}: pass the prompt as inputs_embeds (T, D) or as input_ids (T,), one of them")
+        prompt = inputs_embeds if input_ids is None else input_ids
+        if not isinstance(prompt, torch.Tensor):
+            raise TypeError(f"{who}: the prompt must be a tensor, got {type(prompt).__name__}")
+        D = self.w_e.shape[1]
+        if prompt.is_floating_point():
+            if prompt.dim() != 2 or prompt.shape[1] != D or input_ids is not None:
+                raise ValueError(f"{who}: inputs_embeds {tuple(prompt.shape)} is not (T, D = {D})")
+        elif prompt.dim() != 1 or prompt.dtype == torch.bool:
+            raise ValueError(f"{who}: input_ids {tuple(prompt.shape)} {prompt.dtype} is not an integer (T,)")
+        _count(max_new_tokens, "max_new_tokens", who)
+        T = prompt.shape[0]
+        if T < 1:
+            raise ValueError(f"{who}: an empty prompt")
+        pages = (T + max_new_tokens + ops.KV_PAGE - 1) // ops.KV_PAGE
+        if pages > self.cache.max_pages_per_seq or pages > self.cache.num_pages:
+            raise ValueError(f"{who}: {T} + {max_new_tokens} slots need {pages} pages; a sequence has at most max_pages_per_seq = "
+                             f"{self.cache.max_pages_per_seq} and the pool num_pages = {self.cache.num_pages}")
+        ticket, self._tickets = self._tickets, self._tickets + 1
+        self.queue.append((ticket, prompt, max_new_tokens))
+        return ticket
+
+    def _tokens_of(self, h: torch.Tensor) -> torch.Tensor:
+        """States (M, D) -> lm_head -> the rows' argmax, (M,) int64 on the device."""
+        return ops.argmax_rows(ops.linear(h, self.w_lm))
+
+    def _embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
+        """Token ids (M,) -> embed_tokens' rows (M, D)."""
+        return ops.splice_rows(ids.to(device=self.device, dtype=torch.int32).reshape(-1, 1), self.w_e, None).reshape(ids.shape[0], -1)
+
+    def _admit(self) -> List[int]:
+        """Admissions of this step, FIFO: the rows that got a request, each with its first token in `cur`."""
+        cache, st, fresh = self.cache, self.stats, []
+        while self.queue:
+            idle = [r for r in range(self.rows) if self.running[r] is None]
+            if not idle:
+                break
+            ticket, prompt, max_new = self.queue[0]
+            row, T = idle[0], prompt.shape[0]
+            if not cache.assign(row, T + max_new):
+                st["page_waits"] += 1                                              # a row is idle, the pages are not there yet: nothing overtakes
+                break
+            self.queue.pop(0)
+            st["admitted"] += 1
+            st["admitted_midflight"] += int(any(self.running[r] is not None and r not in fresh for r in range(self.rows)))
+            st["pages_reused"] += sum(p in self._released for p in cache.pages_of(row))
+            x = prompt.to(self.device) if prompt.is_floating_point() else self._embed_ids(prompt)
+            h = self.lm.model.prefill_paged(x[None], cache, row)
+            self.cur[row:row + 1] = self._tokens_of(h[:, -1].contiguous())
+            self.running[row] = _Running(ticket, max_new, [])
+            fresh.append(row)
+        st["pages_high_water"] = max(st["pages_high_water"], cache.num_pages - cache.pages_free)
+        return fresh
+
+    def step(self) -> List[Tuple[int, torch.Tensor]]:
+        """One round: admissions with their prefills, one decode step over all rows, one host read, releases.  Returns [(ticket, tokens (n,) int64)]
+        of the requests that finished in it."""
+        fresh = self._admit()
+        if all(r is None for r in self.running):
+            return []
+        first = self.cur.clone() if fresh else None                               # the admitted rows' first tokens (the decode step overwrites `cur`)
+        # a running row decodes unless it was admitted with max_new_tokens = 1: its first token is its last
+        flags = [r is not None and not (i in fresh and r.max_new == 1) for i, r in enumerate(self.running)]
+        if any(flags):
+            active = torch.tensor(flags, dtype=torch.bool, device=self.device)
+            h = self.lm.model.decode_step_paged(self._embed_ids(self.cur), self.cache, active, active_host=flags)
+            self.cur = self._tokens_of(h)
+            self.stats["steps"] += 1
+            self.stats["row_steps_active"] += sum(flags)
+            self.stats["row_steps_total"] += self.rows
+        read = (self.cur if first is None else torch.stack([self.cur, first])).tolist()      # the step's one host read
+        toks, firsts = (read, None) if first is None else read
+        done = []
+        for row, run in enumerate(self.running):
+            if run is None:
+                continue
+            new = ([firsts[row]] if row in fresh else []) + ([toks[row]] if flags[row] else [])
+            for t in new:
+                run.tokens.append(int(t))
+                if len(run.tokens) == run.max_new or (self.eos_ids is not None and int(t) in self.eos_ids):
+                    self._released.update(self.cache.pages_of(row))
+                    self.cache.release(row)
+                    self.running[row] = None
+                    done.append((run.ticket, torch.tensor(run.tokens, dtype=torch.int64, device=self.device)))
+                    break
+        return done
+
+    def run(self, requests) -> List[torch.Tensor]:
+        """Submit every (prompt, max_new_tokens) pair, step until the queue and the rows are empty; the token tensors in submit order."""
+        tickets = [self.submit(p, n) for p, n in requests]
+        out = {}
+        while self.queue or any(r is not None for r in self.running):
+            out.update(self.step())
+        return [out[t] for t in tickets]

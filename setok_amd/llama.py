@@ -455,6 +455,85 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.next_pos = cache.next_pos + am.sum(1)
         return ops.rmsnorm(x, pk["norm"], self.eps, out=y).reshape(B, Tn, D)
 
+    def _check_paged(self, who: str, cache) -> None:
+        from .generation import PagedKVCache
+        self._refuse_unmerged(who)
+        if not isinstance(cache, PagedKVCache):
+            raise TypeError(f"{who}: cache must be a generation.PagedKVCache, got {type(cache).__name__}")
+        if (cache.num_layers != len(self.layers) or cache.dtype != self.norm.weight.dtype or cache.Hkv != self.num_kv_heads
+                or cache.Dh != self.head_dim):
+            raise ValueError(f"{who}: the cache ({cache.num_layers} layers, Hkv={cache.Hkv}, Dh={cache.Dh}, {cache.dtype}) was not built for this "
+                             f"model ({len(self.layers)} layers, Hkv={self.num_kv_heads}, Dh={self.head_dim}, {self.norm.weight.dtype})")
+
+    @torch.no_grad()
+    def prefill_paged(self, inputs_embeds, cache, row: int):
+        """The prefill of ONE compact sequence into row `row` of a generation.PagedKVCache: inputs_embeds (1, T, D) -> the final-norm hidden states
+        (1, T, D).  The dense `prefill` at B = 1 without a mask - the same calls in the same order, so the same bits -: positions are arange(T), the
+        attention runs over the pass's own q | k | v, and every layer's keys / values go to slots [0, T) of the row through the table (T may cross
+        pages).  Afterwards lens[row] = T.  The row must already own pages for T slots (`cache.assign`) and be empty (ValueError otherwise)."""
+        who = "LlamaModel.prefill_paged"
+        self._check_paged(who, cache)
+        B, T, D = inputs_embeds.shape
+        if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < cache.rows:
+            raise ValueError(f"{who}: row={row!r} is outside [0, {cache.rows})")
+        room = len(cache.pages_of(row)) * ops.KV_PAGE
+        if B != 1 or T < 1 or cache.lens_host[row] != 0 or T > room:
+            raise ValueError(f"{who}: row {row} (length {cache.lens_host[row]}, pages for {room} slots) cannot take a prefill of B={B}, T={T} "
+                             "(one sequence, into an empty row that owns pages for its T slots)")
+        pk = self._pack()
+        H, Hkv, dh = self.num_heads, self.num_kv_heads, self.head_dim
+        x = inputs_embeds.to(self.norm.weight.dtype).reshape(T, D).contiguous().clone()
+        pos = torch.arange(T, device=x.device, dtype=torch.int64)
+        slot0 = cache._zero
+
+        def attend(li, qkv):
+            cache.append(li, qkv, T, H, slot0, row=row)
+            return ops.attention_causal(qkv, None, 1, T, H, dh, dh ** -0.5, Hkv)
+        y = self._run_layers(x, pk["layers"], pos, attend, stream=False)
+        cache.set_len(row, T)
+        return ops.rmsnorm(x, pk["norm"], self.eps, out=y).reshape(1, T, D)
+
+    @torch.no_grad()
+    def decode_step_paged(self, inputs_embeds, cache, active, active_host=None):
+        """One token for every row of a generation.PagedKVCache, at M = rows: inputs_embeds (rows, D) -> the final-norm hidden states (rows, D).
+        `active` (rows,) bool on the device says which rows hold a running sequence.  An active row's token is rotated to position lens[row] (compact:
+        position == slot), appended at that slot and attends over lens[row] + 1 slots; afterwards lens += active.  An idle row's state is computed and
+        means nothing; its pages and length are not touched (slot0 = -1 skips its append, and it attends over its unchanged length).
+        `active_host`: the same flags as a host sequence of bools - what a scheduler has anyway; without it they are read back from `active`
+        (a device read).  The host mirror of the lengths and the attention's `max_len` come from it.  ValueError if an active row lacks a page
+        for its next slot."""
+        who = "LlamaModel.decode_step_paged"
+        self._check_paged(who, cache)
+        R, D = inputs_embeds.shape
+        if R != cache.rows or tuple(active.shape) != (R,) or active.dtype != torch.bool:
+            raise ValueError(f"{who}: a step is (rows, D) states and (rows,) bool flags for the cache's rows = {cache.rows}, got {R} and {tuple(active.shape)} {active.dtype}")
+        flags = [bool(a) for a in (active.tolist() if active_host is None else active_host)]
+        if len(flags) != R:
+            raise ValueError(f"{who}: active_host has {len(flags)} entries for {R} rows")
+        new_host = [n + a for n, a in zip(cache.lens_host, flags)]
+        for r in range(R):
+            if flags[r] and new_host[r] > len(cache.pages_of(r)) * ops.KV_PAGE:
+                raise ValueError(f"{who}: row {r} holds {cache.lens_host[r]} slots and owns pages for {len(cache.pages_of(r)) * ops.KV_PAGE}: no room for one more")
+        pk = self._pack()
+        H, dh = self.num_heads, self.head_dim
+        x = inputs_embeds.to(self.norm.weight.dtype).contiguous().clone()
+        lens = cache.lens
+        pos = lens.to(torch.int64)
+        slot0 = torch.where(active, lens, torch.full_like(lens, -1))
+        new_lens = lens + active.to(torch.int32)
+        max_len = max(new_host)
+        ws, scale, o = cache.workspace(H), dh ** -0.5, None
+
+        def attend(li, qkv):
+            nonlocal o
+            cache.append(li, qkv, 1, H, slot0)
+            o = cache.attend(li, qkv, H, max_len, scale, ws, o, lens=new_lens)
+            return o
+        y = self._run_layers(x, pk["layers"], pos, attend)
+        cache.lens = new_lens
+        cache.lens_host = new_host
+        return ops.rmsnorm(x, pk["norm"], self.eps, out=y)
+
 
 def _refuse_unsupported_llama_fields(g) -> None:
     """The prefill reads hidden / intermediate sizes, layer and head counts, `num_key_value_heads`, `rms_norm_eps` and `rope_theta` — plain

@@ -828,6 +828,52 @@ def attention_decode_fp8kv(q: Tensor, k_q: Tensor, k_e: Tensor, v_q: Tensor, v_e
                              DECODE_CHUNK_FP8KV, ws, out)
 
 
+# ---- the paged KV cache (csrc/attn_paged.hip) ----------------------------------------------------------------------------------------------------
+KV_PAGE = 128                                     # SETOK_KV_PAGE of include/setok_hip.h (== DECODE_CHUNK: a chunk's workgroup reads one page)
+
+
+def _paged_shapes(k_pool: Tensor, v_pool: Tensor, block_table: Tensor, per_seq: Tensor) -> Tuple[int, int, int, int, int]:
+    num_pages, Hkv, page, Dh = k_pool.shape
+    assert page == KV_PAGE and v_pool.shape == k_pool.shape and k_pool.dtype == v_pool.dtype
+    B, max_pages = block_table.shape
+    assert block_table.dtype == torch.int32 and per_seq.dtype == torch.int32 and per_seq.shape == (B,)
+    return num_pages, Hkv, Dh, B, max_pages
+
+
+def kv_append_paged(qkv: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, slot0: Tensor, T: int, H: int) -> None:
+    """The post-rotary k / v columns of rows b*T + t of qkv ([q: H | k: Hkv | v: Hkv]) -> slot slot0[b] + t of sequence b: page
+    block_table[b][slot // KV_PAGE] of the (num_pages, Hkv, KV_PAGE, Dh) pools, row slot % KV_PAGE.  block_table (B, max_pages) and slot0 (B,)
+    are int32 on the device; a sequence with slot0[b] < 0 is skipped, a table entry outside [0, num_pages) is no page (nothing is written)."""
+    num_pages, Hkv, Dh, B, max_pages = _paged_shapes(k_pool, v_pool, block_table, slot0)
+    assert qkv.dtype == k_pool.dtype and qkv.shape == (B * T, (H + 2 * Hkv) * Dh)
+    _lib.call("setok_kv_append_paged", _stream(), _code(qkv.dtype), _p(qkv), _p(k_pool), _p(v_pool), _p(block_table), max_pages, num_pages, _p(slot0),
+              B, T, H, Hkv, Dh)
+
+
+def attention_decode_paged_workspace(B: int, H: int, Dh: int, max_len: int) -> int:
+    """Floats of workspace setok_attention_decode_gqa_paged needs for lengths up to `max_len`."""
+    return B * H * ((max_len + KV_PAGE - 1) // KV_PAGE) * (Dh + 2)
+
+
+def attention_decode_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, lens: Tensor, H: int, max_len: int, scale: float,
+                           ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """One query row per (sequence, query head) against slots [0, lens[b]) of sequence b, found through row b of block_table in the pools; q: (B, >=
+    H*Dh) rows of stride q.stride(0); lens (B,) int32 on the device, `max_len` the host's upper bound on it.  Returns (B, H*Dh); a sequence's bits
+    are attention_decode's at B = 1 on its gathered slots."""
+    num_pages, Hkv, Dh, B, max_pages = _paged_shapes(k_pool, v_pool, block_table, lens)
+    assert q.dtype == k_pool.dtype and q.shape[0] == B and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    need = attention_decode_paged_workspace(B, H, Dh, max_len)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_decode_gqa_paged", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_pool), _p(v_pool), _p(block_table),
+              max_pages, num_pages, _p(lens), _p(out), B, H, Hkv, Dh, max_len, scale, _p(ws), ws.numel())
+    return out
+
+
 # ---- extending a cache by Tn tokens (csrc/attn_extend.hip) ---------------------------------------------------------------------------------------
 EXTEND_CHUNK = 256                                # SETOK_EXTEND_CHUNK of include/setok_hip.h
 
