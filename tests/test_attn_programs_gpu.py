@@ -10,10 +10,9 @@ below the bound, and equal bits on a second run.  The bound is the project's 16-
 of torch's own fp32 evaluation of the same formula against fp64 (a different summation order), floored at the existing 3e-6: one fp32 ulp of a
 score of 50 nats is already 4e-6 in the probability.  Every measured figure goes to SETOK_PARITY_LOG (profiles/attn_programs_parity.txt).
 
-The backward kernels are not here, and are still untested at steered scores.  They are not free of a running maximum: the first walk of
-attn_causal_bwd_dq_kernel (attn_causal_bwd.hip, `m_run` / `l_run`) is the forward's online maximum and sum over the key tiles, from which it forms the
-log-sum-exp that it and the dK / dV kernel then use.  A fair bar for them needs a reference that takes the rounded `out` as given (D = dO . out):
-separate work.  The extend kernels and the decode kernel over the fp8 cache are in tests/test_cache_attn_programs_gpu.py.  `pytest -m gpu`."""
+The backward kernels are in tests/test_attn_bwd_programs_gpu.py: the same programs plus pairs of hot keys, against a reference that takes the
+rounded `out` as given (D = dO . out) and an error-scale bound per output row (tests/attn_bwd_programs.py; shown attainable and sharp on the CPU in
+tests/test_attn_bwd_programs_cpu.py).  The extend kernels and the decode kernel over the fp8 cache are in tests/test_cache_attn_programs_gpu.py.  `pytest -m gpu`."""
 import numpy as np
 import pytest
 import torch
