@@ -928,8 +928,8 @@ int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const void* q, i
  * is the page that holds its slots [SETOK_KV_PAGE * p, SETOK_KV_PAGE * (p + 1)) - and an int32 length on the device: sequences of one batch
  * have lengths of their own, a compact sequence has no dead slots (there is no key_mask), and pages go back to a pool when a sequence ends.
  * A page id outside [0, num_pages) means "no page" to both entries: nothing is written to it, no key of it counts, and no address is formed from
- * it - a bad table is defined behaviour, never a fault.  Greedy decoding over the element type only: quantised pools and a paged extend
- * attention are follow-ups.  Pure additions: the ABI version stays 9. */
+ * it - a bad table is defined behaviour, never a fault.  Greedy decoding over the element type only: quantised pools are a follow-up
+ * (DESIGN.md §7 f17); the extend attention over pages is the next section.  Pure additions: the ABI version stays 9. */
 
 /* Slots per page.  Equal to SETOK_DECODE_CHUNK (a static_assert in csrc/attn_paged.hip): a chunk's workgroup reads exactly one page, so where a
  * page lies cannot change a bit of the output. */
@@ -956,6 +956,32 @@ int setok_kv_append_paged(void* stream, int dtype, const void* qkv, void* k_pool
 int setok_attention_decode_gqa_paged(void* stream, int dtype, const void* q, int64_t ldq, const void* k_pool, const void* v_pool,
                                      const int32_t* block_table, int max_pages, int num_pages, const int32_t* lens, void* out, int B, int H, int Hkv,
                                      int Dh, int max_len, float scale, float* ws, int64_t ws_floats);
+
+/* ---- Paged extend attention (csrc/attn_extend_paged.hip): setok_attention_extend_gqa over the pools of the paged KV cache above - Tn >= 1 query
+ * rows per sequence against pages that are already filled.  What lets requests share a prompt prefix (whole pages, counted by reference on the host;
+ * a request runs only its remainder), and what a verify pass or a prefill window over pages will call.  Pure additions: the ABI version stays 9. */
+
+/* Floats of workspace setok_attention_extend_gqa_paged needs: setok_attention_extend_workspace's rule at len0 = max_len0 (the same partition into
+ * partials, sized for the longest sequence of the call). */
+int64_t setok_attention_extend_paged_workspace(int dtype, int B, int Tn, int H, int Hkv, int Dh, int max_len0);
+
+/* Query row b * Tn + i of q (row stride ldq elements, H heads of Dh) against the slots of sequence b, found through its row of the table: it counts
+ * slot j iff j <= len0[b] + i and block_table[b][j / SETOK_KV_PAGE] is a page.  The new rows' keys / values are already in slots [len0[b], len0[b] +
+ * Tn) (setok_kv_append_paged with slot0 = len0).  len0: (B,) int32 on the device; len0[b] < 0 is an idle sequence - its Tn output rows are exact
+ * zeros and nothing of the pools or the table is read for it.  max_len0 is the host's upper bound on len0 (len0[b] <= max_len0, max_len0 + Tn <=
+ * max_pages * SETOK_KV_PAGE): the grid's span dimension and the workspace come from it.  A table entry outside [0, num_pages) is "no page", as
+ * above: no key of that page counts, no address is formed from the id, nothing is loaded for it.  Slots at or above len0[b] + Tn and pages nobody
+ * points at may hold anything, NaN included.
+ * Sequence b's output bits are those of setok_attention_extend_gqa at B = 1, len0 = len0[b], on its slots gathered into a dense cache under an
+ * all-ones mask (a missing page: a mask that is zero on its SETOK_KV_PAGE slots): the dense kernels' key tiles (32 slots from slot 0), chunks and
+ * spans never straddle a page, so the partition into partials, the arithmetic and the merge order are the dense call's - the bits depend on the
+ * sequence's own q, keys, values and length alone, not on the table, the pool, B, max_len0 or the run.  Both dense paths have a twin: the MFMA
+ * kernel (this build's 16-bit dtype, Dh = 128; NW = 1 / 4 and the span rule on H / Hkv * Tn as there) and the wave-per-chunk kernel (everything
+ * else).  Dh as for setok_attention_decode_gqa_paged; q and the pools 16-byte aligned, ldq % 8 == 0, ws 8-byte aligned,
+ * ws_floats >= setok_attention_extend_paged_workspace(...).  B == 0 launches nothing. */
+int setok_attention_extend_gqa_paged(void* stream, int dtype, const void* q, int64_t ldq, const void* k_pool, const void* v_pool,
+                                     const int32_t* block_table, int max_pages, int num_pages, const int32_t* len0, void* out, int B, int Tn, int H,
+                                     int Hkv, int Dh, int max_len0, float scale, float* ws, int64_t ws_floats);
 
 /* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
  * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest

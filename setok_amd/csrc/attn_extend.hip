@@ -198,8 +198,7 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __rest
     }
 }
 
-// slots per partial on the path a call takes: the MFMA kernel with more than 32 stacked rows spans XSPAN chunks, everything else one
-static inline int extend_span(bool low, int Tn, int H, int Hkv, int Dh) { return low && Dh == XD && (H / Hkv) * Tn > 32 ? XSPAN * EXT_CHUNK : EXT_CHUNK; }
+static_assert(XD == 128 && XSPAN * EXT_CHUNK == SETOK_EXTEND_SPAN * SETOK_EXTEND_CHUNK, "extend_span (attn_partials.h) states this kernel's span rule");
 
 template <typename T>
 int extend_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, const uint8_t* km, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh,

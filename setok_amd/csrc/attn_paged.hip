@@ -231,14 +231,6 @@ int decode_paged_t(const char* name, hipStream_t s, const T* q, int64_t ldq, con
     return SETOK_OK;
 }
 
-// The head dims with a lane layout in the native format: Dh / VEC in {2, 4, 8, 16, 32} (16 ... 256 in 16 bits, 8 ... 128 in fp32).
-bool paged_head_dim(int dtype, int Dh) {
-    const int vec = dtype == SETOK_F32 ? 4 : 8;
-    if (Dh <= 0 || Dh % vec != 0) return false;
-    const int lpr = Dh / vec;
-    return lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32;
-}
-
 }  // namespace
 
 extern "C" int setok_kv_append_paged(void* stream, int dtype, const void* qkv, void* k_pool, void* v_pool, const int32_t* block_table, int max_pages,

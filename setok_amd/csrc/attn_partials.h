@@ -1,4 +1,4 @@
-// attn_partials.h — what the attention kernels that cut a sequence's keys into chunks share (attn_decode.hip, attn_paged.hip, attn_extend.hip): every chunk leaves
+// attn_partials.h — what the attention kernels that cut a sequence's keys into chunks share (attn_decode.hip, attn_paged.hip, attn_extend.hip, attn_extend_paged.hip): every chunk leaves
 // fp32 partials — per (sequence, query head, chunk) Dh + 2 floats [max, sum, Dh accumulators] — in the caller's workspace, and a second launch merges a
 // query head's chunks in chunk order.  ONE definition of the merge and of the exponential both sides of it use: a partial is only meaningful to the
 // merge that rescales it.  Also here, once: the cache formats (native, fp8, MXFP4) as the kernels see them, and the wave-per-chunk kernel every head dim without a
@@ -165,6 +165,21 @@ __device__ inline void merge_chunks(const float* __restrict__ part, T* __restric
         }
         out[d] = (T)(o * inv);
     }
+}
+
+// ---- host rules the dense and the paged entries share ---------------------------------------------------------------------------------------------
+// Slots per partial on the path an extend call takes: the MFMA kernel (16-bit, head dim 128) with more than 32 stacked rows spans SETOK_EXTEND_SPAN
+// chunks, everything else one.  `low`: the call's element type is the build's 16-bit type.
+static inline int extend_span(bool low, int Tn, int H, int Hkv, int Dh) {
+    return low && Dh == 128 && (H / Hkv) * Tn > 32 ? SETOK_EXTEND_SPAN * SETOK_EXTEND_CHUNK : SETOK_EXTEND_CHUNK;
+}
+
+// The head dims the paged entries take, those with a lane layout in the native format: Dh / VEC in {2, 4, 8, 16, 32} (16 ... 256 in 16 bits, 8 ... 128 in fp32).
+static inline bool paged_head_dim(int dtype, int Dh) {
+    const int vec = dtype == SETOK_F32 ? 4 : 8;
+    if (Dh <= 0 || Dh % vec != 0) return false;
+    const int lpr = Dh / vec;
+    return lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32;
 }
 
 template <typename T>

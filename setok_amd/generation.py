@@ -200,6 +200,10 @@ class PagedKVCache:
     every row has a length of its own, a compact sequence has no dead slots (there is no key mask; position == slot), and a finished sequence's
     pages go back to the pool.  Memory: 2 * layers * num_pages * Hkv * 128 * Dh elements, whatever `rows` is.
 
+    Pages are counted by reference (`page_refs`, on the host; 0 = free): a row holds one reference to each page of its table entries, `assign(shared=)`
+    points a row's first entries at pages somebody already holds, `detach` turns a row's references into the caller's and `drop` gives those back.  Shared
+    pages are never written: sharing is in whole pages and a row's first own slot is at a page boundary, so there is no copy-on-write.
+
     `table_host` / `lens_host` mirror both on the host and `_free` is the host's free list.  The scheduler (this class's methods, called by
     `LlamaModel.prefill_paged` / `decode_step_paged` and `ContinuousBatcher`) is the only writer, so the mirrors are exact without any device read.
     The pools are `torch.empty`: nothing depends on their initial contents - a slot is written before the sequence's length covers it."""
@@ -219,8 +223,10 @@ class PagedKVCache:
         self.table_host: List[List[int]] = [[-1] * max_pages_per_seq for _ in range(rows)]
         self.lens_host: List[int] = [0] * rows
         self._free: List[int] = list(range(num_pages))                             # handed out from the front, returned to the back
+        self.page_refs: List[int] = [0] * num_pages                                # references per page: table entries + what `detach` handed out; 0 = free
         self._zero = torch.zeros(1, dtype=torch.int32, device=device)              # a prefill's slot0
         self._ws: Optional[torch.Tensor] = None
+        self._ws_extend: Optional[torch.Tensor] = None
 
     @classmethod
     def for_model(cls, model, rows: int, num_pages: int, max_pages_per_seq: int, device=None) -> "PagedKVCache":
@@ -246,34 +252,77 @@ class PagedKVCache:
             raise ValueError(f"PagedKVCache.{who}: row={row!r} is outside [0, {self.rows})")
         return row
 
-    def assign(self, row: int, n_slots: int) -> bool:
-        """Give the idle row `row` the ceil(n_slots / 128) pages that hold its slots [0, n_slots): they come off the free list and into the row's
-        table entries.  False, with nothing changed, if the pool cannot supply them.  ValueError for a row that already owns pages, n_slots < 1 or
-        more pages than a table row has entries."""
+    def assign(self, row: int, n_slots: int, shared=()) -> bool:
+        """Give the idle row `row` the ceil(n_slots / 128) pages that hold its slots [0, n_slots).  The first len(shared) table entries are the
+        pages in `shared` - pages somebody already holds (count >= 1, else ValueError), each of which gains one reference -; the others come off
+        the free list with count 1.  False, with nothing changed, if the pool cannot supply them.  ValueError for a row that already owns pages,
+        n_slots < 1, more pages than a table row has entries, or len(shared) * 128 >= n_slots: a row must own the page it writes to."""
         self._row(row, "assign")
         n = (_count(n_slots, "n_slots", "PagedKVCache.assign") + ops.KV_PAGE - 1) // ops.KV_PAGE
+        shared = list(shared)
         if self.pages_of(row):
             raise ValueError(f"PagedKVCache.assign: row {row} already owns pages (release it first)")
         if n > self.max_pages_per_seq:
             raise ValueError(f"PagedKVCache.assign: {n_slots} slots need {n} pages, a sequence has at most max_pages_per_seq = {self.max_pages_per_seq}")
-        if n > len(self._free):
+        for p in shared:
+            if isinstance(p, bool) or not isinstance(p, int) or not 0 <= p < self.num_pages or self.page_refs[p] < 1:
+                raise ValueError(f"PagedKVCache.assign: shared page {p!r} is not a page somebody holds (a free page cannot be shared)")
+        if len(shared) * ops.KV_PAGE >= n_slots:
+            raise ValueError(f"PagedKVCache.assign: {len(shared)} shared pages cover all of the row's {n_slots} slots (a row must own the page it "
+                             "writes to: shared pages are never written)")
+        own = n - len(shared)
+        if own > len(self._free):
             return False
-        pages, self._free = self._free[:n], self._free[n:]
-        self.table_host[row] = pages + [-1] * (self.max_pages_per_seq - n)
+        pages, self._free = self._free[:own], self._free[own:]
+        for p in shared + pages:
+            self.page_refs[p] += 1
+        self.table_host[row] = shared + pages + [-1] * (self.max_pages_per_seq - n)
         self.block_table[row] = torch.tensor(self.table_host[row], dtype=torch.int32)
         return True
 
-    def release(self, row: int) -> None:
-        """Return the row's pages to the pool; its table entries become -1 and its length 0.  ValueError for an idle row."""
-        self._row(row, "release")
-        pages = self.pages_of(row)
-        if not pages:
-            raise ValueError(f"PagedKVCache.release: row {row} is idle (it owns no pages)")
-        self._free.extend(pages)
+    def _idle(self, row: int) -> None:
         self.table_host[row] = [-1] * self.max_pages_per_seq
         self.lens_host[row] = 0
         self.block_table[row] = -1
         self.lens[row] = 0
+
+    def release(self, row: int) -> None:
+        """Every page of the row loses one reference; those that reach 0 go to the back of the free list in table order.  The row's table entries
+        become -1 and its length 0.  ValueError for an idle row."""
+        self._row(row, "release")
+        pages = self.pages_of(row)
+        if not pages:
+            raise ValueError(f"PagedKVCache.release: row {row} is idle (it owns no pages)")
+        self._unref(pages)
+        self._idle(row)
+
+    def _unref(self, pages: List[int]) -> None:
+        for p in pages:
+            self.page_refs[p] -= 1
+            if self.page_refs[p] == 0:
+                self._free.append(p)
+
+    def detach(self, row: int) -> List[int]:
+        """The row becomes idle - entries -1, length 0, on the device and in the host mirrors - but its pages are not freed: the caller now holds
+        the row's reference to each of the returned pages (table order) and gives it back with `drop`, after handing the pages to other rows as
+        `assign(shared=)` if it likes.  ValueError for an idle row."""
+        self._row(row, "detach")
+        pages = self.pages_of(row)
+        if not pages:
+            raise ValueError(f"PagedKVCache.detach: row {row} is idle (it owns no pages)")
+        self._idle(row)
+        return pages
+
+    def drop(self, pages) -> None:
+        """Give back one reference to each page of `pages` (what `detach` handed out); a page whose count reaches 0 goes to the back of the free
+        list.  ValueError, with nothing changed, for a page id out of range or a count that would go below 0."""
+        pages = list(pages)
+        for p in set(pages):
+            if isinstance(p, bool) or not isinstance(p, int) or not 0 <= p < self.num_pages:
+                raise ValueError(f"PagedKVCache.drop: page {p!r} is outside [0, {self.num_pages})")
+            if self.page_refs[p] < pages.count(p):
+                raise ValueError(f"PagedKVCache.drop: page {p} has {self.page_refs[p]} references, {pages.count(p)} to give back")
+        self._unref(pages)
 
     def set_len(self, row: int, n: int) -> None:
         """The row's slots [0, n) are filled (a prefill's last act)."""
@@ -293,8 +342,21 @@ class PagedKVCache:
         return ops.attention_decode_paged(q, self.k[li], self.v[li], self.block_table, self.lens if lens is None else lens, H, max_len, scale, ws=ws,
                                           out=out)
 
+    def extend_attend(self, li: int, q: torch.Tensor, H: int, Tn: int, max_len0: int, scale: float, ws: torch.Tensor, out: Optional[torch.Tensor],
+                      table: torch.Tensor, len0: torch.Tensor) -> torch.Tensor:
+        """Layer `li`: Tn query rows per (sequence, query head) of the sequences `table` (n, max_pages_per_seq) describes, each behind its own
+        len0 (n,) int32 filled slots and over its new rows, which `append` has already written (ops.attention_extend_paged)."""
+        return ops.attention_extend_paged(q, self.k[li], self.v[li], table, len0, H, Tn, max_len0, scale, ws=ws, out=out)
+
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for layers in (self.k, self.v) for t in layers)
+
+    def extend_workspace(self, n: int, Tn: int, H: int, max_len0: int) -> torch.Tensor:
+        """The paged extend attention's fp32 partials for n sequences of Tn new rows behind at most max_len0 slots, sized by the library's rule."""
+        need = ops.attention_extend_paged_workspace(n, Tn, H, self.Dh, max_len0, self.Hkv, self.dtype)
+        if self._ws_extend is None or self._ws_extend.numel() < need:
+            self._ws_extend = torch.empty(max(need, 1), dtype=torch.float32, device=self.lens.device)
+        return self._ws_extend
 
     def workspace(self, H: int) -> torch.Tensor:
         """The decode attention's fp32 partials, sized once for the longest sequence a table row can describe."""
@@ -934,6 +996,19 @@ class _Running:
     tokens: List[int]
 
 
+@dataclass(eq=False)
+class PrefixHandle:
+    """What `ContinuousBatcher.register_prefix` returns: a prompt prefix of P rows whose Ps = 128 * (P // 128) leading slots live once in `pages`
+    (the batcher holds one reference to each until `drop_prefix`), and the embeddings of its tail rows [Ps, P), which every request recomputes
+    with its remainder."""
+    owner: object
+    P: int
+    Ps: int
+    pages: List[int]
+    tail: torch.Tensor
+    dropped: bool = False
+
+
 class ContinuousBatcher:
     """Greedy decoding of many requests of different lengths on `rows` rows of one PagedKVCache: a request joins the running batch as soon as a row is
     idle and the pool can reserve the pages for ALL of its prompt + max_new_tokens slots, and leaves - its pages back in the pool - the step it emits
@@ -951,6 +1026,15 @@ class ContinuousBatcher:
     (requests that joined while others were running), page_waits (steps in which a row was idle but the head of the queue had to wait for pages),
     pages_reused (pages handed to a request after another one released them).
 
+    Prompt prefixes are shared in whole pages: `register_prefix(prefix)` prefills the Ps = 128 * (P // 128) leading rows of a P-row prefix once, into
+    pages of their own, and returns a handle; `submit(remainder, n, prefix=handle)` queues the request prefix ++ remainder, whose first table entries
+    point at those pages (counted by reference: `PagedKVCache.assign(shared=)`) and whose admission runs only the P - Ps tail rows and the remainder
+    through the stack - one `LlamaModel.extend_paged` behind Ps filled slots.  Its tokens are those of
+    `lm.generate(inputs_embeds=full[None], max_new_tokens=n, prefill_chunk=Ps)` for that request alone (the same prefill and, while P - Ps + S <= Ps,
+    one dense extend).  `drop_prefix(handle)` gives the batcher's references back; running requests keep their own, so the pages return to the pool
+    when the last of them leaves.  `prefix_stats`: registered, hits (admissions behind a prefix), slots_shared (prompt rows that were not recomputed,
+    summed over hits).
+
     Greedy over the native element type only; refused by name (NotImplementedError): sampler=, beams=, draft=, processors=, prefill_chunk= and a
     quantised kv_cache=."""
 
@@ -959,9 +1043,9 @@ class ContinuousBatcher:
         who = "ContinuousBatcher"
         for name, given, why in (("sampler=", sampler is not None, "the batcher selects by argmax"),
                                  ("beams=", beams is not None, "a beam's pages would have to be shared between rows"),
-                                 ("draft=", draft is not None, "a verify pass needs a paged extend attention"),
+                                 ("draft=", draft is not None, "a verify pass over pages is not wired to LlamaModel.extend_paged yet"),
                                  ("processors=", processors is not None, "the rows' histories are not kept"),
-                                 ("prefill_chunk=", prefill_chunk is not None, "a window needs a paged extend attention")):
+                                 ("prefill_chunk=", prefill_chunk is not None, "a window over pages is not wired to LlamaModel.extend_paged yet")):
             if given:
                 raise NotImplementedError(f"{who}: {name} is not implemented over the paged cache ({why}); use SetokimLlamaPrefill.generate")
         if kv_cache != "native":
@@ -981,23 +1065,22 @@ class ContinuousBatcher:
         self.cache = PagedKVCache.for_model(lm.model, rows, num_pages, max_pages_per_seq, self.device)
         self.eos_ids = None if eos_token_id is None else [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
         self.pad_token_id = pad_token_id                                           # (kept for HF's signature: a finished request leaves, nothing is padded)
-        self.queue: List[Tuple[int, torch.Tensor, int]] = []                       # (ticket, prompt, max_new) in submit order
+        self.queue: List[Tuple[int, torch.Tensor, int, Optional[PrefixHandle]]] = []      # (ticket, prompt, max_new, prefix) in submit order
         self.running: List[Optional[_Running]] = [None] * rows
         self.cur = torch.zeros(rows, dtype=torch.int64, device=self.device)        # every row's latest token: the next decode step's input
         self._tickets = 0
         self._released: set = set()                                                # pages that went back to the pool at least once
         self.stats = dict(steps=0, row_steps_active=0, row_steps_total=0, pages_high_water=0, admitted=0, admitted_midflight=0, page_waits=0,
                           pages_reused=0)
+        self.prefix_stats = dict(registered=0, hits=0, slots_shared=0)
+        self._prefixes: List[PrefixHandle] = []                                    # the registered prefixes that have not been dropped
 
     @property
     def occupancy(self) -> float:
         return self.stats["row_steps_active"] / max(self.stats["row_steps_total"], 1)
 
-    def submit(self, inputs_embeds=None, max_new_tokens: int = 1, input_ids=None) -> int:
-        """Queue one request: its spliced prompt embeddings (T, D), or its token ids (T,) (as `input_ids=`, or an integer tensor in the first place).
-        Returns the ticket.  ValueError - the queue and the cache untouched - if T + max_new_tokens slots cannot fit in max_pages_per_seq pages, or
-        could never fit in the pool."""
-        who = "ContinuousBatcher.submit"
+    def _prompt_of(self, who: str, inputs_embeds, input_ids) -> torch.Tensor:
+        """The one prompt tensor of a call that takes embeddings (T, D) or token ids (T,), checked."""
         if (inputs_embeds is None) == (input_ids is None):
             raise ValueError(f"{who}: pass the prompt as inputs_embeds (T, D) or as input_ids (T,), one of them")
         prompt = inputs_embeds if input_ids is None else input_ids
@@ -1009,16 +1092,109 @@ class ContinuousBatcher:
                 raise ValueError(f"{who}: inputs_embeds {tuple(prompt.shape)} is not (T, D = {D})")
         elif prompt.dim() != 1 or prompt.dtype == torch.bool:
             raise ValueError(f"{who}: input_ids {tuple(prompt.shape)} {prompt.dtype} is not an integer (T,)")
+        return prompt
+
+    def _embeds(self, prompt: torch.Tensor) -> torch.Tensor:
+        """A checked prompt as embeddings (T, D) on the device."""
+        return prompt.to(self.device) if prompt.is_floating_point() else self._embed_ids(prompt)
+
+    def _own(self, who: str, prefix) -> "PrefixHandle":
+        if not isinstance(prefix, PrefixHandle) or prefix.owner is not self or prefix.dropped:
+            raise ValueError(f"{who}: prefix= is not a live handle of this batcher's register_prefix (a dropped or a foreign one)")
+        return prefix
+
+    def register_prefix(self, inputs_embeds=None, input_ids=None) -> PrefixHandle:
+        """Prefill the Ps = 128 * (P // 128) leading rows of a prompt prefix - (P, D) embeddings or (P,) ids - once, into Ps / 128 pages that requests
+        then share (`submit(prefix=)`): `assign` on an idle row, `LlamaModel.prefill_paged` of prefix[:Ps] - so the pages hold the dense prefill's
+        bits -, `detach`.  The handle keeps the pages and the embeddings of the tail rows [Ps, P).  ValueError for P < 128 (nothing to share) or a
+        prefix that leaves a table row no entry of its own; RuntimeError, with nothing changed, without an idle row or Ps / 128 free pages now, and
+        if holding these pages too would leave a queued request fewer pages than it needs of its own even in an empty batcher (a held prefix's pages
+        leave the pool until `drop_prefix`, and a request that can never be admitted would block the queue for good).  If the prefill itself raises,
+        the row is released first: it is idle again and its pages are free."""
+        who = "ContinuousBatcher.register_prefix"
+        prompt = self._prompt_of(who, inputs_embeds, input_ids)
+        P = prompt.shape[0]
+        Ps = ops.KV_PAGE * (P // ops.KV_PAGE)
+        if Ps == 0:
+            raise ValueError(f"{who}: a prefix of {P} rows fills no whole page of {ops.KV_PAGE} slots: there is nothing to share")
+        n = Ps // ops.KV_PAGE
+        if n >= self.cache.max_pages_per_seq:
+            raise ValueError(f"{who}: the prefix's {n} shared pages leave a request none of its max_pages_per_seq = {self.cache.max_pages_per_seq}")
+        idle = [r for r in range(self.rows) if self.running[r] is None]
+        if not idle:
+            raise RuntimeError(f"{who}: no idle row to prefill the prefix on (all {self.rows} rows run a request)")
+        if n > self.cache.pages_free:
+            raise RuntimeError(f"{who}: the prefix needs {n} free pages, the pool has {self.cache.pages_free} of {self.cache.num_pages}")
+        room = self.cache.num_pages - self._pinned() - n                           # what an empty batcher could still hand out with this prefix held too
+        for ticket, queued, max_new, pre in self.queue:
+            own = self._own_pages(queued.shape[0], max_new, pre)
+            if own > room:
+                raise RuntimeError(f"{who}: holding {n} more pages would leave the pool {room} pages for requests, and the queued request {ticket} "
+                                   f"needs {own} of its own: it could never be admitted (register the prefix once it has been admitted, or drop another)")
+        row, x = idle[0], self._embeds(prompt)
+        self.cache.assign(row, Ps)
+        try:
+            self.lm.model.prefill_paged(x[None, :Ps], self.cache, row)
+        except BaseException:
+            self.cache.release(row)                                                # the row is idle again and the pages are back: nothing changed
+            raise
+        self.stats["pages_high_water"] = max(self.stats["pages_high_water"], self.cache.num_pages - self.cache.pages_free)
+        handle = PrefixHandle(self, P, Ps, self.cache.detach(row), x[Ps:].to(self.w_e.dtype).clone())
+        self._prefixes.append(handle)
+        self.prefix_stats["registered"] += 1
+        return handle
+
+    def _pinned(self) -> int:
+        """Pages the registered prefixes hold: the part of the pool no request can have as its own until a `drop_prefix`."""
+        return sum(len(h.pages) for h in self._prefixes)
+
+    @staticmethod
+    def _own_pages(T: int, max_new: int, prefix: Optional[PrefixHandle]) -> int:
+        """Pages a request must take off the free list: all of its prompt's + max_new slots' pages but the shared ones."""
+        P, shared = (0, 0) if prefix is None else (prefix.P, len(prefix.pages))
+        return (P + T + max_new + ops.KV_PAGE - 1) // ops.KV_PAGE - shared
+
+    def drop_prefix(self, handle: PrefixHandle) -> None:
+        """Give the batcher's references to the prefix's pages back.  Running requests keep their own: the pages return to the pool when the last of
+        them leaves.  ValueError for a dropped or foreign handle, and while a queued request names it."""
+        who = "ContinuousBatcher.drop_prefix"
+        self._own(who, handle)
+        if any(entry[3] is handle for entry in self.queue):
+            raise ValueError(f"{who}: a queued request names this prefix (drop it once the request has been admitted)")
+        self._released.update(p for p in handle.pages if self.cache.page_refs[p] == 1)
+        self.cache.drop(handle.pages)
+        handle.dropped = True
+        self._prefixes.remove(handle)
+
+    def submit(self, inputs_embeds=None, max_new_tokens: int = 1, input_ids=None, prefix: Optional[PrefixHandle] = None) -> int:
+        """Queue one request: its spliced prompt embeddings (T, D), or its token ids (T,) (as `input_ids=`, or an integer tensor in the first place).
+        With `prefix=` (a handle of `register_prefix`) the prompt argument is the remainder behind the prefix, S >= 1 rows, and the request's prompt
+        is prefix ++ remainder.  Returns the ticket.  ValueError - the queue and the cache untouched - if the prompt's + max_new_tokens slots cannot
+        fit in max_pages_per_seq pages, or could never fit in the pool - the pool less the pages the registered prefixes hold, which no request can
+        have as its own until a `drop_prefix` -, and for a dropped or foreign handle."""
+        who = "ContinuousBatcher.submit"
+        prompt = self._prompt_of(who, inputs_embeds, input_ids)
         _count(max_new_tokens, "max_new_tokens", who)
         T = prompt.shape[0]
         if T < 1:
             raise ValueError(f"{who}: an empty prompt")
-        pages = (T + max_new_tokens + ops.KV_PAGE - 1) // ops.KV_PAGE
-        if pages > self.cache.max_pages_per_seq or pages > self.cache.num_pages:
-            raise ValueError(f"{who}: {T} + {max_new_tokens} slots need {pages} pages; a sequence has at most max_pages_per_seq = "
-                             f"{self.cache.max_pages_per_seq} and the pool num_pages = {self.cache.num_pages}")
+        if prefix is not None:
+            self._own(who, prefix)
+        pinned = self._pinned()
+        own = self._own_pages(T, max_new_tokens, prefix)
+        held = f", of which registered prefixes hold {pinned}" if pinned else ""
+        if prefix is None:
+            if own > self.cache.max_pages_per_seq or own > self.cache.num_pages - pinned:
+                raise ValueError(f"{who}: {T} + {max_new_tokens} slots need {own} pages; a sequence has at most max_pages_per_seq = "
+                                 f"{self.cache.max_pages_per_seq} and the pool num_pages = {self.cache.num_pages}{held}")
+        else:
+            pages = own + len(prefix.pages)
+            if pages > self.cache.max_pages_per_seq or own > self.cache.num_pages - pinned:
+                raise ValueError(f"{who}: {prefix.P} + {T} + {max_new_tokens} slots need {pages} pages, {own} of them the "
+                                 f"request's own behind the prefix's {len(prefix.pages)} shared ones; a sequence has at most max_pages_per_seq = "
+                                 f"{self.cache.max_pages_per_seq} and the pool num_pages = {self.cache.num_pages}{held}")
         ticket, self._tickets = self._tickets, self._tickets + 1
-        self.queue.append((ticket, prompt, max_new_tokens))
+        self.queue.append((ticket, prompt, max_new_tokens, prefix))
         return ticket
 
     def _tokens_of(self, h: torch.Tensor) -> torch.Tensor:
@@ -1036,17 +1212,28 @@ class ContinuousBatcher:
             idle = [r for r in range(self.rows) if self.running[r] is None]
             if not idle:
                 break
-            ticket, prompt, max_new = self.queue[0]
+            ticket, prompt, max_new, prefix = self.queue[0]
             row, T = idle[0], prompt.shape[0]
-            if not cache.assign(row, T + max_new):
-                st["page_waits"] += 1                                              # a row is idle, the pages are not there yet: nothing overtakes
+            shared = [] if prefix is None else prefix.pages
+            if not cache.assign(row, (0 if prefix is None else prefix.P) + T + max_new, shared=shared):
+                if all(r is None for r in self.running):                           # nobody will ever release a page: refuse by name, never spin
+                    raise RuntimeError(f"ContinuousBatcher.step: request {ticket} at the head of the queue needs "
+                                       f"{self._own_pages(T, max_new, prefix)} pages of its own and no request is running, but only {cache.pages_free} "
+                                       f"of {cache.num_pages} pages are free ({self._pinned()} are held by registered prefixes): drop a prefix")
+                st["page_waits"] += 1                                             # a row is idle, the pages are not there yet: nothing overtakes
                 break
             self.queue.pop(0)
             st["admitted"] += 1
             st["admitted_midflight"] += int(any(self.running[r] is not None and r not in fresh for r in range(self.rows)))
-            st["pages_reused"] += sum(p in self._released for p in cache.pages_of(row))
-            x = prompt.to(self.device) if prompt.is_floating_point() else self._embed_ids(prompt)
-            h = self.lm.model.prefill_paged(x[None], cache, row)
+            st["pages_reused"] += sum(p in self._released for p in cache.pages_of(row)[len(shared):])
+            x = self._embeds(prompt)
+            if prefix is None:
+                h = self.lm.model.prefill_paged(x[None], cache, row)
+            else:                                                                  # the shared slots are filled: only the prefix's tail and the remainder run
+                cache.set_len(row, prefix.Ps)
+                h = self.lm.model.extend_paged(torch.cat([prefix.tail, x.to(prefix.tail.dtype)])[None], cache, [row])
+                self.prefix_stats["hits"] += 1
+                self.prefix_stats["slots_shared"] += prefix.Ps
             self.cur[row:row + 1] = self._tokens_of(h[:, -1].contiguous())
             self.running[row] = _Running(ticket, max_new, [])
             fresh.append(row)
@@ -1079,7 +1266,7 @@ class ContinuousBatcher:
             for t in new:
                 run.tokens.append(int(t))
                 if len(run.tokens) == run.max_new or (self.eos_ids is not None and int(t) in self.eos_ids):
-                    self._released.update(self.cache.pages_of(row))
+                    self._released.update(p for p in self.cache.pages_of(row) if self.cache.page_refs[p] == 1)      # those that go back to the pool
                     self.cache.release(row)
                     self.running[row] = None
                     done.append((run.ticket, torch.tensor(run.tokens, dtype=torch.int64, device=self.device)))
@@ -1087,8 +1274,9 @@ class ContinuousBatcher:
         return done
 
     def run(self, requests) -> List[torch.Tensor]:
-        """Submit every (prompt, max_new_tokens) pair, step until the queue and the rows are empty; the token tensors in submit order."""
-        tickets = [self.submit(p, n) for p, n in requests]
+        """Submit every (prompt, max_new_tokens) pair - or (remainder, max_new_tokens, prefix handle) triple -, step until the queue and the rows
+        are empty; the token tensors in submit order."""
+        tickets = [self.submit(r[0], r[1], prefix=r[2] if len(r) > 2 else None) for r in requests]
         out = {}
         while self.queue or any(r is not None for r in self.running):
             out.update(self.step())

@@ -534,6 +534,46 @@ class LlamaModel(PackCacheMixin, nn.Module):
         cache.lens_host = new_host
         return ops.rmsnorm(x, pk["norm"], self.eps, out=y)
 
+    @torch.no_grad()
+    def extend_paged(self, inputs_embeds, cache, rows):
+        """Tn >= 1 tokens for each of the n distinct rows `rows` of a generation.PagedKVCache: inputs_embeds (n, Tn, D) -> the final-norm hidden
+        states (n, Tn, D).  The dense `extend` over pages: row r's token i is rotated to position lens[r] + i (compact: position == slot), appended
+        at that slot through the table and attends over the row's older slots plus the new ones (csrc/attn_extend_paged.hip, at len0 = lens[rows]
+        over the gathered table rows); afterwards lens[r] += Tn on the device and the host.  With native weights a row's states are the dense
+        `extend`'s for that row alone, bit for bit.  The rows not listed are not touched.  Each listed row must own pages for lens_host[row] + Tn
+        slots (ValueError otherwise, with nothing launched); what it attends over may lie in pages it shares - only its own new slots are written."""
+        who = "LlamaModel.extend_paged"
+        self._check_paged(who, cache)
+        n, Tn, D = inputs_embeds.shape
+        rows = [int(r) for r in rows]
+        if n < 1 or Tn < 1 or len(rows) != n or len(set(rows)) != n or any(not 0 <= r < cache.rows for r in rows):
+            raise ValueError(f"{who}: inputs_embeds {tuple(inputs_embeds.shape)} needs n >= 1 distinct rows of the cache's {cache.rows} and Tn >= 1, got rows={rows}")
+        for r in rows:
+            room = len(cache.pages_of(r)) * ops.KV_PAGE
+            if cache.lens_host[r] + Tn > room:
+                raise ValueError(f"{who}: row {r} holds {cache.lens_host[r]} slots and owns pages for {room}: no room for {Tn} more")
+        pk = self._pack()
+        H, dh = self.num_heads, self.head_dim
+        dev = cache.lens.device
+        x = inputs_embeds.to(self.norm.weight.dtype).reshape(n * Tn, D).contiguous().clone()
+        idx = torch.tensor(rows, dtype=torch.int64, device=dev)
+        len0 = cache.lens.index_select(0, idx).contiguous()
+        table = cache.block_table.index_select(0, idx).contiguous()
+        pos = (len0.to(torch.int64)[:, None] + torch.arange(Tn, device=dev)[None]).reshape(n * Tn).contiguous()
+        max_len0 = max(cache.lens_host[r] for r in rows)
+        ws, scale, o = cache.extend_workspace(n, Tn, H, max_len0), dh ** -0.5, None
+
+        def attend(li, qkv):
+            nonlocal o
+            ops.kv_append_paged(qkv, cache.k[li], cache.v[li], table, len0, Tn, H)
+            o = cache.extend_attend(li, qkv, H, Tn, max_len0, scale, ws, o, table, len0)
+            return o
+        y = self._run_layers(x, pk["layers"], pos, attend)
+        cache.lens[idx] = len0 + Tn
+        for r in rows:
+            cache.lens_host[r] += Tn
+        return ops.rmsnorm(x, pk["norm"], self.eps, out=y).reshape(n, Tn, D)
+
 
 def _refuse_unsupported_llama_fields(g) -> None:
     """The prefill reads hidden / intermediate sizes, layer and head counts, `num_key_value_heads`, `rms_norm_eps` and `rope_theta` — plain

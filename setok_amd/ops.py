@@ -908,6 +908,38 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, key_mask: Tens
     return out
 
 
+# ---- extending sequences of the paged cache (csrc/attn_extend_paged.hip) ------------------------------------------------------------------------
+def attention_extend_paged_workspace(B: int, Tn: int, H: int, Dh: int, max_len0: int, Hkv: Optional[int] = None,
+                                     dtype: torch.dtype = torch.float32) -> int:
+    """Floats of workspace setok_attention_extend_gqa_paged needs for Tn new rows per sequence behind at most max_len0 filled slots, as the library
+    states it (setok_attention_extend_paged_workspace: attention_extend_workspace's rule at len0 = max_len0)."""
+    code = _code(dtype)
+    return int(_lib.load(_lib.is_half(code)).setok_attention_extend_paged_workspace(code, B, Tn, H, H if Hkv is None else Hkv, Dh, max_len0))
+
+
+def attention_extend_paged(q: Tensor, k_pool: Tensor, v_pool: Tensor, block_table: Tensor, len0: Tensor, H: int, Tn: int, max_len0: int, scale: float,
+                           ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Tn query rows per (sequence, query head) against the sequence's slots in the pools, which already hold the new rows' keys / values in slots
+    [len0[b], len0[b] + Tn) (kv_append_paged with slot0 = len0): query i of sequence b counts slot j iff j <= len0[b] + i and
+    block_table[b][j // KV_PAGE] is a page.  q: (B * Tn, >= H*Dh) rows of stride q.stride(0); len0 (B,) int32 on the device, < 0 for an idle
+    sequence (zeros), `max_len0` the host's upper bound on it.  Returns (B * Tn, H*Dh); a sequence's bits are attention_extend's at B = 1 on its
+    gathered slots."""
+    num_pages, Hkv, Dh, B, max_pages = _paged_shapes(k_pool, v_pool, block_table, len0)
+    assert Tn >= 1 and 0 <= max_len0 and max_len0 + Tn <= max_pages * KV_PAGE, \
+        f"attention_extend_paged: slots [{max_len0}, {max_len0} + {Tn}) lie beyond the table ({max_pages} pages)"
+    assert q.dtype == k_pool.dtype and q.shape[0] == B * Tn and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    need = attention_extend_paged_workspace(B, Tn, H, Dh, max_len0, Hkv, q.dtype)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B * Tn, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B * Tn, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_extend_gqa_paged", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_pool), _p(v_pool), _p(block_table),
+              max_pages, num_pages, _p(len0), _p(out), B, Tn, H, Hkv, Dh, max_len0, scale, _p(ws), ws.numel())
+    return out
+
+
 # ---- the MXFP4 KV cache (csrc/attn_decode.hip, csrc/attn_extend.hip; include/setok_hip.h, "MXFP4 KV cache") --------------------------------------
 DECODE_CHUNK_MXFP4KV = 256                        # SETOK_DECODE_CHUNK_MXFP4KV of include/setok_hip.h
 

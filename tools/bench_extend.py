@@ -10,6 +10,8 @@ library had to do the same work before, both arms alternated round by round in O
 
     python tools/bench_extend.py [--layers 32] [--rounds 5] [--reps 10] [--out profiles/extend_bench.json]
     python tools/bench_extend.py --only attention          # one section
+    python tools/bench_extend.py --only paged_pair         # the paged extend attention's launch pair against the dense pair at the same rows
+                                                           # (B = 1, 88 rows behind 512 slots; B = 8, 8 rows behind 2048) -> a section of profiles/prefix_bench.json
     python tools/bench_extend.py --trace-arm unchunked      # two calls of one arm of the chunked section and nothing else (what a kernel trace is pointed at)
 
 After a warm-up of both arms every arm runs `--rounds` times, `--reps` calls per run between two device events; median, min, max and every run are
@@ -136,13 +138,72 @@ def attention(llm, a, g, rnd):
     return out
 
 
+def paged_pair(llm, a, g, rnd):
+    """The paged extend attention's launch pair (csrc/attn_extend_paged.hip) against the dense pair at the same rows, over every layer's cache: the
+    dense caches' slots copied into pools at a shuffled block table.  An admission behind a shared prefix (B = 1, 88 rows behind 512 slots) and a
+    verify-shaped call (B = 8, 8 rows behind 2048).  The ratio of the medians against each arm's spread (max - min over the rounds)."""
+    from setok_amd import ops
+    out = {}
+    for B, Tn, len0 in ((1, 88, 512), (8, 8, 2048)):
+        c = _filled_cache(llm, B, len0 + Tn, len0 + Tn, g)
+        per = (len0 + Tn + ops.KV_PAGE - 1) // ops.KV_PAGE
+        n_pages = B * per
+        perm = torch.randperm(n_pages, generator=torch.Generator().manual_seed(len0)).to(torch.int32).reshape(B, per)
+        q_dev = c.key_mask.device
+        table, idx = perm.to(q_dev), perm.reshape(-1).long().to(q_dev)
+        pools = []
+        for k, v in zip(c.k, c.v):
+            pair = []
+            for src in (k, v):
+                padded = torch.zeros(B, c.Hkv, per * ops.KV_PAGE, DH, dtype=src.dtype, device=q_dev)
+                padded[:, :, :len0 + Tn] = src
+                pool = torch.empty(n_pages, c.Hkv, ops.KV_PAGE, DH, dtype=src.dtype, device=q_dev)
+                pool[idx] = padded.reshape(B, c.Hkv, per, ops.KV_PAGE, DH).transpose(1, 2).reshape(n_pages, c.Hkv, ops.KV_PAGE, DH)
+                pair.append(pool)
+            pools.append(tuple(pair))
+        q = rnd(B * Tn, 3 * D)
+        lens = torch.full((B,), len0, dtype=torch.int32, device=q_dev)
+        ws = c.workspace(H, Tn, len0)
+        o = torch.empty(B * Tn, H * DH, dtype=q.dtype, device=q.device)
+        dense = lambda: [ops.attention_extend(q, k, v, c.key_mask, H, Tn, len0, DH ** -0.5, ws=ws, out=o) for k, v in zip(c.k, c.v)]
+        paged = lambda: [ops.attention_extend_paged(q, kp, vp, table, lens, H, Tn, len0, DH ** -0.5, ws=ws, out=o) for kp, vp in pools]
+        same = torch.equal(ops.attention_extend(q, c.k[0], c.v[0], c.key_mask, H, Tn, len0, DH ** -0.5),
+                           ops.attention_extend_paged(q, pools[0][0], pools[0][1], table, lens, H, Tn, len0, DH ** -0.5))
+        r = _arms({"dense_pair": dense, "paged_pair": paged}, a.rounds, a.reps)
+        d, p = r["dense_pair"], r["paged_pair"]
+        r["paged_over_dense"] = round(p["median"] / d["median"], 4)
+        r["difference_ms"] = round(p["median"] - d["median"], 4)
+        r["largest_spread_ms"] = round(max(d["max"] - d["min"], p["max"] - p["min"]), 4)
+        r["paged_slower_beyond_spread"] = bool(p["median"] - d["median"] > r["largest_spread_ms"])
+        r["bit_identical_outputs"] = bool(same)
+        out[f"B{B}_Tn{Tn}_len0_{len0}"] = r
+        del c, pools
+        torch.cuda.empty_cache()
+    return dict(shape=dict(H=H, Hkv=H, Dh=DH, layers=a.layers, dtype="bf16"), launches_of_the_pair=2, ms=out)
+
+
+def _merge_into(path, key, value):
+    """One section of a JSON file that several tools write: the file's other keys are kept."""
+    run = {}
+    if os.path.isfile(path):
+        with open(path) as f:
+            run = json.load(f)
+    run[key] = value
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(run, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--chunked-batch", type=int, default=4)
-    ap.add_argument("--only", choices=("verify", "second_turn", "chunked", "attention"), default=None)
+    ap.add_argument("--only", choices=("verify", "second_turn", "chunked", "attention", "paged_pair"), default=None)
+    ap.add_argument("--prefix-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "prefix_bench.json"),
+                    help="where --only paged_pair records its section (a file it shares with tools/bench_paged.py --prefix)")
     ap.add_argument("--trace-arm", choices=("prefill_chunk_512", "unchunked"), default=None)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "extend_bench.json"))
     a = ap.parse_args()
@@ -158,6 +219,11 @@ def main():
             llm.generate(inputs_embeds=x, max_new_tokens=1, prefill_chunk=512 if a.trace_arm == "prefill_chunk_512" else None)
         torch.cuda.synchronize()
         print(json.dumps(dict(arm=a.trace_arm, calls=2, B=a.chunked_batch, T=2048, layers=a.layers)))
+        return
+    if a.only == "paged_pair":                                            # its own file: not a section of extend_bench.json
+        res = dict(device=torch.cuda.get_device_name(0), rounds=a.rounds, reps=a.reps, **paged_pair(llm, a, g, rnd))
+        _merge_into(a.prefix_out, "paged_against_dense_launch_pair", res)
+        print(json.dumps(res))
         return
     sections = dict(verify=verify, second_turn=second_turn, chunked=chunked, attention=attention)
     res = {k: fn(llm, a, g, rnd) for k, fn in sections.items() if a.only in (None, k)}
