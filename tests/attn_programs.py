@@ -40,8 +40,8 @@ def offsets(T: int, program: str, tile: int = 32) -> torch.Tensor:
     j = torch.arange(T)
     if program in STAIRS:
         return STAIRS[program] * (j // tile).float()
-    if program == "shift-60":
-        return torch.full((T,), -60.0)
+    if program in ("shift-60", "shift-64"):        # -64 is the level an MXFP4 block carries exactly (-60 comes back as -48)
+        return torch.full((T,), float(program[5:]))
     if program.startswith("hot@"):
         g = torch.zeros(T)
         p = hot_key(program, T, tile)
