@@ -928,8 +928,8 @@ int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const void* q, i
  * is the page that holds its slots [SETOK_KV_PAGE * p, SETOK_KV_PAGE * (p + 1)) - and an int32 length on the device: sequences of one batch
  * have lengths of their own, a compact sequence has no dead slots (there is no key_mask), and pages go back to a pool when a sequence ends.
  * A page id outside [0, num_pages) means "no page" to both entries: nothing is written to it, no key of it counts, and no address is formed from
- * it - a bad table is defined behaviour, never a fault.  Greedy decoding over the element type only: quantised pools are a follow-up
- * (DESIGN.md §7 f17); the extend attention over pages is the next section.  Pure additions: the ABI version stays 9. */
+ * it - a bad table is defined behaviour, never a fault.  These two entries take pools in the element type; MXFP4 pools have entries of their own
+ * ("Paged MXFP4 KV cache" below); the extend attention over pages is the next section.  Pure additions: the ABI version stays 9. */
 
 /* Slots per page.  Equal to SETOK_DECODE_CHUNK (a static_assert in csrc/attn_paged.hip): a chunk's workgroup reads exactly one page, so where a
  * page lies cannot change a bit of the output. */
@@ -982,6 +982,54 @@ int64_t setok_attention_extend_paged_workspace(int dtype, int B, int Tn, int H, 
 int setok_attention_extend_gqa_paged(void* stream, int dtype, const void* q, int64_t ldq, const void* k_pool, const void* v_pool,
                                      const int32_t* block_table, int max_pages, int num_pages, const int32_t* len0, void* out, int B, int Tn, int H,
                                      int Hkv, int Dh, int max_len0, float scale, float* ws, int64_t ws_floats);
+
+/* ---- Paged MXFP4 KV cache (csrc/attn_paged.hip, csrc/attn_extend_paged.hip): the pools of "Paged KV cache" stored by the rule of "MXFP4 KV
+ * cache" - the smallest rows in pages that go back to a pool.  One layer's pools are
+ *     k_q, v_q (num_pages, Hkv, SETOK_KV_PAGE, Dh/2) uint8     e2m1 nibbles, element 2j of a row in the low nibble of byte j
+ *     k_s, v_s (num_pages, Hkv, SETOK_KV_PAGE, Dh/32) uint8    e8m0 scale bytes, one per 32 elements of a row
+ * and a row means what a row of the dense MXFP4 cache means.  block_table, lens / len0, slot0, max_pages, num_pages and max_len / max_len0 are
+ * those of the native paged entries; a table entry outside [0, num_pages) is "no page" and never becomes an address.  The pools take
+ * 2 * layers * num_pages * Hkv * SETOK_KV_PAGE * (Dh/2 + Dh/32) bytes: 68 per slot at Dh = 128 against 256 in 16 bits.  The kernels are the
+ * dense MXFP4 kernels' arithmetic on the same partition of the keys, so a sequence's bits are the dense MXFP4 entries' on its gathered slots
+ * (DESIGN.md §7 f19).  e4m3 pools are not built: that format has no extend attention.  Pure additions: the ABI version stays 9. */
+
+/* setok_kv_append_mxfp4's quantiser with setok_kv_append_paged's destination: row b * T + t of the fused buffer goes, quantised block by block,
+ * to page block_table[b][slot / SETOK_KV_PAGE], row slot % SETOK_KV_PAGE, slot = slot0[b] + t.  Nothing is written for a sequence with
+ * slot0[b] < 0, for a slot past the table's max_pages entries or for a table entry that is no page (such a row's lanes load and store nothing but
+ * still take part in the quantiser's lane exchanges); no other byte of the four pools is written.  The bytes written are exactly those
+ * setok_kv_append_mxfp4 writes for the same source row, a block with a non-finite entry (scale byte 0xFF, nibbles 0) included.
+ * Dh in {32, 64, 128}, as for the decode attention below; qkv, k_q and v_q 16-byte aligned. */
+int setok_kv_append_paged_mxfp4(void* stream, int dtype, const void* qkv, uint8_t* k_q, uint8_t* k_s, uint8_t* v_q, uint8_t* v_s,
+                                const int32_t* block_table, int max_pages, int num_pages, const int32_t* slot0, int B, int T, int H, int Hkv, int Dh);
+
+/* setok_attention_decode_gqa_paged over MXFP4 pools: the same kernel over the nibble format.  A chunk is SETOK_DECODE_CHUNK_MXFP4KV = 256 slots,
+ * TWO pages: a wave's slice is 64 slots and never straddles a page, waves 0-1 of chunk c read table entry 2c and waves 2-3 entry 2c + 1.  A wave
+ * whose slice starts at or past lens[b] reads no table entry and loads nothing, and neither does one whose entry lies at or past max_pages (entry
+ * 2c + 1 at an odd max_pages) or is no page: each writes the empty partial.  The grid's chunk dimension and the workspace come from
+ * ceil(max_len / 256): ws_floats >= B * H * ceil(max_len / SETOK_DECODE_CHUNK_MXFP4KV) * (Dh + 2); the merge takes each sequence's chunk count
+ * from lens[b].  Sequence b's output bits are those of setok_attention_decode_gqa_mxfp4kv at B = 1 on its slots gathered into a dense MXFP4 cache
+ * with an all-ones mask and len = lens[b] (a missing page: a mask that is zero on its 128 slots).  Dh in {32, 64, 128}, the head dims with a lane
+ * layout over nibble rows (16 elements per lane); any other is refused - the dense entry serves them with the generic kernel, which has no paged
+ * twin, and a lane layout of its own for 256 or 512 would not give the dense call's bits.  q, k_q and v_q 16-byte aligned, ldq % 8 == 0. */
+int setok_attention_decode_gqa_paged_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                             const uint8_t* v_q, const uint8_t* v_s, const int32_t* block_table, int max_pages, int num_pages,
+                                             const int32_t* lens, void* out, int B, int H, int Hkv, int Dh, int max_len, float scale, float* ws,
+                                             int64_t ws_floats);
+
+/* Floats of workspace setok_attention_extend_gqa_paged_mxfp4kv needs: setok_attention_extend_mxfp4kv_workspace's rule at len0 = max_len0,
+ * B * Tn * H * ceil((max_len0 + Tn) / SETOK_EXTEND_CHUNK) * (Dh + 2). */
+int64_t setok_attention_extend_paged_mxfp4kv_workspace(int B, int Tn, int H, int Dh, int max_len0);
+
+/* setok_attention_extend_gqa_paged over MXFP4 pools, with that call's meaning of every argument (len0[b] per sequence, < 0 idle; "no page";
+ * only slots that count are read).  One wave per (query row, query head, chunk of SETOK_EXTEND_CHUNK = 256 slots, two pages), a key per lane with
+ * its page looked up per key, then the merge in chunk order, for every Dh % 32 == 0 and element type: this is the FUNCTIONAL path, as
+ * setok_attention_extend_gqa_mxfp4kv is - an MFMA extend over nibble rows is not built, dense or paged.  Sequence b's output bits are those of
+ * setok_attention_extend_gqa_mxfp4kv at B = 1, len0 = len0[b], on its gathered slots under an all-ones mask.  q, k_q and v_q 16-byte aligned,
+ * ldq % 8 == 0, ws_floats >= setok_attention_extend_paged_mxfp4kv_workspace(...).  B == 0 launches nothing. */
+int setok_attention_extend_gqa_paged_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                             const uint8_t* v_q, const uint8_t* v_s, const int32_t* block_table, int max_pages, int num_pages,
+                                             const int32_t* len0, void* out, int B, int Tn, int H, int Hkv, int Dh, int max_len0, float scale,
+                                             float* ws, int64_t ws_floats);
 
 /* ---- The DiffLoss image head (src/model/loss/diffloss.py: SimpleMLPAdaLN driven by a respaced cosine DDPM with learned-range variance,
  * src/model/diffusion/).  Its Linears are setok_linear calls, its plain SiLUs setok_activation(SETOK_ACT_SILU); these are the rest

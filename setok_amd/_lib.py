@@ -37,7 +37,7 @@ class SetokConfig(C.Structure):
 
 RESTYPES = {"setok_last_error": C.c_char_p, "setok_ctx_error": C.c_char_p, "setok_encode_workspace_bytes": _i64, "setok_destroy": None,
             "setok_attention_extend_workspace": _i64, "setok_linear_skinny_workspace": _i64, "setok_attention_extend_mxfp4kv_workspace": _i64,
-            "setok_attention_extend_paged_workspace": _i64}
+            "setok_attention_extend_paged_workspace": _i64, "setok_attention_extend_paged_mxfp4kv_workspace": _i64}
 
 # name -> argtypes; mirrors include/setok_hip.h declaration by declaration
 SIGNATURES = {
@@ -133,6 +133,10 @@ SIGNATURES = {
     "setok_attention_decode_gqa_paged": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_attention_extend_paged_workspace": [_i, _i, _i, _i, _i, _i, _i],
     "setok_attention_extend_gqa_paged": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_kv_append_paged_mxfp4": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i],
+    "setok_attention_decode_gqa_paged_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i64],
+    "setok_attention_extend_paged_mxfp4kv_workspace": [_i, _i, _i, _i, _i],
+    "setok_attention_extend_gqa_paged_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_attention_extend_mxfp4kv_workspace": [_i, _i, _i, _i, _i],
     "setok_attention_extend_gqa_mxfp4kv": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_linear_skinny_workspace": [_i, _i, _i],

@@ -304,23 +304,10 @@ int check_decode(const char* name, const char* caches, bool operands, bool align
 // ==== filling the fp8 KV cache (include/setok_hip.h, "FP8 KV cache") ==============================================================================
 // A cache row is Dh e4m3fn bytes + one int8 exponent and means value(q[d]) * 2^e (fp8.h: the rule of the weight path).
 
-// Maximum over aligned groups of N lanes of non-negative values, every lane of a group ending with the same bits: row_sum's exchanges.
-template <int CTRL> __device__ inline float dpp_max(float a) {
-    return fmaxf(a, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), CTRL, 0xf, 0xf, false)));
-}
-template <int N> __device__ inline float row_max(float a) {
-    if constexpr (N >= 2) a = dpp_max<0xB1>(a);
-    if constexpr (N >= 4) a = dpp_max<0x4E>(a);
-    if constexpr (N >= 8) a = dpp_max<0x141>(a);
-    if constexpr (N >= 16) a = dpp_max<0x140>(a);
-#pragma unroll
-    for (int o = 16; o < N; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-    return a;
-}
-
 // ---- kv_append with the quantiser: one pass, a row in the registers of GL lanes (8 elements each; GL = the power of two >= Dh / 8) -------------
 // Rows are numbered ((b * T + t) * 2 + which) * Hkv + hk; a workgroup takes 256 / GL of them per trip, every wave makes the same number of trips
-// (the exchanges of row_max need the whole wave), lanes without a piece carry zeros and write nothing.
+// (the exchanges of row_max — attn_partials.h — need the whole wave), lanes without a piece carry zeros and write nothing.  The MXFP4 quantiser,
+// which the paged cache shares, is kv_append_mxfp4_kernel in attn_partials.h.
 template <typename T, int GL>
 __global__ __launch_bounds__(256) void kv_append_fp8_kernel(const T* __restrict__ qkv, uint8_t* __restrict__ kq, int8_t* __restrict__ ke,
                                                             uint8_t* __restrict__ vq, int8_t* __restrict__ ve, int B, int Tn, int H, int Hkv, int Dh,
@@ -382,71 +369,6 @@ void launch_append_fp8(hipStream_t s, const T* qkv, uint8_t* kq, int8_t* ke, uin
 #undef F8_APPEND
 }
 
-// ==== filling the MXFP4 KV cache (include/setok_hip.h, "MXFP4 KV cache") ==========================================================================
-// A cache row is Dh / 2 bytes of e2m1 nibbles + Dh / 32 e8m0 scale bytes and means value(nibble[d]) * 2^(s[d / 32] - 127) (mx4.h: the rule of
-// the weight path).  kv_append_fp8_kernel's arrangement: one pass, a row in the registers of GL lanes, 8 elements each, so a block of 32 is an
-// aligned quad of lanes and its amax two quad_perm exchanges; a lane writes its 8 nibbles as one dword, the quad's first lane the scale byte.
-// Dh % 32 == 0, so a row is a whole number of quads and a lane without a piece shares a quad with no live lane.
-template <typename T, int GL>
-__global__ __launch_bounds__(256) void kv_append_mxfp4_kernel(const T* __restrict__ qkv, uint8_t* __restrict__ kq, uint8_t* __restrict__ ks,
-                                                              uint8_t* __restrict__ vq, uint8_t* __restrict__ vs, int B, int Tn, int H, int Hkv, int Dh,
-                                                              int cap, int pos0) {
-    constexpr int RPB = 256 / GL;                                      // rows per workgroup and trip
-    const int vpr = Dh / 8, sub = threadIdx.x % GL;
-    const int64_t rows = (int64_t)B * Tn * 2 * Hkv, ld = (int64_t)(H + 2 * Hkv) * Dh;
-    for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < rows; r0 += (int64_t)gridDim.x * RPB) {
-        const int64_t row = r0 + threadIdx.x / GL;
-        const bool live = row < rows && sub < vpr;
-        float f[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = 0.f;
-        int which = 0;
-        int64_t slot = 0;
-        if (live) {
-            const int hk = (int)(row % Hkv);
-            which = (int)((row / Hkv) & 1);                            // 0 = k, 1 = v
-            const int64_t bt = row / (2 * Hkv);
-            const T* src = qkv + bt * ld + (int64_t)(H + which * Hkv + hk) * Dh + sub * 8;
-#pragma unroll
-            for (int u = 0; u < 8 / Elem<T>::VEC; ++u) ld_vec<T>(src + u * Elem<T>::VEC, f + u * Elem<T>::VEC);
-            slot = ((bt / Tn) * Hkv + hk) * cap + pos0 + bt % Tn;
-        }
-        float amax = 0.f, bad = 0.f;                                   // bad: the block holds a non-finite entry (it becomes scale byte 0xFF, nibbles 0)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float a = fabsf(f[e]);
-            if (a <= 3.402823466e38f) amax = fmaxf(amax, a);
-            else bad = 1.f;
-        }
-        amax = row_max<4>(amax);
-        bad = row_max<4>(bad);
-        const int ex = mx4_exponent(amax);
-        const float inv = mx4_inv_scale(ex);
-        if (live) {
-            unsigned w = 0u;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) w |= mx4_encode(f[e] * inv) << (4 * e);
-            *reinterpret_cast<unsigned*>((which ? vq : kq) + slot * (Dh / 2) + sub * 4) = bad != 0.f ? 0u : w;
-            if ((sub & 3) == 0) (which ? vs : ks)[slot * (Dh / 32) + (sub >> 2)] = (uint8_t)(bad != 0.f ? 0xff : 127 + ex);
-        }
-    }
-}
-
-template <typename T>
-void launch_append_mxfp4(hipStream_t s, const T* qkv, uint8_t* kq, uint8_t* ks, uint8_t* vq, uint8_t* vs, int B, int Tn, int H, int Hkv, int Dh,
-                         int cap, int pos0) {
-    const int vpr = Dh / 8;
-    const int64_t rows = (int64_t)B * Tn * 2 * Hkv;
-#define MX4_APPEND(GL)                                                                                                           \
-    if (vpr <= GL) {                                                                                                             \
-        const int64_t wgs = (rows + 256 / GL - 1) / (256 / GL);                                                                  \
-        kv_append_mxfp4_kernel<T, GL><<<(int)(wgs > 65536 ? 65536 : wgs), 256, 0, s>>>(qkv, kq, ks, vq, vs, B, Tn, H, Hkv, Dh, cap, pos0); \
-        return;                                                                                                                  \
-    }
-    MX4_APPEND(4) MX4_APPEND(8) MX4_APPEND(16) MX4_APPEND(32) MX4_APPEND(64)
-#undef MX4_APPEND
-}
-
 }  // namespace
 
 extern "C" int setok_kv_append_fp8(void* stream, int dtype, const void* qkv, uint8_t* k_q, int8_t* k_e, uint8_t* v_q, int8_t* v_e, int B, int T, int H,
@@ -489,8 +411,8 @@ extern "C" int setok_kv_append_mxfp4(void* stream, int dtype, const void* qkv, u
     SETOK_CHECK_ARG(aligned16(qkv) && aligned16(k_q) && aligned16(v_q), "setok_kv_append_mxfp4: qkv, k_q and v_q must be 16-byte aligned");
     if (B == 0 || T == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_T("setok_kv_append_mxfp4", (launch_append_mxfp4<bf16>(s, (const bf16*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, cap, pos0)),
-               (launch_append_mxfp4<float>(s, (const float*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, cap, pos0)));
+    DISPATCH_T("setok_kv_append_mxfp4", (launch_append_mxfp4<bf16>(s, (const bf16*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, Mx4ToDense{cap, pos0})),
+               (launch_append_mxfp4<float>(s, (const float*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, Mx4ToDense{cap, pos0})));
     SETOK_CHECK_LAUNCH("setok_kv_append_mxfp4");
     return SETOK_OK;
 }

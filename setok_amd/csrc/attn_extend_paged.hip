@@ -1,6 +1,8 @@
 // attn_extend_paged.hip — extending sequences of the paged KV cache by Tn >= 1 tokens each (include/setok_hip.h, "Paged extend attention"): a request
 // that starts behind a shared prefix, and what a verify pass or a prefill window over pages will need.
-//   setok_attention_extend_gqa_paged   Tn query rows per (sequence, query head) against the sequence's own len0[b] + Tn slots, found through the table
+//   setok_attention_extend_gqa_paged          Tn query rows per (sequence, query head) against the sequence's own len0[b] + Tn slots, found through the table
+//   setok_attention_extend_gqa_paged_mxfp4kv  the same over MXFP4 pools (attn_paged.hip): the wave-per-chunk kernel below over the KvMxfp4 format for
+//                                             every Dh % 32 == 0 and element type — the functional path, as the dense MXFP4 extend is; no MFMA over nibbles
 // Query i of sequence b counts slot j iff j <= len0[b] + i and table[b][j / SETOK_KV_PAGE] is a page; len0[b] < 0 is an idle sequence (zeros).
 //
 // These are attn_extend.hip's two kernels with two things replaced, as attn_decode_paged_kernel did it for decode — where a tile's rows start (a table
@@ -8,7 +10,8 @@
 // and no mask bytes: a page that is "no page" is what a mask that is zero on its 128 slots is to the dense kernel.  The dense kernel's key tiles are
 // 32 slots counted from slot 0, its chunks 256 and its spans 1024, so a tile never straddles a page and chunks and spans are whole pages: the same
 // partition into partials, the same online softmax per tile, the same merge in chunk order (attn_partials.h).  So a sequence's output bits are those
-// of setok_attention_extend_gqa at B = 1, len0 = len0[b], on its slots gathered into a dense cache, wherever its pages lie.
+// of setok_attention_extend_gqa (over MXFP4 pools: of setok_attention_extend_gqa_mxfp4kv, whose chunks are the same 256 slots) at B = 1,
+// len0 = len0[b], on its slots gathered into a dense cache, wherever its pages lie.
 //
 // No address is formed from a page id outside [0, num_pages), nor from a table index at or past max_pages: such a tile is not staged and no key of
 // it counts.  With that, every pool address lies inside a page the table names and every table address inside the sequence's row.
@@ -204,12 +207,13 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_paged_kernel(const bf16* 
 
 // ---- every other case: attn_chunk_any_kernel (attn_partials.h) over pages, one wave per (query row, query head, chunk), a key per lane -------------
 // grid (B * Tn, H, chunks of max_len0 + Tn).  Only a slot that counts is read: below the row's own limit, in a page.  A chunk is EXT_CHUNK / PAGE
-// whole pages, whose ids the wave loads once.
-template <typename T>
-__global__ __launch_bounds__(64) void attn_chunk_paged_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kp, const T* __restrict__ vp,
-                                                              const int* __restrict__ table, int max_pages, int num_pages, const int* __restrict__ lens0,
-                                                              float* __restrict__ ws, int Tn, int H, int Hkv, int Dh, float scale) {
+// whole pages, whose ids the wave loads once.  kv: the pools in the format F (attn_partials.h), read an element at a time as attn_chunk_any_kernel does.
+template <typename T, typename F>
+__global__ __launch_bounds__(64) void attn_chunk_paged_kernel(const T* __restrict__ q, int64_t ldq, F kv, const int* __restrict__ table, int max_pages,
+                                                              int num_pages, const int* __restrict__ lens0, float* __restrict__ ws, int Tn, int H, int Hkv,
+                                                              int Dh, float scale) {
     constexpr int CHUNK = EXT_CHUNK, NPG = CHUNK / PAGE;
+    static_assert(!F::SCALED, "no exponent per row: the e4m3 format has no extend attention");
     __shared__ float ps[CHUNK];
     const int row = blockIdx.x, h = blockIdx.y, c = blockIdx.z, nch = gridDim.z, lane = threadIdx.x;
     const int b = row / Tn, len0 = lens0[b];
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(64) void attn_chunk_paged_kernel(const T* __restric
         const int64_t r = rowof(jj);
         if (j < len && r >= 0) {
             float a = 0.f;
-            for (int d = 0; d < Dh; ++d) a = fmaf((float)qr[d], (float)kp[r * Dh + d], a);
+            for (int d = 0; d < Dh; ++d) a = fmaf((float)qr[d], F::at(kv.k, r * Dh + d), a);
             sc = a * scale;
         }
         ps[jj] = sc;
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(64) void attn_chunk_paged_kernel(const T* __restric
         for (int jj = 0; jj < CHUNK; ++jj)
             if (ps[jj] != 0.f) {                                       // (a non-zero weight: the slot counts for this row, so it lies in a page)
                 const float pr = rnd<T>(ps[jj]);
-                o = fmaf(pr, (float)vp[rowof(jj) * Dh + d], o);
+                o = fmaf(pr, F::at(kv.v, rowof(jj) * Dh + d), o);
             }
         part[2 + d] = o;
     }
@@ -291,10 +295,23 @@ int extend_paged_t(const char* name, hipStream_t s, const T* q, int64_t ldq, con
             attn_extend_paged_kernel<4><<<dim3(nch, Hkv * cdiv(MR, 128), B), 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kp, (const bf16*)vp, table,
                                                                                         max_pages, num_pages, lens0, ws, Tn, H, Hkv, span, sl);
     } else {
-        attn_chunk_paged_kernel<T><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kp, vp, table, max_pages, num_pages, lens0, ws, Tn, H, Hkv, Dh, scale);
+        attn_chunk_paged_kernel<T, KvNative<T>><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, KvNative<T>{kp, vp}, table, max_pages, num_pages, lens0, ws, Tn, H,
+                                                                                  Hkv, Dh, scale);
     }
     if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(chunks): %s", name, hipGetErrorString(e));
     attn_extend_merge_paged_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, lens0, nch, span, Tn, H, Dh);
+    if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(merge): %s", name, hipGetErrorString(e));
+    return SETOK_OK;
+}
+
+// Over MXFP4 pools: the wave-per-chunk kernel for every head dim and element type, one partial per chunk (the dense MXFP4 extend's partition).
+template <typename T>
+int extend_paged_mxfp4_t(const char* name, hipStream_t s, const T* q, int64_t ldq, KvMxfp4 kv, const int* table, int max_pages, int num_pages,
+                         const int* lens0, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh, int max_len0, float scale) {
+    const int nch = cdiv(max_len0 + Tn, EXT_CHUNK);
+    attn_chunk_paged_kernel<T, KvMxfp4><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kv, table, max_pages, num_pages, lens0, ws, Tn, H, Hkv, Dh, scale);
+    if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(chunks): %s", name, hipGetErrorString(e));
+    attn_extend_merge_paged_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, lens0, nch, EXT_CHUNK, Tn, H, Dh);
     if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(merge): %s", name, hipGetErrorString(e));
     return SETOK_OK;
 }
@@ -331,4 +348,36 @@ extern "C" int setok_attention_extend_gqa_paged(void* stream, int dtype, const v
                                     (bf16*)out, ws, B, Tn, H, Hkv, Dh, max_len0, scale);
     return extend_paged_t<float>(name, s, (const float*)q, ldq, (const float*)k_pool, (const float*)v_pool, block_table, max_pages, num_pages, len0,
                                  (float*)out, ws, B, Tn, H, Hkv, Dh, max_len0, scale);
+}
+
+extern "C" int64_t setok_attention_extend_paged_mxfp4kv_workspace(int B, int Tn, int H, int Dh, int max_len0) {
+    return setok_attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, max_len0);          // the dense MXFP4 rule at len0 = max_len0: one partial per chunk
+}
+
+extern "C" int setok_attention_extend_gqa_paged_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                                        const uint8_t* v_q, const uint8_t* v_s, const int32_t* block_table, int max_pages, int num_pages,
+                                                        const int32_t* len0, void* out, int B, int Tn, int H, int Hkv, int Dh, int max_len0, float scale,
+                                                        float* ws, int64_t ws_floats) {
+    const char* name = "setok_attention_extend_paged_mxfp4kv";
+    SETOK_CHECK_ARG(q && k_q && k_s && v_q && v_s && block_table && len0 && out && ws, "%s: null operand", name);
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "%s: bad dtype %d", name, dtype);
+    SETOK_CHECK_ARG(B >= 0 && B <= 65535 && Tn >= 1 && H > 0 && H <= 65535 && Hkv > 0 && H % Hkv == 0 && max_pages > 0 && num_pages > 0,
+                    "%s: bad shape B=%d Tn=%d H=%d Hkv=%d max_pages=%d num_pages=%d", name, B, Tn, H, Hkv, max_pages, num_pages);
+    SETOK_CHECK_ARG(Dh > 0 && Dh % 32 == 0, "%s: unsupported head dim %d (a multiple of 32, the MX block)", name, Dh);
+    SETOK_CHECK_ARG(max_len0 >= 0 && (int64_t)max_len0 + Tn <= (int64_t)max_pages * PAGE,
+                    "%s: slots [%d, %d + %d) outside [0, max_pages = %d * %d slots] (beyond the table)", name, max_len0, max_len0, Tn, max_pages, PAGE);
+    SETOK_CHECK_ARG((int64_t)B * Tn <= 0x7fffffffll && cdiv(max_len0 + Tn, EXT_CHUNK) <= 65535, "%s: B=%d Tn=%d H=%d max_len0=%d exceed the launch grid", name,
+                    B, Tn, H, max_len0);
+    SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_q) && aligned16(v_q),
+                    "%s: q rows (stride %lld) and the nibble pools must be 16-byte aligned", name, (long long)ldq);
+    const int64_t need = setok_attention_extend_paged_mxfp4kv_workspace(B, Tn, H, Dh, max_len0);
+    SETOK_CHECK_ARG(ws_floats >= need, "%s: workspace of %lld floats, %lld needed", name, (long long)ws_floats, (long long)need);
+    if (B == 0) return SETOK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const KvMxfp4 kv{{k_q, k_s}, {v_q, v_s}};
+    if (dtype == SETOK_BF16)
+        return extend_paged_mxfp4_t<bf16>(name, s, (const bf16*)q, ldq, kv, block_table, max_pages, num_pages, len0, (bf16*)out, ws, B, Tn, H, Hkv, Dh, max_len0,
+                                          scale);
+    return extend_paged_mxfp4_t<float>(name, s, (const float*)q, ldq, kv, block_table, max_pages, num_pages, len0, (float*)out, ws, B, Tn, H, Hkv, Dh, max_len0,
+                                       scale);
 }

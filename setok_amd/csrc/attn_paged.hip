@@ -1,26 +1,34 @@
-// attn_paged.hip — the paged KV cache: one layer's keys / values live in pools of pages, (num_pages, Hkv, SETOK_KV_PAGE, Dh) in the element type, and
-// a sequence is a row of a block table (entry p: the page that holds its slots [128 p, 128 p + 128)) plus a length of its own.
-//   setok_kv_append_paged             the post-rotary k / v columns of a fused [q | k | v] buffer -> slots [slot0[b], slot0[b] + T) of sequence b
-//   setok_attention_decode_gqa_paged  one query row per (sequence, query head) against the sequence's own lens[b] slots, found through the table
+// attn_paged.hip — the paged KV cache: one layer's keys / values live in pools of pages and a sequence is a row of a block table (entry p: the
+// page that holds its slots [128 p, 128 p + 128)) plus a length of its own.  Two pool formats (attn_partials.h): the element type — two pools
+// (num_pages, Hkv, SETOK_KV_PAGE, Dh) — and MXFP4 — nibble pools (…, Dh / 2) and scale pools (…, Dh / 32), a row meaning what a row of the dense
+// MXFP4 cache means.
+//   setok_kv_append_paged                     the post-rotary k / v columns of a fused [q | k | v] buffer -> slots [slot0[b], slot0[b] + T) of sequence b
+//   setok_attention_decode_gqa_paged          one query row per (sequence, query head) against the sequence's own lens[b] slots, found through the table
+//   setok_kv_append_paged_mxfp4, setok_attention_decode_gqa_paged_mxfp4kv     the same two over MXFP4 pools
 //
-// A page is exactly one chunk of the decode attention (SETOK_KV_PAGE == SETOK_DECODE_CHUNK), so the workgroup that owns chunk c of a sequence reads
-// exactly one page: 128 contiguous rows per key / value head, as in the dense cache.  The kernel below is attn_decode_kernel (attn_decode.hip) over
-// the native format with two things replaced — where the chunk's rows start (a table entry instead of b * Hkv * cap) and where `len` comes from
-// (lens[b] instead of an argument) — and no mask bytes: the same wave slices, row_sum, rounding point of the probabilities, wave-order reduction
-// and (attn_partials.h: merge_chunks) merge.  So a sequence's output bits are those of setok_attention_decode_gqa on its slots gathered into a
-// dense cache with an all-ones mask, wherever its pages lie.
+// The kernel below is attn_decode_kernel (attn_decode.hip) over the format F with two things replaced — where a wave's rows start (a table entry
+// instead of b * Hkv * cap) and where `len` comes from (lens[b] instead of an argument) — and no mask bytes: the same wave slices, row_sum,
+// rounding point of the probabilities, wave-order reduction and (attn_partials.h: merge_chunks) merge.  So a sequence's output bits are those of
+// the dense entry of the same format on its slots gathered into a dense cache with an all-ones mask, wherever its pages lie.
 //
-// A page id outside [0, num_pages) means "no page": the append writes nothing for such a row, the attention counts no key of such a chunk, and
+// A chunk of the decode attention is F::CHUNK slots: one page in the native format (SETOK_KV_PAGE == SETOK_DECODE_CHUNK), TWO over nibble rows
+// (SETOK_DECODE_CHUNK_MXFP4KV = 256).  Either way a wave's slice — a quarter of the chunk, 32 or 64 keys — lies inside one page, so the page is
+// looked up per wave: over nibble rows waves 0-1 of chunk c read table entry 2c, waves 2-3 entry 2c + 1.  A wave reads its entry only if its slice
+// starts below the sequence's length and the entry lies inside the table row (entry 2c + 1 may not, at an odd max_pages).
+//
+// A page id outside [0, num_pages) means "no page": the append writes nothing for such a row, the attention counts no key of such a page, and
 // neither forms an address from the id.
 #include "common.h"
 #include "attn_partials.h"
+#include <type_traits>
 
-static_assert(SETOK_KV_PAGE == SETOK_DECODE_CHUNK, "a page is one chunk of the decode attention: a chunk's workgroup reads exactly one page");
+static_assert(SETOK_KV_PAGE == SETOK_DECODE_CHUNK, "native pools: a page is one chunk of the decode attention, a chunk's workgroup reads exactly one page");
+static_assert(SETOK_DECODE_CHUNK_MXFP4KV == 2 * SETOK_KV_PAGE, "MXFP4 pools: a chunk's workgroup covers two pages, a wave's slice of 64 slots lies in one");
 
 namespace {
 
 constexpr int PAGE = SETOK_KV_PAGE;
-constexpr int DEC_WAVES = 4;                              // as in attn_decode.hip: a wave's slice is PAGE / 4 = 32 keys
+constexpr int DEC_WAVES = 4;                              // as in attn_decode.hip: a wave's slice is F::CHUNK / 4 keys, 32 native and 64 over nibble rows
 
 // ---- kv_append through the table --------------------------------------------------------------------------------------------------------------
 // kv_append_kernel's enumeration of 16-byte pieces; the destination row is page table[b][slot / PAGE], row slot % PAGE.  Nothing is written for a
@@ -51,29 +59,32 @@ __global__ __launch_bounds__(256) void kv_append_paged_kernel(const T* __restric
     }
 }
 
-// ---- decode attention, a page per workgroup, a row spread over LPR lanes -----------------------------------------------------------------------
-// grid (chunks of max_len, Hkv * (G / GT), B).  Chunk c of sequence b holds keys iff c * PAGE < lens[b] and table[b][c] is a page; otherwise every wave
-// writes the empty partial, loads nothing from the pools and — a chunk at or past the sequence's length — does not read the table either.
-template <typename T, int LPR, int GT>
-__global__ __launch_bounds__(256) void attn_decode_paged_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ kp, const T* __restrict__ vp,
-                                                                const int* __restrict__ table, int max_pages, int num_pages,
-                                                                const int* __restrict__ lens, float* __restrict__ ws, int H, int Hkv, float scale) {
-    typedef KvNative<T> F;
-    constexpr int VEC = F::VEC, DH = LPR * VEC, KPS = 64 / LPR, WKEYS = PAGE / DEC_WAVES, NSTEP = WKEYS / KPS, QV = Elem<T>::VEC;
+// ---- decode attention, a chunk of F::CHUNK slots per workgroup, a row spread over LPR lanes ---------------------------------------------------
+// grid (chunks of max_len, Hkv * (G / GT), B).  kv: the pools in the format F, a pool row where a cache row was.  The slice of wave w of chunk c — slots
+// [jw, jw + WKEYS), jw = c * F::CHUNK + w * WKEYS, inside page entry jw / PAGE — holds keys iff jw < lens[b] and that entry lies in the table row and is a
+// page; otherwise the wave writes the empty partial, loads nothing from the pools and — a slice at or past the sequence's length, or an entry at or
+// past max_pages — does not read the table either.
+template <typename T, typename F, int LPR, int GT>
+__global__ __launch_bounds__(256) void attn_decode_paged_kernel(const T* __restrict__ q, int64_t ldq, F kv, const int* __restrict__ table, int max_pages,
+                                                                int num_pages, const int* __restrict__ lens, float* __restrict__ ws, int H, int Hkv,
+                                                                float scale) {
+    constexpr int VEC = F::VEC, DH = LPR * VEC, KPS = 64 / LPR, WKEYS = F::CHUNK / DEC_WAVES, NSTEP = WKEYS / KPS, QV = Elem<T>::VEC;
     static_assert(WKEYS % KPS == 0 && NSTEP >= 1, "a wave's slice is a whole number of load steps");
+    static_assert(!F::SCALED && F::CHUNK % PAGE == 0 && PAGE % WKEYS == 0, "no exponent per row; a chunk is whole pages and a wave's slice lies in one page");
     typedef typename F::Raw V16;
     __shared__ float red[DEC_WAVES][GT][DH + 2];
     const int c = blockIdx.x, b = blockIdx.z, nch = gridDim.x;
     const int G = H / Hkv, npass = G / GT;
     const int hk = blockIdx.y / npass, h0 = hk * G + (blockIdx.y % npass) * GT;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane / LPR, cc = lane % LPR;
+    const int jw = c * F::CHUNK + wave * WKEYS;                        // the wave's first key
+    const int pi = jw / PAGE;                                          // (wave-uniform) the table entry of the wave's slice: c natively, 2c + wave / 2 over nibble rows
     int len = lens[b], page = 0;
-    if (c * PAGE < len) {
-        page = table[(int64_t)b * max_pages + c];                      // (c < ceil(max_len / PAGE) <= max_pages: the host's check)
-        if (page < 0 || page >= num_pages) { page = 0; len = 0; }      // no page: no key of this chunk counts
+    if (jw < len) {
+        page = pi < max_pages ? table[(int64_t)b * max_pages + pi] : -1;               // an entry at or past max_pages is not read: no page
+        if (page < 0 || page >= num_pages) { page = 0; len = 0; }      // no page: no key of this slice counts
     }
-    const int64_t rowbase = ((int64_t)page * Hkv + hk) * PAGE - (int64_t)c * PAGE;      // slot j of the chunk is row rowbase + j of the pool
-    const int jw = c * PAGE + wave * WKEYS;                            // the wave's first key
+    const int64_t rowbase = ((int64_t)page * Hkv + hk) * PAGE - (int64_t)pi * PAGE;    // slot j of the wave's page is row rowbase + j of the pool
 
     if (jw >= len) {                                                   // the whole slice lies past len: no key, nothing to load
         if (r == 0) {
@@ -90,12 +101,12 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const T* __restr
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            kr[i] = F::load(kp, (rowbase + jc) * DH + cc * VEC);
+            kr[i] = F::load(kv.k, (rowbase + jc) * DH + cc * VEC);
         }
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
             const int j = jw + i * KPS + r, jc = j < len ? j : len - 1;
-            vr[i] = F::load(vp, (rowbase + jc) * DH + cc * VEC);
+            vr[i] = F::load(kv.v, (rowbase + jc) * DH + cc * VEC);
         }
         float qf[GT][VEC];
 #pragma unroll
@@ -183,24 +194,24 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const T* __restr
     }
 }
 
-// ---- merge: the dense merge's loop over the sequence's own ceil(lens[b] / PAGE) chunks (at most the launch's nch: lens[b] <= max_len is the caller's promise) ----
+// ---- merge: the dense merge's loop over the sequence's own ceil(lens[b] / chunk) chunks (at most the launch's nch: lens[b] <= max_len is the caller's promise) ----
 template <typename T>
 __global__ __launch_bounds__(64) void attn_decode_merge_paged_kernel(const float* __restrict__ ws, T* __restrict__ out, const int* __restrict__ lens,
-                                                                     int nch, int H, int Dh) {
+                                                                     int nch, int chunk, int H, int Dh) {
     const int64_t bh = blockIdx.x;                                     // b * H + h; out rows are H * Dh wide
     const int len = lens[bh / H];
-    int n = len <= 0 ? 0 : (len - 1) / PAGE + 1;
+    int n = len <= 0 ? 0 : (len - 1) / chunk + 1;
     n = n < nch ? n : nch;
     merge_chunks<T>(ws + bh * nch * (Dh + 2), out + bh * Dh, n, Dh);
 }
 
-template <typename T, int LPR>
-void launch_decode_paged(hipStream_t s, const T* q, int64_t ldq, const T* kp, const T* vp, const int* table, int max_pages, int num_pages, const int* lens,
-                         float* ws, int B, int H, int Hkv, int nch, float scale) {
+template <typename T, typename F, int LPR>
+void launch_decode_paged(hipStream_t s, const T* q, int64_t ldq, F kv, const int* table, int max_pages, int num_pages, const int* lens, float* ws, int B,
+                         int H, int Hkv, int nch, float scale) {
     const int G = H / Hkv;
     const int GT = G % 8 == 0 ? 8 : G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1;
     dim3 grid(nch, Hkv * (G / GT), B);
-#define PAGED_GT(N) attn_decode_paged_kernel<T, LPR, N><<<grid, 256, 0, s>>>(q, ldq, kp, vp, table, max_pages, num_pages, lens, ws, H, Hkv, scale); break
+#define PAGED_GT(N) attn_decode_paged_kernel<T, F, LPR, N><<<grid, 256, 0, s>>>(q, ldq, kv, table, max_pages, num_pages, lens, ws, H, Hkv, scale); break
     switch (GT) {
         case 8: PAGED_GT(8);
         case 4: PAGED_GT(4);
@@ -210,23 +221,32 @@ void launch_decode_paged(hipStream_t s, const T* q, int64_t ldq, const T* kp, co
 #undef PAGED_GT
 }
 
-template <typename T>
-int decode_paged_t(const char* name, hipStream_t s, const T* q, int64_t ldq, const T* kp, const T* vp, const int* table, int max_pages, int num_pages,
-                   const int* lens, T* out, float* ws, int B, int H, int Hkv, int Dh, int max_len, float scale) {
-    const int nch = cdiv(max_len, PAGE);
+// Both decode entries (`name`: the entry's, for its messages).  The head dim has a lane layout in F: the entry checked it (paged_head_dim, paged_mxfp4_head_dim).
+template <typename T, typename F>
+int decode_paged_t(const char* name, hipStream_t s, const T* q, int64_t ldq, F kv, const int* table, int max_pages, int num_pages, const int* lens, T* out,
+                   float* ws, int B, int H, int Hkv, int Dh, int max_len, float scale) {
+    const int nch = cdiv(max_len, F::CHUNK);
     if (nch > 0) {                                                     // (max_len == 0: every sequence is empty, the merge alone writes the zeros)
-#define PAGED_LPR(N) launch_decode_paged<T, N>(s, q, ldq, kp, vp, table, max_pages, num_pages, lens, ws, B, H, Hkv, nch, scale); break
-        switch (Dh / Elem<T>::VEC) {
-            case 2: PAGED_LPR(2);
-            case 4: PAGED_LPR(4);
-            case 8: PAGED_LPR(8);
-            case 16: PAGED_LPR(16);                                    // head dim 128 in the 16-bit types
-            default: PAGED_LPR(32);
+#define PAGED_LPR(N) launch_decode_paged<T, F, N>(s, q, ldq, kv, table, max_pages, num_pages, lens, ws, B, H, Hkv, nch, scale); break
+        if constexpr (std::is_same<F, KvMxfp4>::value) {               // 16 elements per lane: attn_decode.hip's three lane layouts over nibble rows
+            switch (Dh) {
+                case 32: PAGED_LPR(2);
+                case 64: PAGED_LPR(4);
+                default: PAGED_LPR(8);
+            }
+        } else {
+            switch (Dh / F::VEC) {
+                case 2: PAGED_LPR(2);
+                case 4: PAGED_LPR(4);
+                case 8: PAGED_LPR(8);
+                case 16: PAGED_LPR(16);                                // head dim 128 in the 16-bit types
+                default: PAGED_LPR(32);
+            }
         }
 #undef PAGED_LPR
         if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(chunks): %s", name, hipGetErrorString(e));
     }
-    attn_decode_merge_paged_kernel<T><<<B * H, 64, 0, s>>>(ws, out, lens, nch, H, Dh);
+    attn_decode_merge_paged_kernel<T><<<B * H, 64, 0, s>>>(ws, out, lens, nch, F::CHUNK, H, Dh);
     if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(merge): %s", name, hipGetErrorString(e));
     return SETOK_OK;
 }
@@ -273,8 +293,51 @@ extern "C" int setok_attention_decode_gqa_paged(void* stream, int dtype, const v
     if (B == 0) return SETOK_OK;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == SETOK_BF16)
-        return decode_paged_t<bf16>(name, s, (const bf16*)q, ldq, (const bf16*)k_pool, (const bf16*)v_pool, block_table, max_pages, num_pages, lens,
-                                    (bf16*)out, ws, B, H, Hkv, Dh, max_len, scale);
-    return decode_paged_t<float>(name, s, (const float*)q, ldq, (const float*)k_pool, (const float*)v_pool, block_table, max_pages, num_pages, lens,
-                                 (float*)out, ws, B, H, Hkv, Dh, max_len, scale);
+        return decode_paged_t<bf16>(name, s, (const bf16*)q, ldq, KvNative<bf16>{(const bf16*)k_pool, (const bf16*)v_pool}, block_table, max_pages, num_pages,
+                                    lens, (bf16*)out, ws, B, H, Hkv, Dh, max_len, scale);
+    return decode_paged_t<float>(name, s, (const float*)q, ldq, KvNative<float>{(const float*)k_pool, (const float*)v_pool}, block_table, max_pages,
+                                 num_pages, lens, (float*)out, ws, B, H, Hkv, Dh, max_len, scale);
+}
+
+extern "C" int setok_kv_append_paged_mxfp4(void* stream, int dtype, const void* qkv, uint8_t* k_q, uint8_t* k_s, uint8_t* v_q, uint8_t* v_s,
+                                           const int32_t* block_table, int max_pages, int num_pages, const int32_t* slot0, int B, int T, int H, int Hkv,
+                                           int Dh) {
+    const char* name = "setok_kv_append_paged_mxfp4";
+    SETOK_CHECK_ARG(qkv && k_q && k_s && v_q && v_s && block_table && slot0, "%s: null operand", name);
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "%s: bad dtype %d", name, dtype);
+    SETOK_CHECK_ARG(B >= 0 && T >= 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && max_pages > 0 && num_pages > 0,
+                    "%s: bad shape B=%d T=%d H=%d Hkv=%d max_pages=%d num_pages=%d", name, B, T, H, Hkv, max_pages, num_pages);
+    SETOK_CHECK_ARG(paged_mxfp4_head_dim(Dh), "%s: unsupported head dim %d (32, 64 or 128: the lane layouts of the decode attention over nibble rows)", name, Dh);
+    SETOK_CHECK_ARG(aligned16(qkv) && aligned16(k_q) && aligned16(v_q), "%s: qkv and the nibble pools must be 16-byte aligned", name);
+    if (B == 0 || T == 0) return SETOK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const Mx4ToPages dest{block_table, slot0, max_pages, num_pages};
+    DISPATCH_T("setok_kv_append_paged_mxfp4", (launch_append_mxfp4<bf16>(s, (const bf16*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, dest)),
+               (launch_append_mxfp4<float>(s, (const float*)qkv, k_q, k_s, v_q, v_s, B, T, H, Hkv, Dh, dest)));
+    SETOK_CHECK_LAUNCH(name);
+    return SETOK_OK;
+}
+
+extern "C" int setok_attention_decode_gqa_paged_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
+                                                        const uint8_t* v_q, const uint8_t* v_s, const int32_t* block_table, int max_pages, int num_pages,
+                                                        const int32_t* lens, void* out, int B, int H, int Hkv, int Dh, int max_len, float scale, float* ws,
+                                                        int64_t ws_floats) {
+    const char* name = "setok_attention_decode_paged_mxfp4kv";
+    SETOK_CHECK_ARG(q && k_q && k_s && v_q && v_s && block_table && lens && out && ws, "%s: null operand", name);
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "%s: bad dtype %d", name, dtype);
+    SETOK_CHECK_ARG(B >= 0 && B <= 65535 && H > 0 && Hkv > 0 && H % Hkv == 0 && max_pages > 0 && num_pages > 0,
+                    "%s: bad shape B=%d H=%d Hkv=%d max_pages=%d num_pages=%d", name, B, H, Hkv, max_pages, num_pages);
+    SETOK_CHECK_ARG(paged_mxfp4_head_dim(Dh), "%s: unsupported head dim %d (32, 64 or 128: no paged twin of the generic kernel)", name, Dh);
+    SETOK_CHECK_ARG(max_len >= 0 && (int64_t)max_len <= (int64_t)max_pages * PAGE, "%s: max_len = %d outside [0, max_pages = %d * %d slots] (beyond the table)",
+                    name, max_len, max_pages, PAGE);
+    SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_q) && aligned16(v_q),
+                    "%s: q rows (stride %lld) and the nibble pools must be 16-byte aligned", name, (long long)ldq);
+    const int64_t need = (int64_t)B * H * cdiv(max_len, KvMxfp4::CHUNK) * (Dh + 2);
+    SETOK_CHECK_ARG(ws_floats >= need, "%s: workspace of %lld floats, %lld needed", name, (long long)ws_floats, (long long)need);
+    if (B == 0) return SETOK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const KvMxfp4 kv{{k_q, k_s}, {v_q, v_s}};
+    if (dtype == SETOK_BF16)
+        return decode_paged_t<bf16>(name, s, (const bf16*)q, ldq, kv, block_table, max_pages, num_pages, lens, (bf16*)out, ws, B, H, Hkv, Dh, max_len, scale);
+    return decode_paged_t<float>(name, s, (const float*)q, ldq, kv, block_table, max_pages, num_pages, lens, (float*)out, ws, B, H, Hkv, Dh, max_len, scale);
 }

@@ -3,6 +3,7 @@
 // query head's chunks in chunk order.  ONE definition of the merge and of the exponential both sides of it use: a partial is only meaningful to the
 // merge that rescales it.  Also here, once: the cache formats (native, fp8, MXFP4) as the kernels see them, and the wave-per-chunk kernel every head dim without a
 // lane layout falls back to, whichever entry point it came through; and row_sum, the lane-group reduction of the lane-layout kernels (dense and paged).
+// And the MXFP4 quantiser of kv_append, once for the dense cache and the pages (kv_append_mxfp4_kernel, with row_max).
 #pragma once
 #include "common.h"
 #include "fp8.h"
@@ -182,10 +183,119 @@ static inline bool paged_head_dim(int dtype, int Dh) {
     return lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16 || lpr == 32;
 }
 
+// The head dims the paged MXFP4 entries take: those with a lane layout over nibble rows (16 elements per lane; attn_decode.hip's decode_t has the
+// same three), so that a paged sequence's bits are the dense lane-layout kernel's.  The paged extend alone would serve every Dh % 32 == 0.
+static inline bool paged_mxfp4_head_dim(int Dh) { return Dh == 32 || Dh == 64 || Dh == 128; }
+
 template <typename T>
 __global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* __restrict__ ws, T* __restrict__ out, int nch, int H, int Dh) {
     const int64_t bh = blockIdx.x;                                     // b * H + h; out rows are H * Dh wide
     merge_chunks<T>(ws + bh * nch * (Dh + 2), out + bh * Dh, nch, Dh);
+}
+
+// Maximum over aligned groups of N lanes of non-negative values, every lane of a group ending with the same bits: row_sum's exchanges.
+template <int CTRL> __device__ inline float dpp_max(float a) {
+    return fmaxf(a, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), CTRL, 0xf, 0xf, false)));
+}
+template <int N> __device__ inline float row_max(float a) {
+    if constexpr (N >= 2) a = dpp_max<0xB1>(a);
+    if constexpr (N >= 4) a = dpp_max<0x4E>(a);
+    if constexpr (N >= 8) a = dpp_max<0x141>(a);
+    if constexpr (N >= 16) a = dpp_max<0x140>(a);
+#pragma unroll
+    for (int o = 16; o < N; o <<= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+    return a;
+}
+
+// ==== filling an MXFP4 KV cache, dense (attn_decode.hip) or paged (attn_paged.hip): ONE quantiser, the destination a parameter ====================
+// A cache row is Dh / 2 bytes of e2m1 nibbles + Dh / 32 e8m0 scale bytes and means value(nibble[d]) * 2^(s[d / 32] - 127) (mx4.h: the rule of
+// the weight path).  kv_append_fp8_kernel's arrangement: one pass, a row in the registers of GL lanes, 8 elements each, so a block of 32 is an
+// aligned quad of lanes and its amax two quad_perm exchanges; a lane writes its 8 nibbles as one dword, the quad's first lane the scale byte.
+// Dh % 32 == 0, so a row is a whole number of quads and a lane without a piece shares a quad with no live lane.
+//
+// D says where the row of (sequence b, new token t, key / value head hk) goes: row(b, t, hk, Hkv) is its row in the (…, Dh / 2) and (…, Dh / 32)
+// operands, or < 0 for "nowhere".  A row that goes nowhere is skipped by predication — its lanes load nothing, carry zeros through the exchanges
+// (which need every lane of a quad) and store nothing —, never by leaving the loop.
+struct Mx4ToDense {                                                    // slot pos0 + t of a (B, Hkv, cap, ·) cache
+    int cap, pos0;
+    __device__ inline int64_t row(int b, int t, int hk, int Hkv) const { return ((int64_t)b * Hkv + hk) * cap + pos0 + t; }
+};
+struct Mx4ToPages {                                                    // slot slot0[b] + t of sequence b, through its row of the block table
+    const int* table;
+    const int* slot0;
+    int max_pages, num_pages;
+    __device__ inline int64_t row(int b, int t, int hk, int Hkv) const {
+        const int s0 = slot0[b];
+        if (s0 < 0) return -1;                                         // an idle row of the running batch
+        const int64_t slot = (int64_t)s0 + t, pi = slot / SETOK_KV_PAGE;
+        if (pi >= max_pages) return -1;
+        const int page = table[(int64_t)b * max_pages + pi];
+        if (page < 0 || page >= num_pages) return -1;                  // no page: nothing is written, no address is formed
+        return ((int64_t)page * Hkv + hk) * SETOK_KV_PAGE + slot % SETOK_KV_PAGE;
+    }
+};
+
+// Rows are numbered ((b * T + t) * 2 + which) * Hkv + hk; a workgroup takes 256 / GL of them per trip, every wave makes the same number of trips.
+template <typename T, int GL, typename D>
+__global__ __launch_bounds__(256) void kv_append_mxfp4_kernel(const T* __restrict__ qkv, uint8_t* __restrict__ kq, uint8_t* __restrict__ ks,
+                                                              uint8_t* __restrict__ vq, uint8_t* __restrict__ vs, int B, int Tn, int H, int Hkv, int Dh,
+                                                              D dest) {
+    constexpr int RPB = 256 / GL;                                      // rows per workgroup and trip
+    const int vpr = Dh / 8, sub = threadIdx.x % GL;
+    const int64_t rows = (int64_t)B * Tn * 2 * Hkv, ld = (int64_t)(H + 2 * Hkv) * Dh;
+    for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < rows; r0 += (int64_t)gridDim.x * RPB) {
+        const int64_t row = r0 + threadIdx.x / GL;
+        bool live = row < rows && sub < vpr;
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = 0.f;
+        int which = 0;
+        int64_t slot = 0;
+        if (live) {
+            const int hk = (int)(row % Hkv);
+            which = (int)((row / Hkv) & 1);                            // 0 = k, 1 = v
+            const int64_t bt = row / (2 * Hkv);
+            slot = dest.row((int)(bt / Tn), (int)(bt % Tn), hk, Hkv);
+            live = slot >= 0;                                          // (the same for all lanes of the row, so for all lanes of a quad)
+            if (live) {
+                const T* src = qkv + bt * ld + (int64_t)(H + which * Hkv + hk) * Dh + sub * 8;
+#pragma unroll
+                for (int u = 0; u < 8 / Elem<T>::VEC; ++u) ld_vec<T>(src + u * Elem<T>::VEC, f + u * Elem<T>::VEC);
+            }
+        }
+        float amax = 0.f, bad = 0.f;                                   // bad: the block holds a non-finite entry (it becomes scale byte 0xFF, nibbles 0)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float a = fabsf(f[e]);
+            if (a <= 3.402823466e38f) amax = fmaxf(amax, a);
+            else bad = 1.f;
+        }
+        amax = row_max<4>(amax);
+        bad = row_max<4>(bad);
+        const int ex = mx4_exponent(amax);
+        const float inv = mx4_inv_scale(ex);
+        if (live) {
+            unsigned w = 0u;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w |= mx4_encode(f[e] * inv) << (4 * e);
+            *reinterpret_cast<unsigned*>((which ? vq : kq) + slot * (Dh / 2) + sub * 4) = bad != 0.f ? 0u : w;
+            if ((sub & 3) == 0) (which ? vs : ks)[slot * (Dh / 32) + (sub >> 2)] = (uint8_t)(bad != 0.f ? 0xff : 127 + ex);
+        }
+    }
+}
+
+template <typename T, typename D>
+void launch_append_mxfp4(hipStream_t s, const T* qkv, uint8_t* kq, uint8_t* ks, uint8_t* vq, uint8_t* vs, int B, int Tn, int H, int Hkv, int Dh, D dest) {
+    const int vpr = Dh / 8;
+    const int64_t rows = (int64_t)B * Tn * 2 * Hkv;
+#define MX4_APPEND(GL)                                                                                                          \
+    if (vpr <= GL) {                                                                                                            \
+        const int64_t wgs = (rows + 256 / GL - 1) / (256 / GL);                                                                 \
+        kv_append_mxfp4_kernel<T, GL, D><<<(int)(wgs > 65536 ? 65536 : wgs), 256, 0, s>>>(qkv, kq, ks, vq, vs, B, Tn, H, Hkv, Dh, dest); \
+        return;                                                                                                                 \
+    }
+    MX4_APPEND(4) MX4_APPEND(8) MX4_APPEND(16) MX4_APPEND(32) MX4_APPEND(64)
+#undef MX4_APPEND
 }
 
 }  // namespace

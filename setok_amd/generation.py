@@ -193,8 +193,23 @@ def _count(v, name: str, who: str) -> int:
     return v
 
 
+@dataclass
+class _PagedKVFormat:
+    """`_KVFormat` for the pools of `PagedKVCache`, chosen once in its `__init__`: the per-layer pool lists in the order the ops take them,
+    `append(qkv, *pools, table, slot0, T, H)`, `attend(q, *pools, table, lens, H, max_len, scale, ws=, out=)`,
+    `extend(q, *pools, table, len0, H, Tn, max_len0, scale, ws=, out=)`, the two workspace rules `decode_ws(B, H, Dh, max_len)` and
+    `extend_ws(n, Tn, H, Dh, max_len0, Hkv, dtype)`, and the bytes one slot of one key / value head takes."""
+    pools: Tuple[List[torch.Tensor], ...]
+    append: Callable
+    attend: Callable
+    extend: Callable
+    decode_ws: Callable
+    extend_ws: Callable
+    row_nbytes: int
+
+
 class PagedKVCache:
-    """The native-format cache without a capacity per sequence (include/setok_hip.h, "Paged KV cache"): per layer two pools `k[li]`, `v[li]` of
+    """The cache without a capacity per sequence (include/setok_hip.h, "Paged KV cache"): per layer two pools `k[li]`, `v[li]` of
     shape (num_pages, Hkv, ops.KV_PAGE, Dh) in the model's element type, shared by `rows` sequences.  A sequence is row r of `block_table`
     ((rows, max_pages_per_seq) int32 on the device, -1 = no page; entry p holds slots [128 p, 128 p + 128)) and `lens[r]` ((rows,) int32 on the device):
     every row has a length of its own, a compact sequence has no dead slots (there is no key mask; position == slot), and a finished sequence's
@@ -206,18 +221,47 @@ class PagedKVCache:
 
     `table_host` / `lens_host` mirror both on the host and `_free` is the host's free list.  The scheduler (this class's methods, called by
     `LlamaModel.prefill_paged` / `decode_step_paged` and `ContinuousBatcher`) is the only writer, so the mirrors are exact without any device read.
-    The pools are `torch.empty`: nothing depends on their initial contents - a slot is written before the sequence's length covers it."""
+    The pools are `torch.empty`: nothing depends on their initial contents - a slot is written before the sequence's length covers it.
 
-    def __init__(self, num_layers: int, rows: int, Hkv: int, Dh: int, dtype: torch.dtype, device, num_pages: int, max_pages_per_seq: int):
+    `kv_format="mxfp4"` stores a slot as OCP MXFP4, as `KVCache` does (include/setok_hip.h, "Paged MXFP4 KV cache"): per layer `k_q`, `v_q`
+    (num_pages, Hkv, 128, Dh/2) uint8 and `k_s`, `v_s` (num_pages, Hkv, 128, Dh/32) uint8, and `k` and `v` are empty lists;
+    2 * layers * num_pages * Hkv * 128 * (Dh/2 + Dh/32) bytes, 68 per slot at head dim 128 against 256 in 16 bits.  Head dims 32, 64 and 128 (the
+    ones the decode attention over nibble rows has a lane layout for); `"fp8"` is not built - that format has no extend attention, so it could not
+    serve prefixes.  Scheduling - pages, references, lengths - does not depend on the format; what does is one `_PagedKVFormat` record."""
+
+    FORMATS = ("native", "mxfp4")
+
+    def __init__(self, num_layers: int, rows: int, Hkv: int, Dh: int, dtype: torch.dtype, device, num_pages: int, max_pages_per_seq: int,
+                 kv_format: str = "native"):
         who = "PagedKVCache"
+        if kv_format == "fp8":
+            raise NotImplementedError(f"{who}: kv_format='fp8' is not implemented over pages (the fp8 cache has no extend attention, so it could not "
+                                      "serve shared prefixes); use kv_format='native' or 'mxfp4'")
+        if kv_format not in self.FORMATS:
+            raise ValueError(f"{who}: kv_format={kv_format!r} is not one of 'native', 'mxfp4'")
         for name, v in (("num_layers", num_layers), ("rows", rows), ("Hkv", Hkv), ("Dh", Dh), ("num_pages", num_pages),
                         ("max_pages_per_seq", max_pages_per_seq)):
             _count(v, name, who)
         self.num_layers, self.rows, self.Hkv, self.Dh, self.dtype = num_layers, rows, Hkv, Dh, dtype
-        self.num_pages, self.max_pages_per_seq = num_pages, max_pages_per_seq
-        pool = lambda: [torch.empty((num_pages, Hkv, ops.KV_PAGE, Dh), dtype=dtype, device=device) for _ in range(num_layers)]
-        self.k: List[torch.Tensor] = pool()
-        self.v: List[torch.Tensor] = pool()
+        self.num_pages, self.max_pages_per_seq, self.kv_format = num_pages, max_pages_per_seq, kv_format
+        pool = lambda cols, dt: [torch.empty((num_pages, Hkv, ops.KV_PAGE, cols), dtype=dt, device=device) for _ in range(num_layers)]
+        self.k: List[torch.Tensor] = []
+        self.v: List[torch.Tensor] = []
+        if kv_format == "mxfp4":
+            check_kv_head_dim(kv_format, Dh, who, "kv_format")
+            if Dh not in ops.PAGED_MXFP4_HEAD_DIMS:
+                raise ValueError(f"{who}: kv_format='mxfp4' needs a head dim of 32, 64 or 128 (the lane layouts of the decode attention over nibble "
+                                 f"rows), the model's is {Dh}; use kv_format='native'")
+            self.k_q, self.v_q = pool(Dh // 2, torch.uint8), pool(Dh // 2, torch.uint8)
+            self.k_s, self.v_s = pool(Dh // 32, torch.uint8), pool(Dh // 32, torch.uint8)
+            self._fmt = _PagedKVFormat((self.k_q, self.k_s, self.v_q, self.v_s), ops.kv_append_paged_mxfp4, ops.attention_decode_paged_mxfp4kv,
+                                       ops.attention_extend_paged_mxfp4kv, ops.attention_decode_paged_mxfp4kv_workspace,
+                                       lambda n, Tn, H, Dh, max_len0, Hkv, dtype: ops.attention_extend_paged_mxfp4kv_workspace(n, Tn, H, Dh, max_len0),
+                                       Dh // 2 + Dh // 32)
+        else:
+            self.k, self.v = pool(Dh, dtype), pool(Dh, dtype)
+            self._fmt = _PagedKVFormat((self.k, self.v), ops.kv_append_paged, ops.attention_decode_paged, ops.attention_extend_paged,
+                                       ops.attention_decode_paged_workspace, ops.attention_extend_paged_workspace, Dh * self.k[0].element_size())
         self.block_table = torch.full((rows, max_pages_per_seq), -1, dtype=torch.int32, device=device)
         self.lens = torch.zeros(rows, dtype=torch.int32, device=device)
         self.table_host: List[List[int]] = [[-1] * max_pages_per_seq for _ in range(rows)]
@@ -229,11 +273,17 @@ class PagedKVCache:
         self._ws_extend: Optional[torch.Tensor] = None
 
     @classmethod
-    def for_model(cls, model, rows: int, num_pages: int, max_pages_per_seq: int, device=None) -> "PagedKVCache":
-        """Pools for `model` (a LlamaModel): `rows` sequences at a time, `num_pages` pages of 128 slots per layer, at most `max_pages_per_seq` per sequence."""
+    def for_model(cls, model, rows: int, num_pages: int, max_pages_per_seq: int, device=None, kv_format: str = "native") -> "PagedKVCache":
+        """Pools for `model` (a LlamaModel): `rows` sequences at a time, `num_pages` pages of 128 slots per layer, at most `max_pages_per_seq` per
+        sequence, in `kv_format` ("native" or "mxfp4"; the constructor's refusals, before anything is allocated)."""
         w = model.norm.weight
         return cls(len(model.layers), rows, model.num_kv_heads, model.head_dim, w.dtype, device if device is not None else w.device, num_pages,
-                   max_pages_per_seq)
+                   max_pages_per_seq, kv_format)
+
+    @property
+    def fresh(self) -> bool:
+        """Nothing has used the cache yet, or everything gave it back: every row idle, every page free."""
+        return len(self._free) == self.num_pages and not any(self.lens_host) and all(p < 0 for row in self.table_host for p in row)
 
     @property
     def pages_free(self) -> int:
@@ -242,7 +292,7 @@ class PagedKVCache:
     @property
     def page_nbytes(self) -> int:
         """Bytes one page takes over all layers, keys and values."""
-        return 2 * self.num_layers * self.Hkv * ops.KV_PAGE * self.Dh * self.k[0].element_size()
+        return 2 * self.num_layers * self.Hkv * ops.KV_PAGE * self._fmt.row_nbytes
 
     def pages_of(self, row: int) -> List[int]:
         return [p for p in self.table_host[row] if p >= 0]
@@ -329,38 +379,41 @@ class PagedKVCache:
         self.lens_host[row] = n
         self.lens[row] = n
 
-    def append(self, li: int, qkv: torch.Tensor, T: int, H: int, slot0: torch.Tensor, row: Optional[int] = None) -> None:
+    def append(self, li: int, qkv: torch.Tensor, T: int, H: int, slot0: torch.Tensor, row: Optional[int] = None,
+               table: Optional[torch.Tensor] = None) -> None:
         """Layer `li`: the post-rotary k / v columns of the fused qkv buffer -> slots [slot0[b], slot0[b] + T) of every row (qkv: rows * T rows; a row
-        with slot0 < 0 is skipped), or - with `row` - of that one row (qkv: T rows, slot0 (1,))."""
-        table = self.block_table if row is None else self.block_table[row:row + 1]
-        ops.kv_append_paged(qkv, self.k[li], self.v[li], table, slot0, T, H)
+        with slot0 < 0 is skipped), or - with `row` - of that one row (qkv: T rows, slot0 (1,)), or - with `table` (n, max_pages_per_seq), gathered
+        rows of the block table - of those n sequences (qkv: n * T rows, slot0 (n,)); in the cache's own format."""
+        if table is None:
+            table = self.block_table if row is None else self.block_table[row:row + 1]
+        self._fmt.append(qkv, *(t[li] for t in self._fmt.pools), table, slot0, T, H)
 
     def attend(self, li: int, q: torch.Tensor, H: int, max_len: int, scale: float, ws: torch.Tensor, out: Optional[torch.Tensor],
                lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Layer `li`: one query row per (row, query head) against the row's own slots [0, lens[row]) (`lens`: the cache's, or the caller's (rows,)
         int32 - a decode step attends over the lengths it is about to commit); `max_len` is the host's upper bound on them."""
-        return ops.attention_decode_paged(q, self.k[li], self.v[li], self.block_table, self.lens if lens is None else lens, H, max_len, scale, ws=ws,
-                                          out=out)
+        return self._fmt.attend(q, *(t[li] for t in self._fmt.pools), self.block_table, self.lens if lens is None else lens, H, max_len, scale, ws=ws,
+                                out=out)
 
     def extend_attend(self, li: int, q: torch.Tensor, H: int, Tn: int, max_len0: int, scale: float, ws: torch.Tensor, out: Optional[torch.Tensor],
                       table: torch.Tensor, len0: torch.Tensor) -> torch.Tensor:
         """Layer `li`: Tn query rows per (sequence, query head) of the sequences `table` (n, max_pages_per_seq) describes, each behind its own
-        len0 (n,) int32 filled slots and over its new rows, which `append` has already written (ops.attention_extend_paged)."""
-        return ops.attention_extend_paged(q, self.k[li], self.v[li], table, len0, H, Tn, max_len0, scale, ws=ws, out=out)
+        len0 (n,) int32 filled slots and over its new rows, which `append` has already written (ops.attention_extend_paged, ops.attention_extend_paged_mxfp4kv)."""
+        return self._fmt.extend(q, *(t[li] for t in self._fmt.pools), table, len0, H, Tn, max_len0, scale, ws=ws, out=out)
 
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for layers in (self.k, self.v) for t in layers)
+        return sum(t.numel() * t.element_size() for layers in self._fmt.pools for t in layers)
 
     def extend_workspace(self, n: int, Tn: int, H: int, max_len0: int) -> torch.Tensor:
         """The paged extend attention's fp32 partials for n sequences of Tn new rows behind at most max_len0 slots, sized by the library's rule."""
-        need = ops.attention_extend_paged_workspace(n, Tn, H, self.Dh, max_len0, self.Hkv, self.dtype)
+        need = self._fmt.extend_ws(n, Tn, H, self.Dh, max_len0, self.Hkv, self.dtype)
         if self._ws_extend is None or self._ws_extend.numel() < need:
             self._ws_extend = torch.empty(max(need, 1), dtype=torch.float32, device=self.lens.device)
         return self._ws_extend
 
     def workspace(self, H: int) -> torch.Tensor:
         """The decode attention's fp32 partials, sized once for the longest sequence a table row can describe."""
-        need = ops.attention_decode_paged_workspace(self.rows, H, self.Dh, self.max_pages_per_seq * ops.KV_PAGE)
+        need = self._fmt.decode_ws(self.rows, H, self.Dh, self.max_pages_per_seq * ops.KV_PAGE)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1), dtype=torch.float32, device=self.lens.device)
         return self._ws
@@ -1035,11 +1088,17 @@ class ContinuousBatcher:
     when the last of them leaves.  `prefix_stats`: registered, hits (admissions behind a prefix), slots_shared (prompt rows that were not recomputed,
     summed over hits).
 
-    Greedy over the native element type only; refused by name (NotImplementedError): sampler=, beams=, draft=, processors=, prefill_chunk= and a
-    quantised kv_cache=."""
+    `cache=`: a fresh `PagedKVCache` the caller built for this model - `PagedKVCache.for_model(lm.model, rows, num_pages, max_pages_per_seq,
+    kv_format="mxfp4")` for MXFP4 pages - in the place of the native pools the batcher would build.  `num_pages` / `max_pages_per_seq` must then equal
+    the cache's or be omitted; admission, prefixes and release run unchanged over whichever format the cache has.  Over MXFP4 pages a request's
+    tokens are those of `lm.generate(..., kv_cache="mxfp4")` for that request alone, a prefixed request's those of the same call with
+    `prefill_chunk=Ps`: the paged kernels run the dense MXFP4 kernels' arithmetic on the same partition of the keys.
 
-    def __init__(self, lm, rows: int, num_pages: int, max_pages_per_seq: Optional[int] = None, eos_token_id=None, pad_token_id=None, *, sampler=None,
-                 beams=None, draft=None, processors=None, prefill_chunk=None, kv_cache: str = "native"):
+    Greedy only; refused by name (NotImplementedError): sampler=, beams=, draft=, processors=, prefill_chunk= and a quantised kv_cache= string
+    (quantised pages come in through `cache=`)."""
+
+    def __init__(self, lm, rows: int, num_pages: Optional[int] = None, max_pages_per_seq: Optional[int] = None, eos_token_id=None, pad_token_id=None, *,
+                 sampler=None, beams=None, draft=None, processors=None, prefill_chunk=None, kv_cache: str = "native", cache: Optional[PagedKVCache] = None):
         who = "ContinuousBatcher"
         for name, given, why in (("sampler=", sampler is not None, "the batcher selects by argmax"),
                                  ("beams=", beams is not None, "a beam's pages would have to be shared between rows"),
@@ -1050,11 +1109,24 @@ class ContinuousBatcher:
                 raise NotImplementedError(f"{who}: {name} is not implemented over the paged cache ({why}); use SetokimLlamaPrefill.generate")
         if kv_cache != "native":
             if kv_cache in KVCache.FORMATS:
-                raise NotImplementedError(f"{who}: kv_cache={kv_cache!r} is not implemented over the paged cache (quantised rows in pages are a follow-up); "
-                                          "the pools hold the model's element type")
+                raise NotImplementedError(f"{who}: kv_cache={kv_cache!r} is not implemented over the paged cache: the pools the batcher builds hold the "
+                                          "model's element type; for MXFP4 pages pass cache=PagedKVCache.for_model(lm.model, rows, num_pages, "
+                                          "max_pages_per_seq, kv_format=\"mxfp4\")")
             raise ValueError(f"{who}: kv_cache={kv_cache!r} is not one of 'native', 'fp8', 'mxfp4'")
         lm.model._refuse_unmerged(who)
         _count(rows, "rows", who)
+        if cache is not None:
+            if not isinstance(cache, PagedKVCache):
+                raise TypeError(f"{who}: cache= must be a PagedKVCache, got {type(cache).__name__}")
+            for name, given, has in (("rows", rows, cache.rows), ("num_pages", num_pages, cache.num_pages),
+                                     ("max_pages_per_seq", max_pages_per_seq, cache.max_pages_per_seq)):
+                if given is not None and (isinstance(given, bool) or given != has):
+                    raise ValueError(f"{who}: {name}={given!r} conflicts with cache= ({name} = {has}); omit it or pass the cache's value")
+            if not cache.fresh:
+                raise ValueError(f"{who}: cache= must be fresh - every row idle and every page free - but {cache.num_pages - cache.pages_free} of its "
+                                 f"{cache.num_pages} pages are in use and its lengths are {cache.lens_host}")
+            lm.model._check_paged(who, cache)
+            num_pages, max_pages_per_seq = cache.num_pages, cache.max_pages_per_seq
         _count(num_pages, "num_pages", who)
         if max_pages_per_seq is None:
             max_pages_per_seq = num_pages
@@ -1062,7 +1134,7 @@ class ContinuousBatcher:
         self.lm, self.rows = lm, rows
         self.w_lm, self.w_e = lm.lm_head.weight.detach().contiguous(), lm.model.embed_tokens.weight.detach().contiguous()
         self.device = self.w_lm.device
-        self.cache = PagedKVCache.for_model(lm.model, rows, num_pages, max_pages_per_seq, self.device)
+        self.cache = cache if cache is not None else PagedKVCache.for_model(lm.model, rows, num_pages, max_pages_per_seq, self.device)
         self.eos_ids = None if eos_token_id is None else [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
         self.pad_token_id = pad_token_id                                           # (kept for HF's signature: a finished request leaves, nothing is padded)
         self.queue: List[Tuple[int, torch.Tensor, int, Optional[PrefixHandle]]] = []      # (ticket, prompt, max_new, prefix) in submit order

@@ -565,7 +565,7 @@ class LlamaModel(PackCacheMixin, nn.Module):
 
         def attend(li, qkv):
             nonlocal o
-            ops.kv_append_paged(qkv, cache.k[li], cache.v[li], table, len0, Tn, H)
+            cache.append(li, qkv, Tn, H, len0, table=table)
             o = cache.extend_attend(li, qkv, H, Tn, max_len0, scale, ws, o, table, len0)
             return o
         y = self._run_layers(x, pk["layers"], pos, attend)

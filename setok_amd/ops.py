@@ -997,6 +997,77 @@ def attention_extend_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v
     return out
 
 
+# ---- MXFP4 pools of the paged cache (csrc/attn_paged.hip, csrc/attn_extend_paged.hip; include/setok_hip.h, "Paged MXFP4 KV cache") ---------------
+PAGED_MXFP4_HEAD_DIMS = (32, 64, 128)             # the head dims with a lane layout over nibble rows: what the paged append and decode entries take
+
+
+def _paged_mxfp4_shapes(k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, block_table: Tensor, per_seq: Tensor) -> Tuple[int, int, int, int, int]:
+    num_pages, Hkv, page, Dh = _mxfp4kv_shapes(k_q, k_s, v_q, v_s)         # the dense cache's rules with a page where a sequence was
+    assert page == KV_PAGE
+    B, max_pages = block_table.shape
+    assert block_table.dtype == torch.int32 and per_seq.dtype == torch.int32 and per_seq.shape == (B,)
+    return num_pages, Hkv, Dh, B, max_pages
+
+
+def kv_append_paged_mxfp4(qkv: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, block_table: Tensor, slot0: Tensor, T: int, H: int) -> None:
+    """kv_append_paged into MXFP4 pools: rows b*T + t of qkv are quantised by kv_append_mxfp4's rule into slot slot0[b] + t of sequence b - page
+    block_table[b][slot // KV_PAGE], row slot % KV_PAGE of k_q / v_q (num_pages, Hkv, KV_PAGE, Dh/2) and k_s / v_s (num_pages, Hkv, KV_PAGE, Dh/32),
+    all uint8.  A sequence with slot0[b] < 0 is skipped; a table entry outside [0, num_pages) is no page (nothing is written)."""
+    num_pages, Hkv, Dh, B, max_pages = _paged_mxfp4_shapes(k_q, k_s, v_q, v_s, block_table, slot0)
+    assert qkv.shape == (B * T, (H + 2 * Hkv) * Dh) and qkv.is_contiguous()
+    _lib.call("setok_kv_append_paged_mxfp4", _stream(), _code(qkv.dtype), _p(qkv), _p(k_q), _p(k_s), _p(v_q), _p(v_s), _p(block_table), max_pages,
+              num_pages, _p(slot0), B, T, H, Hkv, Dh)
+
+
+def attention_decode_paged_mxfp4kv_workspace(B: int, H: int, Dh: int, max_len: int) -> int:
+    """Floats of workspace setok_attention_decode_gqa_paged_mxfp4kv needs for lengths up to `max_len`: a partial per DECODE_CHUNK_MXFP4KV slots."""
+    return B * H * ((max_len + DECODE_CHUNK_MXFP4KV - 1) // DECODE_CHUNK_MXFP4KV) * (Dh + 2)
+
+
+def attention_decode_paged_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, block_table: Tensor, lens: Tensor, H: int,
+                                   max_len: int, scale: float, ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """attention_decode_paged over MXFP4 pools; q and the result in q.dtype.  A sequence's bits are attention_decode_mxfp4kv's at B = 1 on its
+    gathered slots."""
+    num_pages, Hkv, Dh, B, max_pages = _paged_mxfp4_shapes(k_q, k_s, v_q, v_s, block_table, lens)
+    assert q.shape[0] == B and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    need = attention_decode_paged_mxfp4kv_workspace(B, H, Dh, max_len)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_decode_gqa_paged_mxfp4kv", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_q), _p(k_s), _p(v_q), _p(v_s),
+              _p(block_table), max_pages, num_pages, _p(lens), _p(out), B, H, Hkv, Dh, max_len, scale, _p(ws), ws.numel())
+    return out
+
+
+def attention_extend_paged_mxfp4kv_workspace(B: int, Tn: int, H: int, Dh: int, max_len0: int) -> int:
+    """Floats of workspace setok_attention_extend_gqa_paged_mxfp4kv needs: attention_extend_mxfp4kv_workspace's rule at len0 = max_len0."""
+    return attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, max_len0)
+
+
+def attention_extend_paged_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, block_table: Tensor, len0: Tensor, H: int, Tn: int,
+                                   max_len0: int, scale: float, ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """attention_extend_paged over MXFP4 pools, which already hold the new rows' quantised keys / values in slots [len0[b], len0[b] + Tn)
+    (kv_append_paged_mxfp4 with slot0 = len0).  The functional path, for every head dim that is a multiple of 32; a sequence's bits are
+    attention_extend_mxfp4kv's at B = 1 on its gathered slots."""
+    num_pages, Hkv, Dh, B, max_pages = _paged_mxfp4_shapes(k_q, k_s, v_q, v_s, block_table, len0)
+    assert Tn >= 1 and 0 <= max_len0 and max_len0 + Tn <= max_pages * KV_PAGE, \
+        f"attention_extend_paged_mxfp4kv: slots [{max_len0}, {max_len0} + {Tn}) lie beyond the table ({max_pages} pages)"
+    assert q.shape[0] == B * Tn and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
+    need = attention_extend_paged_mxfp4kv_workspace(B, Tn, H, Dh, max_len0)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need
+    if out is None:
+        out = torch.empty((B * Tn, H * Dh), dtype=q.dtype, device=q.device)
+    assert out.shape == (B * Tn, H * Dh) and out.dtype == q.dtype
+    _lib.call("setok_attention_extend_gqa_paged_mxfp4kv", _stream(), _code(q.dtype), q.data_ptr(), q.stride(0), _p(k_q), _p(k_s), _p(v_q), _p(v_s),
+              _p(block_table), max_pages, num_pages, _p(len0), _p(out), B, Tn, H, Hkv, Dh, max_len0, scale, _p(ws), ws.numel())
+    return out
+
+
 def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """int64 (rows,): the lowest index of each row's maximum; x (rows, V) with any row stride."""
     rows, V = x.shape
