@@ -317,7 +317,7 @@ int setok_splice_lengths(void* stream, const int64_t* input_ids, const uint8_t* 
  * | INT32_MIN for a zero padding row; new_labels (NULL iff labels is NULL, :341-342): the token's label, ignore_index on
  * image rows (:293) and padding (:319), target_token_index mapped to ignore_index (:344); new_mask (uint8, optional);
  * new_position_ids (int64, optional; 0..len-1 inside the kept range, 0 in the padding, :321,337).  left_pad selects
- * tokenizer_padding_side == "left" (:324-330). */
+ * tokenizer_padding_side == "left" (:324-330).  max_len = 0 (no sequence keeps anything): nothing is written and the outputs may be NULL. */
 int setok_splice_plan(void* stream, const int64_t* input_ids, const uint8_t* attention_mask, const int64_t* labels, int B, int T,
                       int64_t image_token_index, int64_t ignore_index, int64_t target_token_index,
                       const int32_t* img_offsets, const int32_t* seq_len, const int32_t* img_start, int max_len, int left_pad,
@@ -327,7 +327,8 @@ int setok_splice_plan(void* stream, const int64_t* input_ids, const uint8_t* att
  * fused with the concatenations and the zero padding (:296-303, 324-333).  D * sizeof(dtype) must be a multiple of 16.
  * A src the operands cannot serve (>= vocab; an image-token row >= image_token_rows or with image_tokens == NULL, e.g. an
  * IMAGE_TOKEN_INDEX in a text-only call) is never turned into an address: the row is zero-filled and, with `status` (int32[2], optional,
- * device), status[0] = 1 and status[1] = the first such row — where the reference's embed_tokens raises IndexError (:273). */
+ * device), status[0] = 1 and status[1] = the first such row — where the reference's embed_tokens raises IndexError (:273).
+ * rows = 0: src and out may be NULL (status is still initialised). */
 int setok_splice_rows(void* stream, int dtype, const int32_t* src, const void* embed_table, int vocab, const void* image_tokens,
                       int64_t image_token_rows, void* out, int64_t rows, int D, int32_t* status);
 

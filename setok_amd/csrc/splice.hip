@@ -222,10 +222,10 @@ extern "C" int setok_splice_plan(void* stream, const int64_t* input_ids, const u
                                  int B, int T, int64_t image_token_index, int64_t ignore_index, int64_t target_token_index,
                                  const int32_t* img_offsets, const int32_t* seq_len, const int32_t* img_start, int max_len,
                                  int left_pad, int32_t* src, int64_t* new_labels, uint8_t* new_mask, int64_t* new_position_ids) {
+    SETOK_CHECK_ARG(B > 0 && T > 0 && max_len >= 0, "setok_splice_plan: bad shape");
+    if (max_len == 0) return SETOK_OK;                              // no sequence keeps anything: the outputs are empty, and an empty buffer's address is null
     SETOK_CHECK_ARG(input_ids && img_offsets && seq_len && img_start && src, "setok_splice_plan: null operand");
     SETOK_CHECK_ARG((labels == nullptr) == (new_labels == nullptr), "setok_splice_plan: labels and new_labels go together");
-    SETOK_CHECK_ARG(B > 0 && T > 0 && max_len >= 0, "setok_splice_plan: bad shape");
-    if (max_len == 0) return SETOK_OK;
     splice_plan_kernel<<<B, 256, 0, (hipStream_t)stream>>>(input_ids, attention_mask, labels, T, image_token_index, ignore_index,
                                                           target_token_index, img_offsets, seq_len, img_start, max_len, left_pad, src,
                                                           new_labels, new_mask, new_position_ids);
@@ -235,7 +235,7 @@ extern "C" int setok_splice_plan(void* stream, const int64_t* input_ids, const u
 
 extern "C" int setok_splice_rows(void* stream, int dtype, const int32_t* src, const void* embed_table, int vocab,
                                  const void* image_tokens, int64_t image_token_rows, void* out, int64_t rows, int D, int32_t* status) {
-    SETOK_CHECK_ARG(src && embed_table && out, "setok_splice_rows: null operand");
+    SETOK_CHECK_ARG(embed_table && (rows == 0 || (src && out)), "setok_splice_rows: null operand");      // (rows == 0: empty buffers, null addresses)
     SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_splice_rows: bad dtype %d", dtype);
     const int row_bytes = D * (dtype == SETOK_BF16 ? 2 : 4);
     SETOK_CHECK_ARG(rows >= 0 && D > 0 && row_bytes % 16 == 0 && vocab > 0 && image_token_rows >= 0, "setok_splice_rows: bad shape rows=%lld D=%d", (long long)rows, D);
@@ -252,7 +252,7 @@ extern "C" int setok_splice_rows(void* stream, int dtype, const int32_t* src, co
 
 extern "C" int setok_splice_rows_bwd(void* stream, int dtype, const int32_t* src, const void* d_out, int64_t rows, int D,
                                      void* d_image_tokens, int64_t image_token_rows, float* d_embed, int vocab) {
-    SETOK_CHECK_ARG(src && d_out, "setok_splice_rows_bwd: null operand");
+    SETOK_CHECK_ARG(rows == 0 || (src && d_out), "setok_splice_rows_bwd: null operand");
     SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_splice_rows_bwd: bad dtype %d", dtype);
     const int es = dtype == SETOK_BF16 ? 2 : 4;
     SETOK_CHECK_ARG(rows >= 0 && D > 0 && (D * es) % 16 == 0 && image_token_rows >= 0 && (!d_embed || vocab > 0), "setok_splice_rows_bwd: bad shape rows=%lld D=%d", (long long)rows, D);
