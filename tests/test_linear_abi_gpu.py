@@ -80,78 +80,10 @@ def _assert_only_the_window_changed(buf, before, M, W):
 
 
 # ---------------------------------------------------------------------------------------------
-# the dispatch rules, restated (gemm.hip: bf16_kernel; gemm_persist.hip: tail_shape_for, pp_takes, setok_gemm_persist_bf16)
+# the dispatch rules, restated (gemm.hip: bf16_kernel; gemm_persist.hip: tail_shape_for, pp_takes, setok_gemm_persist_bf16): tests/gemm_dispatch.py,
+# shared with test_gemm_programs_gpu.py
 # ---------------------------------------------------------------------------------------------
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def _ncu():
-    return _lib.device_info()[1]
-
-
-def _tail_shape(M, N, ncu, whole):
-    t64 = _cdiv(M, 64) * _cdiv(N, 64)
-    if whole and N % 64 == 0 and t64 > ncu:
-        main, rem = (M // 128) * (N // 64), M % 128
-        if ncu // 2 < main <= ncu and (rem == 0 or _cdiv(rem, 32) * (N // 32) <= main):
-            return (128, 64, 6)
-    if t64 * 4 <= ncu and N % 32 == 0:
-        return (32, 32, 8)
-    if N % 32 == 0 and _cdiv(M, 32) * _cdiv(N, 32) <= 2 * ncu:
-        return (32, 32, 8)
-    if t64 * 2 <= ncu and N % 32 == 0:
-        return (64, 32, 8)                      # (unreachable: see the module's docstring)
-    if ncu < t64 <= 2 * ncu:
-        return (64, 64, 4)
-    return (64, 64, 8)
-
-
-def _persist_class(M, N, K, ncu):
-    tilesM, tilesN = _cdiv(M, 256), _cdiv(N, 256)
-    T = tilesM * tilesN
-    r, p = T % ncu, 0
-    if T > ncu and r != 0 and r % tilesN == 0 and r // tilesN <= 2:
-        p = r // tilesN
-    if p == 0 and M % 256 != 0 and tilesM > 1 and N % 256 == 0:
-        p = 1
-    tm = tilesM - p
-    main_rows = min(tm * 256, M)
-    name = "pp" if (N % 256 == 0 and K >= 128 and main_rows % 256 == 0) else "persist"
-    if p == 0:
-        return name
-    rem = M - tm * 256
-    if name == "pp":
-        sh = _tail_shape(rem, N, ncu, False)
-        grid = min(tm * tilesN, ncu)
-        shape = sh[0] if sh[0] == sh[1] and sh[2] == 8 else 64
-        if _cdiv(rem, shape) * (N // shape) > grid:
-            shape = 64
-        if _cdiv(rem, shape) * (N // shape) <= grid:
-            return "pp+rem"                     # the remainder rows inside the ping-pong launch
-    return name + "+tail"                       # ... as a small-tile launch of their own
-
-
-def _kernel_class(M, N, K, ldc, ncu, out16=True, batch=1, ln=False, plain=False):
-    """The kernel a 16-bit-input problem goes to.  `plain`: no bias / activation / residual (what the fp32-out batched persistent kernel needs)."""
-    tiles = _cdiv(M, 256) * _cdiv(N, 256)
-    if out16 and batch == 1 and N % 64 == 0 and ldc % 8 == 0:
-        if K >= 192 and tiles >= 90:
-            return _persist_class(M, N, K, ncu)
-        return "small %dx%d/%d" % _tail_shape(M, N, ncu, not ln)
-    if not out16 and plain and N % 64 == 0 and K >= 192 and ldc % 4 == 0 and tiles * batch >= 96:
-        return "f32b"
-    return "tile128"
-
-
-def _rows_reaching(want, M, N, K, ncu, ln=False):
-    """`M` reaches class `want` on 256 CUs; on a device with another CU count: the first row count the rules send there."""
-    if _kernel_class(M, N, K, N, ncu, ln=ln) == want:
-        return M
-    for m in range(1, 1 << 15):
-        if _kernel_class(m, N, K, N, ncu, ln=ln) == want:
-            return m
-    pytest.fail(f"no row count reaches {want} at N={N} K={K} on {ncu} CUs")
+from gemm_dispatch import _cdiv, _kernel_class, _ncu, _persist_class, _rows_reaching, _tail_shape  # noqa: E402,F401
 
 
 # ---------------------------------------------------------------------------------------------
