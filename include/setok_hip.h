@@ -910,15 +910,24 @@ int setok_attention_decode_gqa_mxfp4kv(void* stream, int dtype, const void* q, i
                                        int cap, int len, float scale, float* ws, int64_t ws_floats);
 
 /* Floats of workspace setok_attention_extend_gqa_mxfp4kv needs: B * Tn * H * ceil((len0 + Tn) / SETOK_EXTEND_CHUNK) * (Dh + 2), whatever the
- * element type (one partial per chunk; setok_attention_extend_gqa's span rule does not apply).  0 for arguments the call would refuse. */
+ * element type and head dim: one partial per chunk.  The MFMA path (below) partitions as setok_attention_extend_gqa does — a partial per span of
+ * up to SETOK_EXTEND_SPAN chunks — and uses a prefix of these floats; the rule does not follow it.  0 for arguments the call would refuse. */
 int64_t setok_attention_extend_mxfp4kv_workspace(int B, int Tn, int H, int Dh, int len0);
 
 /* setok_attention_extend_gqa over the MXFP4 cache: Tn >= 1 query rows per (sequence, query head) against slots [0, len0 + Tn), which already
  * hold the new rows' quantised keys / values; query i of sequence b counts slot j iff j <= len0 + i and key_mask[b][j] != 0, a query without a
- * counted key gets zeros.  That call's semantics and refusals, with Dh % 32 == 0.  One wave per (query row, query head, chunk of
- * SETOK_EXTEND_CHUNK slots), a key per lane, then the shared merge in chunk order, for every head dim and element type: this is a FUNCTIONAL
- * path — it reads the cache once per query row and query head and uses no MFMA; an MFMA extend over nibbles is a follow-up (DESIGN.md §7 f16 has
- * the measurements that say where it stops being worth it).  q, k_q and v_q 16-byte aligned. */
+ * counted key gets zeros.  That call's semantics and refusals, with Dh % 32 == 0, and that call's dispatch:
+ *   - the 16-bit type at Dh == 128: the MFMA kernel of setok_attention_extend_gqa — its partition into tiles, chunks and spans, its online
+ *     softmax, its merge — whose 32-key tiles are converted from nibbles on their way to LDS (v_cvt_scalef32_pk_{bf16,f16}_fp4, the scale
+ *     applied).  THE OUTPUT BITS ARE THOSE OF setok_attention_extend_gqa on the same q, key_mask, len0 and Tn over caches that hold K', V',
+ *     provided K', V' are representable in the element type.  Every row setok_kv_append_mxfp4 writes is (block exponents in [-13, 13]: exact in
+ *     bf16 and fp16); a hand-made scale byte outside that range is the caller's business here — the converter rounds or overflows as the type
+ *     does — while the path below computes such a block in fp32.  Also needs Hkv * ceil((H / Hkv) * Tn / 128) <= 65535 (the launch grid);
+ *   - everything else (fp32, the other head dims): one wave per (query row, query head, chunk of SETOK_EXTEND_CHUNK slots), a key per lane, then
+ *     the shared merge in chunk order — a functional path that reads the cache once per query row and query head and uses no MFMA, as the native
+ *     call's is for these shapes.
+ * A slot that counts for no query may hold any nibbles and any scale byte (0xFF, the NaN block, included).  DESIGN.md §7 f16 has the
+ * measurements.  q, k_q and v_q 16-byte aligned. */
 int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,
                                        const uint8_t* v_q, const uint8_t* v_s, const uint8_t* key_mask, void* out, int B, int Tn, int H, int Hkv,
                                        int Dh, int cap, int len0, float scale, float* workspace, int64_t workspace_floats);
@@ -1018,13 +1027,17 @@ int setok_attention_decode_gqa_paged_mxfp4kv(void* stream, int dtype, const void
                                              int64_t ws_floats);
 
 /* Floats of workspace setok_attention_extend_gqa_paged_mxfp4kv needs: setok_attention_extend_mxfp4kv_workspace's rule at len0 = max_len0,
- * B * Tn * H * ceil((max_len0 + Tn) / SETOK_EXTEND_CHUNK) * (Dh + 2). */
+ * B * Tn * H * ceil((max_len0 + Tn) / SETOK_EXTEND_CHUNK) * (Dh + 2) (the MFMA path uses a prefix of it, as the dense call's does). */
 int64_t setok_attention_extend_paged_mxfp4kv_workspace(int B, int Tn, int H, int Dh, int max_len0);
 
 /* setok_attention_extend_gqa_paged over MXFP4 pools, with that call's meaning of every argument (len0[b] per sequence, < 0 idle; "no page";
- * only slots that count are read).  One wave per (query row, query head, chunk of SETOK_EXTEND_CHUNK = 256 slots, two pages), a key per lane with
- * its page looked up per key, then the merge in chunk order, for every Dh % 32 == 0 and element type: this is the FUNCTIONAL path, as
- * setok_attention_extend_gqa_mxfp4kv is - an MFMA extend over nibble rows is not built, dense or paged.  Sequence b's output bits are those of
+ * only slots that count are read), and setok_attention_extend_gqa_mxfp4kv's dispatch.  The 16-bit type at Dh == 128: the MFMA kernel of
+ * setok_attention_extend_gqa_paged — one table lookup per 32-key tile, a tile without a page is not staged — with its tiles converted from
+ * nibbles on their way to LDS; THE OUTPUT BITS ARE THOSE OF setok_attention_extend_gqa_paged on the same q, block_table, len0 and Tn over pools
+ * that hold K', V', provided K', V' are representable in the element type (every row setok_kv_append_paged_mxfp4 writes is; a hand-made scale
+ * byte outside [-13, 13] + 127 is the caller's business); needs Hkv * ceil((H / Hkv) * Tn / 128) <= 65535.  Everything else (fp32, the other
+ * Dh % 32 == 0): one wave per (query row, query head, chunk of SETOK_EXTEND_CHUNK = 256 slots, two pages), a key per lane with its page looked
+ * up per key, then the merge in chunk order — the functional path.  On either path sequence b's output bits are those of
  * setok_attention_extend_gqa_mxfp4kv at B = 1, len0 = len0[b], on its gathered slots under an all-ones mask.  q, k_q and v_q 16-byte aligned,
  * ldq % 8 == 0, ws_floats >= setok_attention_extend_paged_mxfp4kv_workspace(...).  B == 0 launches nothing. */
 int setok_attention_extend_gqa_paged_mxfp4kv(void* stream, int dtype, const void* q, int64_t ldq, const uint8_t* k_q, const uint8_t* k_s,

@@ -19,9 +19,15 @@
 // its scores are replaced by selection and its V row is zeroed in LDS before the tile is used (0 * NaN would reach the accumulators otherwise).
 // Everything else (fp32, other head dims) is one wave per (query row, query head, chunk) on a grid (B * Tn, H, chunks): attn_chunk_any_kernel of
 // attn_partials.h, the decode path's fallback, with the row's own limit len0 + i + 1.
-//   setok_attention_extend_gqa_mxfp4kv   the same over a cache stored as MXFP4 rows (include/setok_hip.h, "MXFP4 KV cache"): that wave-per-chunk
-//                                        kernel over the KvMxfp4 format for every head dim and element type — the functional path; an MFMA
-//                                        kernel over nibbles is a follow-up
+//   setok_attention_extend_gqa_mxfp4kv   the same over a cache stored as MXFP4 rows (include/setok_hip.h, "MXFP4 KV cache"), with the native call's
+//                                        dispatch.  Head dim 128 in the 16-bit type: the MFMA kernel, the same text, under the staging policy
+//                                        StageMx4 (attn_partials.h) — a thread loads MX blocks (16 bytes of nibbles + the e8m0 byte) of tile
+//                                        kt + 1 into registers before tile kt's MFMAs and, after them, converts them with the hardware converter
+//                                        (v_cvt_scalef32_pk_*_fp4: exact, the scale applied) and writes the 64 bytes into the LDS image the native
+//                                        staging fills by LDS-DMA; the V rows of slots that cannot count are written as zeros there, which saves
+//                                        the native staging's extra pass and barrier.  Everything from S^T = K Q^T to the partial is the native
+//                                        kernel's, operation for operation: the output bits are setok_attention_extend_gqa's over a cache that
+//                                        holds K', V' (DESIGN.md §7 f16).  Everything else: that wave-per-chunk kernel over the KvMxfp4 format.
 #include "common.h"
 #include "lds_mma.h"
 #include "attn_partials.h"
@@ -40,10 +46,11 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 // ---- 16-bit MFMA kernel, head dim 128 -------------------------------------------------------------------------------------------------------------
 // grid (spans, Hkv * mblocks, B), NW waves of 32 M rows each (mblocks = ceil(G * Tn / (32 NW))); NW = 1 serves a verify-shaped call (G * Tn <= 32).
 // A workgroup owns `span` slots (EXT_CHUNK, or XSPAN chunks) counted from slot 0 and writes one partial per row.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ kc,
-                                                              const bf16* __restrict__ vc, const uint8_t* __restrict__ kmask, float* __restrict__ ws,
-                                                              int Tn, int H, int Hkv, int cap, int len0, int span, float scale_log2e) {
+// S (attn_partials.h): how a tile reaches LDS — StageDma from native rows kc / vc, StageMx4 from MXFP4 rows (nibbles, scales) through registers.
+template <int NW, typename S>
+__global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __restrict__ q, int64_t ldq, typename S::Rows kc, typename S::Rows vc,
+                                                              const uint8_t* __restrict__ kmask, float* __restrict__ ws, int Tn, int H, int Hkv, int cap,
+                                                              int len0, int span, float scale_log2e) {
     constexpr int NT = NW * 64, PP = (XT * 16) / NT;                     // a tile is 512 pieces of 16 B: PP per thread
     __shared__ __attribute__((aligned(16))) char Ks[2][XT * XROW];       // K tile, 16-byte slots XOR-swizzled by (row & 15)
     __shared__ __attribute__((aligned(16))) char Vs[2][XT * XROW];       // V tile, row-major (hardware-transposing reads)
@@ -88,43 +95,70 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __rest
         koffs[u] = (unsigned)(row * XROW + ((pc ^ (row & 15)) << 4));    // physical slot pc of a row holds logical piece pc ^ (row & 15)
         voffs[u] = (unsigned)(row * XROW + (pc << 4));
     }
+    // the tile's slots that can count at all, as a 32-bit set (bit j: slot k0 + j lies below `top` and is attended): the same in every wave
+    auto countable = [&](int k0) { return (unsigned)__ballot(lane < 32 && k0 + lane < top && km[min(k0 + lane, top - 1)] != 0); };
+    Mx4Tile<NT> tile = {};                                               // (StageMx4) the requested tile in registers, the mask byte of its slot
+    unsigned kmb = 0u, kb_next = 0u;                                     // (lane & 31) as it was loaded, and — from commit() on — its set of slots
     auto stage = [&](int k0, int buf) {                                  // K and V rows [k0, k0 + 32) of the (sequence, key / value head) -> LDS buffer buf
-        if (k0 + XT <= top) {                                            // (uniform) all 32 slots lie below `top`
-            const char* kb = reinterpret_cast<const char*>(kc + (rowbase + k0) * XD);
-            const char* vb = reinterpret_cast<const char*>(vc + (rowbase + k0) * XD);
+        if constexpr (S::MX4) {                                          // requested into registers; commit() puts them into the image
+            tile.request(kc, vc, rowbase + k0, min(XT, top - k0) - 1, tid);              // k0 < top always (k0 < kend <= lim_wg + 1 <= top)
+            kmb = km[min(k0 + (lane & 31), top - 1)];                    // no use before commit(): nothing waits for these loads until then
+        } else {
+            if (k0 + XT <= top) {                                        // (uniform) all 32 slots lie below `top`
+                const char* kb = reinterpret_cast<const char*>(kc + (rowbase + k0) * XD);
+                const char* vb = reinterpret_cast<const char*>(vc + (rowbase + k0) * XD);
 #pragma unroll
-            for (int u = 0; u < PP; ++u) {
-                lds_dma16_sbase(kb, koffs[u], klds + buf * (XT * XROW) + u * (NT * 16));
-                lds_dma16_sbase(vb, voffs[u], vlds + buf * (XT * XROW) + u * (NT * 16));
+                for (int u = 0; u < PP; ++u) {
+                    lds_dma16_sbase(kb, koffs[u], klds + buf * (XT * XROW) + u * (NT * 16));
+                    lds_dma16_sbase(vb, voffs[u], vlds + buf * (XT * XROW) + u * (NT * 16));
+                }
+                return;
             }
-            return;
-        }
 #pragma unroll
-        for (int u = 0; u < PP; ++u) {                                   // a slot at or above `top` is read as slot top - 1 (in bounds) and discarded
-            const int p = u * NT + tid, row = p >> 4, pc = p & 15;
-            const int64_t src = (rowbase + min(k0 + row, top - 1)) * XD;
-            lds_dma16(kc + src + ((pc ^ (row & 15)) << 3), klds + buf * (XT * XROW) + u * (NT * 16));
-            lds_dma16(vc + src + (pc << 3), vlds + buf * (XT * XROW) + u * (NT * 16));
+            for (int u = 0; u < PP; ++u) {                               // a slot at or above `top` is read as slot top - 1 (in bounds) and discarded
+                const int p = u * NT + tid, row = p >> 4, pc = p & 15;
+                const int64_t src = (rowbase + min(k0 + row, top - 1)) * XD;
+                lds_dma16(kc + src + ((pc ^ (row & 15)) << 3), klds + buf * (XT * XROW) + u * (NT * 16));
+                lds_dma16(vc + src + (pc << 3), vlds + buf * (XT * XROW) + u * (NT * 16));
+            }
         }
     };
-    if (nkt > 0) stage(kbeg, 0);
+    auto commit = [&](int k0, int buf) {                                 // (StageMx4) the requested tile k0 -> LDS buffer buf, the V rows of dead slots as zeros
+        if constexpr (S::MX4) {
+            kb_next = (unsigned)__ballot(lane < 32 && k0 + lane < top && kmb != 0u);     // countable(k0)
+            tile.commit(&Ks[buf][0], &Vs[buf][0], kb_next, true, tid);
+        }
+    };
+    if (nkt > 0) { stage(kbeg, 0); commit(kbeg, 0); }
+    // (StageMx4) vmcnt(0), as an instruction the compiler's own wait counting sees: q has arrived on every path into the loop, so no wait for a q
+    // fragment inside it also waits for the tile loads that were just requested.
+    if constexpr (S::MX4) __builtin_amdgcn_s_waitcnt(0x0f70);
     for (int kt = 0; kt < nkt; ++kt) {
         const int buf = kt & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // this thread's pieces of tile kt
+        if constexpr (!S::MX4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this thread's pieces of tile kt (StageMx4: the barrier waits for its LDS writes)
         __syncthreads();                                                 // everyone's; everyone is done with the other buffer
         const int k0 = kbeg + kt * XT;
-        if (kt + 1 < nkt) stage(k0 + XT, buf ^ 1);
-        // the tile's slots that can count at all, as a 32-bit set (bit j: slot k0 + j lies below `top` and is attended): the same in every wave
-        const unsigned kbits = (unsigned)__ballot(lane < 32 && k0 + lane < top && km[min(k0 + lane, top - 1)] != 0);
-        if (kbits != 0xffffffffu) {                                      // (workgroup-uniform) zero the V rows of the other slots: they may hold anything
+        const unsigned kb_cur = kb_next;                                 // (StageMx4) this tile's set, found when it was requested
+        const bool more = kt + 1 < nkt;
+        if (more) stage(k0 + XT, buf ^ 1);
+        unsigned kbits;
+        if constexpr (S::MX4) {
+            kbits = kb_cur;                                              // commit() wrote zeros for the V rows of the other slots
+        } else {
+            kbits = countable(k0);
+            if (kbits != 0xffffffffu) {                                  // (workgroup-uniform) zero the V rows of the other slots: they may hold anything
 #pragma unroll
-            for (int u = 0; u < PP; ++u) {
-                const int p = u * NT + tid;
-                if (!((kbits >> (p >> 4)) & 1u)) *reinterpret_cast<f32x4*>(&Vs[buf][p * 16]) = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int u = 0; u < PP; ++u) {
+                    const int p = u * NT + tid;
+                    if (!((kbits >> (p >> 4)) & 1u)) *reinterpret_cast<f32x4*>(&Vs[buf][p * 16]) = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                __syncthreads();
             }
-            __syncthreads();
         }
-        if (!live || k0 > lim_hi) continue;                              // wave-uniform: no rows, or the whole tile lies in this wave's future
+        if (!live || k0 > lim_hi) {                                      // wave-uniform: no rows, or the whole tile lies in this wave's future
+            if (more) commit(k0 + XT, buf ^ 1);
+            continue;
+        }
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
@@ -179,6 +213,7 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __rest
                 o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(va, va + 8 * XROW), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
             }
         }
+        if (more) commit(k0 + XT, buf ^ 1);                                       // after this tile's MFMAs: the loads had their time
     }
     // the chunk's partial of every row: [max (natural-log units, what the merge rescales by), sum, 128 accumulators]; a row that counted no slot of the
     // chunk writes (-inf, 0, zeros)
@@ -200,19 +235,22 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16* __rest
 
 static_assert(XD == 128 && XSPAN * EXT_CHUNK == SETOK_EXTEND_SPAN * SETOK_EXTEND_CHUNK, "extend_span (attn_partials.h) states this kernel's span rule");
 
+// The MFMA kernel's launch for either staging: NW = 1 serves G * Tn <= 32 stacked rows, NW = 4 everything else; `nch` partials per row.
+template <typename S>
+void launch_extend_mfma(hipStream_t s, const bf16* q, int64_t ldq, typename S::Rows kc, typename S::Rows vc, const uint8_t* km, float* ws, int B, int Tn,
+                        int H, int Hkv, int cap, int len0, int span, int nch, float scale) {
+    const int MR = (H / Hkv) * Tn;
+    const float sl = scale * 1.44269504088896340736f;
+    if (MR <= 32) attn_extend_kernel<1, S><<<dim3(nch, Hkv, B), 64, 0, s>>>(q, ldq, kc, vc, km, ws, Tn, H, Hkv, cap, len0, span, sl);
+    else attn_extend_kernel<4, S><<<dim3(nch, Hkv * cdiv(MR, 128), B), 256, 0, s>>>(q, ldq, kc, vc, km, ws, Tn, H, Hkv, cap, len0, span, sl);
+}
+
 template <typename T>
 int extend_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, const uint8_t* km, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh,
              int cap, int len0, float scale) {
     const int span = extend_span(sizeof(T) == 2, Tn, H, Hkv, Dh), nch = cdiv(len0 + Tn, span);
     if (sizeof(T) == 2 && Dh == XD) {
-        const int MR = (H / Hkv) * Tn;
-        const float sl = scale * 1.44269504088896340736f;
-        if (MR <= 32)
-            attn_extend_kernel<1><<<dim3(nch, Hkv, B), 64, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, km, ws, Tn, H, Hkv, cap, len0, span,
-                                                                 sl);
-        else
-            attn_extend_kernel<4><<<dim3(nch, Hkv * cdiv(MR, 128), B), 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, km, ws, Tn, H, Hkv,
-                                                                                  cap, len0, span, sl);
+        launch_extend_mfma<StageDma>(s, (const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, km, ws, B, Tn, H, Hkv, cap, len0, span, nch, scale);
     } else {
         attn_chunk_any_kernel<T, KvNative<T>, EXT_CHUNK, true><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, KvNative<T>{kc, vc}, km, ws, Tn, H, Hkv, Dh, cap, len0,
                                                                                                scale);
@@ -223,11 +261,17 @@ int extend_t(hipStream_t s, const T* q, int64_t ldq, const T* kc, const T* vc, c
     return SETOK_OK;
 }
 
+// Over an MXFP4 cache: the native call's dispatch and partition.  16-bit at head dim 128: the MFMA kernel staged from nibbles, `span` slots per
+// partial (a prefix of the workspace, whose rule stays one partial per chunk); everything else the wave-per-chunk kernel, one partial per chunk.
 template <typename T>
 int extend_mxfp4_t(hipStream_t s, const T* q, int64_t ldq, KvMxfp4 kv, const uint8_t* km, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh, int cap,
                    int len0, float scale) {
-    const int nch = cdiv(len0 + Tn, EXT_CHUNK);
-    attn_chunk_any_kernel<T, KvMxfp4, EXT_CHUNK, true><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kv, km, ws, Tn, H, Hkv, Dh, cap, len0, scale);
+    const int span = extend_span(sizeof(T) == 2, Tn, H, Hkv, Dh), nch = cdiv(len0 + Tn, span);
+    if (sizeof(T) == 2 && Dh == XD) {
+        launch_extend_mfma<StageMx4>(s, (const bf16*)q, ldq, kv.k, kv.v, km, ws, B, Tn, H, Hkv, cap, len0, span, nch, scale);
+    } else {
+        attn_chunk_any_kernel<T, KvMxfp4, EXT_CHUNK, true><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kv, km, ws, Tn, H, Hkv, Dh, cap, len0, scale);
+    }
     SETOK_CHECK_LAUNCH("setok_attention_extend_mxfp4kv(chunks)");
     attn_decode_merge_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, nch, H, Dh);
     SETOK_CHECK_LAUNCH("setok_attention_extend_mxfp4kv(merge)");
@@ -284,6 +328,8 @@ extern "C" int setok_attention_extend_gqa_mxfp4kv(void* stream, int dtype, const
                     "setok_attention_extend_mxfp4kv: slots [%d, %d + %d) exceed the cache (len0 + Tn > cap = %d)", len0, len0, Tn, cap);
     SETOK_CHECK_ARG((int64_t)B * Tn <= 0x7fffffffll && cdiv(len0 + Tn, EXT_CHUNK) <= 65535,
                     "setok_attention_extend_mxfp4kv: B=%d Tn=%d H=%d len0=%d exceed the launch grid", B, Tn, H, len0);
+    SETOK_CHECK_ARG(!(dtype == SETOK_BF16 && Dh == XD) || ((int64_t)(H / Hkv) * Tn + 127) / 128 * Hkv <= 65535,
+                    "setok_attention_extend_mxfp4kv: Tn=%d H=%d Hkv=%d exceed the launch grid of the MFMA kernel (Hkv * ceil(G * Tn / 128) <= 65535)", Tn, H, Hkv);
     SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_q) && aligned16(v_q),
                     "setok_attention_extend_mxfp4kv: q rows (stride %lld) and the nibble caches must be 16-byte aligned", (long long)ldq);
     const int64_t need = setok_attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, len0);

@@ -1,8 +1,9 @@
 // attn_extend_paged.hip — extending sequences of the paged KV cache by Tn >= 1 tokens each (include/setok_hip.h, "Paged extend attention"): a request
 // that starts behind a shared prefix, and what a verify pass or a prefill window over pages will need.
 //   setok_attention_extend_gqa_paged          Tn query rows per (sequence, query head) against the sequence's own len0[b] + Tn slots, found through the table
-//   setok_attention_extend_gqa_paged_mxfp4kv  the same over MXFP4 pools (attn_paged.hip): the wave-per-chunk kernel below over the KvMxfp4 format for
-//                                             every Dh % 32 == 0 and element type — the functional path, as the dense MXFP4 extend is; no MFMA over nibbles
+//   setok_attention_extend_gqa_paged_mxfp4kv  the same over MXFP4 pools (attn_paged.hip), with the native call's dispatch: head dim 128 in the 16-bit
+//                                             type is the MFMA kernel below under the staging policy StageMx4 (attn_partials.h; attn_extend.hip says
+//                                             what it does), everything else (every Dh % 32 == 0, fp32) the wave-per-chunk kernel over KvMxfp4
 // Query i of sequence b counts slot j iff j <= len0[b] + i and table[b][j / SETOK_KV_PAGE] is a page; len0[b] < 0 is an idle sequence (zeros).
 //
 // These are attn_extend.hip's two kernels with two things replaced, as attn_decode_paged_kernel did it for decode — where a tile's rows start (a table
@@ -10,7 +11,7 @@
 // and no mask bytes: a page that is "no page" is what a mask that is zero on its 128 slots is to the dense kernel.  The dense kernel's key tiles are
 // 32 slots counted from slot 0, its chunks 256 and its spans 1024, so a tile never straddles a page and chunks and spans are whole pages: the same
 // partition into partials, the same online softmax per tile, the same merge in chunk order (attn_partials.h).  So a sequence's output bits are those
-// of setok_attention_extend_gqa (over MXFP4 pools: of setok_attention_extend_gqa_mxfp4kv, whose chunks are the same 256 slots) at B = 1,
+// of setok_attention_extend_gqa (over MXFP4 pools: of setok_attention_extend_gqa_mxfp4kv, whose partition is the same on either of its paths) at B = 1,
 // len0 = len0[b], on its slots gathered into a dense cache, wherever its pages lie.
 //
 // No address is formed from a page id outside [0, num_pages), nor from a table index at or past max_pages: such a tile is not staged and no key of
@@ -34,11 +35,12 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 // ---- 16-bit MFMA kernel, head dim 128: attn_extend_kernel<NW> over pages ---------------------------------------------------------------------------
 // grid (spans of max_len0 + Tn, Hkv * mblocks, B).  An idle sequence and a span at or above the sequence's own top write nothing: the merge reads
 // neither.  Every other workgroup writes one partial per row, exactly the dense kernel's.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_extend_paged_kernel(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ kp,
-                                                                    const bf16* __restrict__ vp, const int* __restrict__ table, int max_pages,
-                                                                    int num_pages, const int* __restrict__ lens0, float* __restrict__ ws, int Tn, int H,
-                                                                    int Hkv, int span, float scale_log2e) {
+// S (attn_partials.h): how a tile reaches LDS — StageDma from native pools kp / vp, StageMx4 from MXFP4 pools (nibbles, scales) through registers.
+template <int NW, typename S>
+__global__ __launch_bounds__(NW * 64) void attn_extend_paged_kernel(const bf16* __restrict__ q, int64_t ldq, typename S::Rows kp, typename S::Rows vp,
+                                                                    const int* __restrict__ table, int max_pages, int num_pages,
+                                                                    const int* __restrict__ lens0, float* __restrict__ ws, int Tn, int H, int Hkv, int span,
+                                                                    float scale_log2e) {
     constexpr int NT = NW * 64, PP = (XT * 16) / NT;                     // a tile is 512 pieces of 16 B: PP per thread
     __shared__ __attribute__((aligned(16))) char Ks[2][XT * XROW];       // K tile, 16-byte slots XOR-swizzled by (row & 15)
     __shared__ __attribute__((aligned(16))) char Vs[2][XT * XROW];       // V tile, row-major (hardware-transposing reads)
@@ -87,52 +89,81 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_paged_kernel(const bf16* 
     // K and V rows [k0, k0 + 32) of the (sequence, key / value head) -> LDS buffer buf; false, with nothing requested, if the tile's page is no page.
     // k0 < top always (k0 < kend <= lim_wg + 1 <= top), and the tile lies in ONE page (k0 % 32 == 0, PAGE % 32 == 0): row j of the tile is row
     // (page * Hkv + hk) * PAGE + k0 % PAGE + j of the pool, below the page's PAGE rows.
+    // the tile's slots that can count at all, as a 32-bit set (bit j: slot k0 + j lies below `top`; none without a page): the same in every wave
+    auto countable = [&](int k0, bool paged) { return paged ? (unsigned)__ballot(lane < 32 && k0 + lane < top) : 0u; };
+    Mx4Tile<NT> tile = {};                                               // (StageMx4) the requested tile in registers and, from commit() on, its set of slots
+    unsigned kb_next = 0u;
     auto stage = [&](int k0, int buf) -> bool {
         const int pi = k0 / PAGE;                                        // (workgroup-uniform, like everything up to the requests)
         const int page = pi < max_pages ? trow[pi] : -1;                 // one uniform load per tile; an index past the row is no page
-        if (page < 0 || page >= num_pages) return false;                 // no page: no address is formed from the id
+        if (page < 0 || page >= num_pages) {                             // no page: no address is formed from the id
+            return false;
+        }
         const int64_t tilebase = ((int64_t)page * Hkv + hk) * PAGE + k0 % PAGE;
-        if (k0 + XT <= top) {                                            // (uniform) all 32 slots lie below `top`
-            const char* kb = reinterpret_cast<const char*>(kp + tilebase * XD);
-            const char* vb = reinterpret_cast<const char*>(vp + tilebase * XD);
+        if constexpr (S::MX4) {                                          // requested into registers; commit() puts them into the image.  Tile rows
+            tile.request(kp, vp, tilebase, min(XT, top - k0) - 1, tid);  // above slot top - 1 are read as that slot of THIS tile: inside its page
+            return true;
+        } else {
+            if (k0 + XT <= top) {                                        // (uniform) all 32 slots lie below `top`
+                const char* kb = reinterpret_cast<const char*>(kp + tilebase * XD);
+                const char* vb = reinterpret_cast<const char*>(vp + tilebase * XD);
+#pragma unroll
+                for (int u = 0; u < PP; ++u) {
+                    lds_dma16_sbase(kb, koffs[u], klds + buf * (XT * XROW) + u * (NT * 16));
+                    lds_dma16_sbase(vb, voffs[u], vlds + buf * (XT * XROW) + u * (NT * 16));
+                }
+                return true;
+            }
+            // a slot at or above `top` is read as slot top - 1 and discarded.  k0 < top <= k0 + 31 here, so slot top - 1 is a slot of THIS tile: the
+            // clamped read stays inside the tile's own page, which is what keeps every address in bounds.
 #pragma unroll
             for (int u = 0; u < PP; ++u) {
-                lds_dma16_sbase(kb, koffs[u], klds + buf * (XT * XROW) + u * (NT * 16));
-                lds_dma16_sbase(vb, voffs[u], vlds + buf * (XT * XROW) + u * (NT * 16));
+                const int p = u * NT + tid, row = p >> 4, pc = p & 15;
+                const int64_t src = (tilebase + min(row, top - 1 - k0)) * XD;
+                lds_dma16(kp + src + ((pc ^ (row & 15)) << 3), klds + buf * (XT * XROW) + u * (NT * 16));
+                lds_dma16(vp + src + (pc << 3), vlds + buf * (XT * XROW) + u * (NT * 16));
             }
             return true;
         }
-        // a slot at or above `top` is read as slot top - 1 and discarded.  k0 < top <= k0 + 31 here, so slot top - 1 is a slot of THIS tile: the
-        // clamped read stays inside the tile's own page, which is what keeps every address in bounds.
-#pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            const int p = u * NT + tid, row = p >> 4, pc = p & 15;
-            const int64_t src = (tilebase + min(row, top - 1 - k0)) * XD;
-            lds_dma16(kp + src + ((pc ^ (row & 15)) << 3), klds + buf * (XT * XROW) + u * (NT * 16));
-            lds_dma16(vp + src + (pc << 3), vlds + buf * (XT * XROW) + u * (NT * 16));
-        }
-        return true;
     };
     bool paged_next = false;                                             // (workgroup-uniform) was the tile about to be used staged from a page?
-    if (nkt > 0) paged_next = stage(kbeg, 0);
+    auto commit = [&](int k0, int buf) {                                 // (StageMx4) the requested tile k0 -> LDS buffer buf, the V rows of dead slots as zeros
+        if constexpr (S::MX4) {
+            kb_next = countable(k0, paged_next);
+            tile.commit(&Ks[buf][0], &Vs[buf][0], kb_next, paged_next, tid);
+        }
+    };
+    if (nkt > 0) { paged_next = stage(kbeg, 0); commit(kbeg, 0); }
+    // (StageMx4) vmcnt(0), as an instruction the compiler's own wait counting sees: q has arrived on every path into the loop, so no wait for a q
+    // fragment inside it also waits for the tile loads that were just requested.
+    if constexpr (S::MX4) __builtin_amdgcn_s_waitcnt(0x0f70);
     for (int kt = 0; kt < nkt; ++kt) {
         const int buf = kt & 1;
         const bool paged = paged_next;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // this thread's pieces of tile kt
+        if constexpr (!S::MX4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this thread's pieces of tile kt (StageMx4: the barrier waits for its LDS writes)
         __syncthreads();                                                 // everyone's; everyone is done with the other buffer
         const int k0 = kbeg + kt * XT;
-        if (kt + 1 < nkt) paged_next = stage(k0 + XT, buf ^ 1);
-        // the tile's slots that can count at all, as a 32-bit set (bit j: slot k0 + j lies below `top`; none without a page): the same in every wave
-        const unsigned kbits = paged ? (unsigned)__ballot(lane < 32 && k0 + lane < top) : 0u;
-        if (kbits != 0xffffffffu) {                                      // (workgroup-uniform) zero the V rows of the other slots: they may hold anything
+        const unsigned kb_cur = kb_next;                                 // (StageMx4) this tile's set, found when it was requested
+        const bool more = kt + 1 < nkt;
+        if (more) paged_next = stage(k0 + XT, buf ^ 1);
+        unsigned kbits;
+        if constexpr (S::MX4) {
+            kbits = kb_cur;                                              // commit() wrote zeros for the V rows of the other slots
+        } else {
+            kbits = countable(k0, paged);
+            if (kbits != 0xffffffffu) {                                  // (workgroup-uniform) zero the V rows of the other slots: they may hold anything
 #pragma unroll
-            for (int u = 0; u < PP; ++u) {
-                const int p = u * NT + tid;
-                if (!((kbits >> (p >> 4)) & 1u)) *reinterpret_cast<f32x4*>(&Vs[buf][p * 16]) = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int u = 0; u < PP; ++u) {
+                    const int p = u * NT + tid;
+                    if (!((kbits >> (p >> 4)) & 1u)) *reinterpret_cast<f32x4*>(&Vs[buf][p * 16]) = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                __syncthreads();
             }
-            __syncthreads();
         }
-        if (!live || k0 > lim_hi) continue;                              // wave-uniform: no rows, or the whole tile lies in this wave's future
+        if (!live || k0 > lim_hi) {                                      // wave-uniform: no rows, or the whole tile lies in this wave's future
+            if (more) commit(k0 + XT, buf ^ 1);
+            continue;
+        }
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
@@ -187,6 +218,7 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_paged_kernel(const bf16* 
                 o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_read_tr16(va, va + 8 * XROW), k2 == 0 ? p0 : p1, o[d], 0, 0, 0);
             }
         }
+        if (more) commit(k0 + XT, buf ^ 1);                                       // after this tile's MFMAs: the loads had their time
     }
     // the span's partial of every row, as the dense kernel writes it; a row that counted no slot of the span writes (-inf, 0, zeros)
     if (m0 + qi < MR) {
@@ -281,19 +313,26 @@ __global__ __launch_bounds__(64) void attn_extend_merge_paged_kernel(const float
     merge_chunks<T>(ws + bh * nch * (Dh + 2), out + bh * Dh, n, Dh);
 }
 
+// The MFMA kernel's launch for either staging: NW = 1 serves G * Tn <= 32 stacked rows, NW = 4 everything else; `nch` partials per row.
+template <typename S>
+void launch_extend_paged_mfma(hipStream_t s, const bf16* q, int64_t ldq, typename S::Rows kp, typename S::Rows vp, const int* table, int max_pages,
+                              int num_pages, const int* lens0, float* ws, int B, int Tn, int H, int Hkv, int span, int nch, float scale) {
+    const int MR = (H / Hkv) * Tn;
+    const float sl = scale * 1.44269504088896340736f;
+    if (MR <= 32)
+        attn_extend_paged_kernel<1, S><<<dim3(nch, Hkv, B), 64, 0, s>>>(q, ldq, kp, vp, table, max_pages, num_pages, lens0, ws, Tn, H, Hkv, span, sl);
+    else
+        attn_extend_paged_kernel<4, S><<<dim3(nch, Hkv * cdiv(MR, 128), B), 256, 0, s>>>(q, ldq, kp, vp, table, max_pages, num_pages, lens0, ws, Tn, H, Hkv,
+                                                                                         span, sl);
+}
+
 template <typename T>
 int extend_paged_t(const char* name, hipStream_t s, const T* q, int64_t ldq, const T* kp, const T* vp, const int* table, int max_pages, int num_pages,
                    const int* lens0, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh, int max_len0, float scale) {
     const int span = extend_span(sizeof(T) == 2, Tn, H, Hkv, Dh), nch = cdiv(max_len0 + Tn, span);       // the dense call's partition at len0 = max_len0
     if (sizeof(T) == 2 && Dh == XD) {
-        const int MR = (H / Hkv) * Tn;
-        const float sl = scale * 1.44269504088896340736f;
-        if (MR <= 32)
-            attn_extend_paged_kernel<1><<<dim3(nch, Hkv, B), 64, 0, s>>>((const bf16*)q, ldq, (const bf16*)kp, (const bf16*)vp, table, max_pages, num_pages,
-                                                                       lens0, ws, Tn, H, Hkv, span, sl);
-        else
-            attn_extend_paged_kernel<4><<<dim3(nch, Hkv * cdiv(MR, 128), B), 256, 0, s>>>((const bf16*)q, ldq, (const bf16*)kp, (const bf16*)vp, table,
-                                                                                        max_pages, num_pages, lens0, ws, Tn, H, Hkv, span, sl);
+        launch_extend_paged_mfma<StageDma>(s, (const bf16*)q, ldq, (const bf16*)kp, (const bf16*)vp, table, max_pages, num_pages, lens0, ws, B, Tn, H, Hkv, span,
+                                           nch, scale);
     } else {
         attn_chunk_paged_kernel<T, KvNative<T>><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, KvNative<T>{kp, vp}, table, max_pages, num_pages, lens0, ws, Tn, H,
                                                                                   Hkv, Dh, scale);
@@ -304,14 +343,19 @@ int extend_paged_t(const char* name, hipStream_t s, const T* q, int64_t ldq, con
     return SETOK_OK;
 }
 
-// Over MXFP4 pools: the wave-per-chunk kernel for every head dim and element type, one partial per chunk (the dense MXFP4 extend's partition).
+// Over MXFP4 pools: the native call's dispatch and partition (the dense MXFP4 extend's).  16-bit at head dim 128: the MFMA kernel staged from
+// nibbles, `span` slots per partial (a prefix of the workspace, whose rule stays one partial per chunk); everything else the wave-per-chunk kernel.
 template <typename T>
 int extend_paged_mxfp4_t(const char* name, hipStream_t s, const T* q, int64_t ldq, KvMxfp4 kv, const int* table, int max_pages, int num_pages,
                          const int* lens0, T* out, float* ws, int B, int Tn, int H, int Hkv, int Dh, int max_len0, float scale) {
-    const int nch = cdiv(max_len0 + Tn, EXT_CHUNK);
-    attn_chunk_paged_kernel<T, KvMxfp4><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kv, table, max_pages, num_pages, lens0, ws, Tn, H, Hkv, Dh, scale);
+    const int span = extend_span(sizeof(T) == 2, Tn, H, Hkv, Dh), nch = cdiv(max_len0 + Tn, span);
+    if (sizeof(T) == 2 && Dh == XD) {
+        launch_extend_paged_mfma<StageMx4>(s, (const bf16*)q, ldq, kv.k, kv.v, table, max_pages, num_pages, lens0, ws, B, Tn, H, Hkv, span, nch, scale);
+    } else {
+        attn_chunk_paged_kernel<T, KvMxfp4><<<dim3(B * Tn, H, nch), 64, 0, s>>>(q, ldq, kv, table, max_pages, num_pages, lens0, ws, Tn, H, Hkv, Dh, scale);
+    }
     if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(chunks): %s", name, hipGetErrorString(e));
-    attn_extend_merge_paged_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, lens0, nch, EXT_CHUNK, Tn, H, Dh);
+    attn_extend_merge_paged_kernel<T><<<B * Tn * H, 64, 0, s>>>(ws, out, lens0, nch, span, Tn, H, Dh);
     if (hipError_t e = hipGetLastError()) return setok_fail(SETOK_ELAUNCH, "%s(merge): %s", name, hipGetErrorString(e));
     return SETOK_OK;
 }
@@ -368,6 +412,8 @@ extern "C" int setok_attention_extend_gqa_paged_mxfp4kv(void* stream, int dtype,
                     "%s: slots [%d, %d + %d) outside [0, max_pages = %d * %d slots] (beyond the table)", name, max_len0, max_len0, Tn, max_pages, PAGE);
     SETOK_CHECK_ARG((int64_t)B * Tn <= 0x7fffffffll && cdiv(max_len0 + Tn, EXT_CHUNK) <= 65535, "%s: B=%d Tn=%d H=%d max_len0=%d exceed the launch grid", name,
                     B, Tn, H, max_len0);
+    SETOK_CHECK_ARG(!(dtype == SETOK_BF16 && Dh == XD) || ((int64_t)(H / Hkv) * Tn + 127) / 128 * Hkv <= 65535,
+                    "%s: Tn=%d H=%d Hkv=%d exceed the launch grid of the MFMA kernel (Hkv * ceil(G * Tn / 128) <= 65535)", name, Tn, H, Hkv);
     SETOK_CHECK_ARG(ldq >= (int64_t)H * Dh && ldq % 8 == 0 && aligned16(q) && aligned16(k_q) && aligned16(v_q),
                     "%s: q rows (stride %lld) and the nibble pools must be 16-byte aligned", name, (long long)ldq);
     const int64_t need = setok_attention_extend_paged_mxfp4kv_workspace(B, Tn, H, Dh, max_len0);

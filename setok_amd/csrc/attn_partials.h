@@ -96,6 +96,76 @@ struct KvMxfp4 {
     }
 };
 
+// ---- how a 32-key tile of the MFMA extend kernels (attn_extend.hip, attn_extend_paged.hip) reaches LDS: the staging policy S -------------------
+// Both kernels read ONE LDS image — 256-byte rows of the 16-bit type, K in 16-byte slots XOR-swizzled by (row & 15), V row-major for the
+// transposing reads — and state the tile arithmetic once each; S says what a cache operand is (Rows) and whether the image is filled by LDS-DMA
+// from native rows (StageDma: the request IS the fill, nothing to commit) or from MXFP4 rows through registers (StageMx4: request = loads into an
+// Mx4Tile, commit = convert and write after the previous tile's MFMAs).
+struct StageDma {
+    static constexpr bool MX4 = false;
+    typedef const bf16* __restrict__ Rows;
+};
+struct StageMx4 {
+    static constexpr bool MX4 = true;
+    typedef Mx4Rows Rows;
+};
+
+// A tile of MXFP4 rows at head dim 128 on its way to LDS: 128 MX blocks of K, then 128 of V (a block: 16 bytes of nibbles + its e8m0 byte = 32
+// elements = 64 bytes of the image), 256 / NT per thread of a workgroup of NT threads; block p & 127 is block (p & 3) of tile row (p & 127) >> 2,
+// so a wave's loads are consecutive in memory, and p < 128 (K or V) is wave-uniform.
+template <int NT> struct Mx4Tile {
+    static constexpr int NB = 256 / NT;
+    u32x4 w[NB];
+    unsigned s[NB];
+
+    // row0: the operands' row of the tile's slot 0; tile rows above `last` (the last slot below `top`) are read as row `last` and discarded
+    __device__ inline void request(const Mx4Rows& k, const Mx4Rows& v, int64_t row0, int last, int tid) {
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            const int p = u * NT + tid;
+            const Mx4Rows& src = p < 128 ? k : v;
+            const int64_t blk = (row0 + min((p & 127) >> 2, last)) * 4 + (p & 3);       // the block's index in the operand
+            w[u] = *reinterpret_cast<const u32x4*>(src.q + blk * 16);
+            s[u] = src.s[blk];
+        }
+    }
+
+    // out[j] = x[(j + r) & 3]: a lane writes its block's four 16-byte pieces in an order rotated by r, which costs selects on the nibble dwords only
+    __device__ static inline u32x4 rot4(u32x4 x, int r) {
+        if (r & 1) x = u32x4{x[1], x[2], x[3], x[0]};
+        if (r & 2) x = u32x4{x[2], x[3], x[0], x[1]};
+        return x;
+    }
+
+    // Convert (v_cvt_scalef32_pk_*_fp4: exact, the scale applied) and write the tile into the image Kb / Vb.  kbits: the tile's slots that can count;
+    // the V row of every other slot is written as zeros (its nibbles and scale byte may be anything, 0xFF -> NaN included, and 0 * NaN would reach the
+    // accumulators), its K row as it is (the score is replaced by selection).  !staged: nothing was requested (no page) — kbits is 0, V becomes
+    // zeros, K stays whatever the buffer held.  ds_write_b128 is served in groups of 8 consecutive lanes over 32 banks: the rotation makes the 8
+    // pieces of a group distinct modulo 128 bytes (V: r = (p >> 1) & 3; K: r = p & 2, the swizzle's row bit does the rest).
+    __device__ inline void commit(char* Kb, char* Vb, unsigned kbits, bool staged, int tid) const {
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            const int p = u * NT + tid, row = (p & 127) >> 2, c0 = (p & 3) * 4;
+            if (p < 128) {
+                if (!staged) continue;
+                const int r = p & 2;
+                const u32x4 x = rot4(w[u], r);
+                const float sc = mx4_scale(s[u]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    *reinterpret_cast<bf16x8*>(Kb + row * 256 + (((c0 + ((j + r) & 3)) ^ (row & 15)) << 4)) = mx4_frag(x[j], sc);
+            } else {
+                const bool on = (kbits >> row) & 1u;
+                const int r = (p >> 1) & 3;
+                const u32x4 x = rot4(on ? w[u] : u32x4{0u, 0u, 0u, 0u}, r);            // nibble 0 under scale byte 127 is +0.0
+                const float sc = mx4_scale(on ? s[u] : 127u);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<bf16x8*>(Vb + row * 256 + ((c0 + ((j + r) & 3)) << 4)) = mx4_frag(x[j], sc);
+            }
+        }
+    }
+};
+
 // ---- any head dim (Dh % 8 == 0): one wave per (query row, query head, chunk of CHUNK slots), a key per lane ------------------------------------
 // Row b * Tn + i counts slot j iff j <= len0 + i and its mask byte is non-zero (a decode call: Tn = 1, len0 = len - 1).  Only a slot that counts is
 // read.  grid (rows, H, chunks) with ROWS_X, else (chunks, H, rows): each caller keeps the grid its entry point's limits were written for.

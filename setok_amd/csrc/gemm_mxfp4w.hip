@@ -14,17 +14,6 @@
 #include "wstream.h"
 #include "mx4.h"
 
-#ifdef SETOK_HALF
-#define MX4_CVT_PK16 __builtin_amdgcn_cvt_scalef32_pk_f16_fp4
-#else
-#define MX4_CVT_PK16 __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4
-#endif
-
-// the 8 values of one dword (mx4.h: mx4_f32x8's order), scaled, in the 16-bit element type
-__device__ inline bf16x8 mx4_frag(unsigned w, float sc) {
-    const bf16x2 p0 = MX4_CVT_PK16(w, sc, 0), p1 = MX4_CVT_PK16(w, sc, 1), p2 = MX4_CVT_PK16(w, sc, 2), p3 = MX4_CVT_PK16(w, sc, 3);
-    return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
 // ---- the quantiser: one thread per 32-element block, the block in registers, no atomics ---------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void mx4_quantize_kernel(const T* __restrict__ W, int64_t ldw, uint8_t* __restrict__ q, int64_t ldq,

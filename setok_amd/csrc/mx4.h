@@ -15,6 +15,20 @@ __device__ inline void mx4_f32x8(unsigned w, float sc, float* f) {
     f[0] = p0[0]; f[1] = p0[1]; f[2] = p1[0]; f[3] = p1[1]; f[4] = p2[0]; f[5] = p2[1]; f[6] = p3[0]; f[7] = p3[1];
 }
 
+// The converter into the build's 16-bit element type (common.h): exact for every value(nibble) * 2^e with e in [-13, 13], the exponents the
+// quantisers write (6 * 2^13 < 65504, 0.5 * 2^-13 is fp16's smallest normal).
+#ifdef SETOK_HALF
+#define MX4_CVT_PK16 __builtin_amdgcn_cvt_scalef32_pk_f16_fp4
+#else
+#define MX4_CVT_PK16 __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4
+#endif
+
+// the 8 values of one dword (mx4_f32x8's order), scaled, in the 16-bit element type: one 16-byte MFMA operand fragment
+__device__ inline bf16x8 mx4_frag(unsigned w, float sc) {
+    const bf16x2 p0 = MX4_CVT_PK16(w, sc, 0), p1 = MX4_CVT_PK16(w, sc, 1), p2 = MX4_CVT_PK16(w, sc, 2), p3 = MX4_CVT_PK16(w, sc, 3);
+    return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
 // round-to-nearest, ties to the even code, to e2m1 (0, 0.5, 1, 1.5, 2, 3, 4, 6), saturating at +-6; v is finite.  The sign bit is v's own.
 __device__ inline unsigned mx4_encode(float v) {
     const unsigned sign = (__builtin_bit_cast(unsigned, v) >> 28) & 0x8u;

@@ -416,7 +416,8 @@ class LlamaModel(PackCacheMixin, nn.Module):
         stays masked and its hidden state means nothing.  HF LlamaDecoderLayer.forward with `past_key_values` on a Tn-token input; the GEMMs are the
         prefill's at M = B * Tn (fp8 weights: `decode_step`'s streaming GEMM up to FP8W_MAX_M rows, the dequantise scratch above).
         Over an mxfp4 KV cache the rows are quantised on append and the attention reads the stored slots, the new rows' own included
-        (ops.attention_extend_mxfp4kv: the functional kernel, every head dim).
+        (ops.attention_extend_mxfp4kv: at head dim 128 in bf16 / fp16 the native MFMA kernel on tiles converted from nibbles, so the bits are the
+        native extend's over the stored values; every other head dim and fp32 the wave-per-chunk kernel).
         Refused with the cache untouched: an fp8 KV cache (NotImplementedError), a wrong B, Tn == 0 on an empty cache, len + Tn > cap (ValueError)."""
         self._refuse_unmerged("LlamaModel.extend")
         B, Tn, D = inputs_embeds.shape
@@ -771,7 +772,8 @@ class SetokimLlamaPrefill(nn.Module, SetokimVisionMixin):
         `_forward`) and stores the quantised rows; every later step attends over the stored values.  Unlike the fp8 cache it works with `draft=`,
         `prefill_chunk=`, `past=` / `return_past` and `LlamaModel.extend`.  A window of a chunked prefill attends over the stored, quantised
         slots — its own rows included — so `prefill_chunk=N` over a quantised cache is NOT the unchunked function (over the native cache it is).
-        The extend attention over nibbles is a functional kernel without MFMA: long windows and turns are slow.
+        The extend attention over nibbles is the native MFMA kernel at head dim 128 in bf16 / fp16 (its tiles are converted on their way to LDS);
+        in fp32 and at other head dims it is a functional kernel without MFMA, where long windows and turns are slow.
 
         `sampler=` (a generation.Sampler: temperature, top_k, top_p and the uniforms, given or drawn from a generator) replaces the step's argmax
         by one `setok_sample_rows` launch; everything else in the loop is the same, and `sampler=None` is the greedy path bit for bit.  A row

@@ -973,14 +973,17 @@ def attention_decode_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v
 
 def attention_extend_mxfp4kv_workspace(B: int, Tn: int, H: int, Dh: int, len0: int) -> int:
     """Floats of workspace setok_attention_extend_gqa_mxfp4kv needs: B * Tn * H * ceil((len0 + Tn) / EXTEND_CHUNK) * (Dh + 2), whatever the
-    element type (one partial per chunk: attention_extend_workspace's span rule does not apply)."""
+    element type and head dim (one partial per chunk; the MFMA path, 16 bits at head dim 128, leaves a partial per span as attention_extend
+    does and uses a prefix of it: the rule does not follow it)."""
     return B * Tn * H * ((len0 + Tn + EXTEND_CHUNK - 1) // EXTEND_CHUNK) * (Dh + 2)
 
 
 def attention_extend_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, key_mask: Tensor, H: int, Tn: int, len0: int,
                              scale: float, ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
-    """attention_extend over an MXFP4 cache, which already holds the new rows' quantised keys / values in slots [len0, len0 + Tn).  The
-    functional path: one wave per (query row, query head, chunk) for every head dim and element type, no MFMA."""
+    """attention_extend over an MXFP4 cache, which already holds the new rows' quantised keys / values in slots [len0, len0 + Tn), with
+    attention_extend's dispatch.  bf16 / fp16 at head dim 128: the native MFMA kernel on tiles converted from nibbles — the result's bits are
+    attention_extend's over caches holding K', V' = value(nibble) * 2^(scale byte - 127), which must be representable in q.dtype (every row
+    kv_append_mxfp4 writes is).  fp32 and the other head dims: one wave per (query row, query head, chunk), no MFMA."""
     B, Hkv, cap, Dh = _mxfp4kv_shapes(k_q, k_s, v_q, v_s)
     assert Tn >= 1 and len0 >= 0 and len0 + Tn <= cap, f"attention_extend_mxfp4kv: slots [{len0}, {len0} + {Tn}) exceed the cache (cap = {cap})"
     assert q.shape[0] == B * Tn and q.shape[1] >= H * Dh and q.stride(1) == 1 and q.is_cuda
@@ -1043,14 +1046,17 @@ def attention_decode_paged_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Ten
 
 
 def attention_extend_paged_mxfp4kv_workspace(B: int, Tn: int, H: int, Dh: int, max_len0: int) -> int:
-    """Floats of workspace setok_attention_extend_gqa_paged_mxfp4kv needs: attention_extend_mxfp4kv_workspace's rule at len0 = max_len0."""
+    """Floats of workspace setok_attention_extend_gqa_paged_mxfp4kv needs: attention_extend_mxfp4kv_workspace's rule at len0 = max_len0 (on the
+    MFMA path an upper bound of which a prefix is used, as there)."""
     return attention_extend_mxfp4kv_workspace(B, Tn, H, Dh, max_len0)
 
 
 def attention_extend_paged_mxfp4kv(q: Tensor, k_q: Tensor, k_s: Tensor, v_q: Tensor, v_s: Tensor, block_table: Tensor, len0: Tensor, H: int, Tn: int,
                                    max_len0: int, scale: float, ws: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """attention_extend_paged over MXFP4 pools, which already hold the new rows' quantised keys / values in slots [len0[b], len0[b] + Tn)
-    (kv_append_paged_mxfp4 with slot0 = len0).  The functional path, for every head dim that is a multiple of 32; a sequence's bits are
+    (kv_append_paged_mxfp4 with slot0 = len0), for every head dim that is a multiple of 32.  bf16 / fp16 at head dim 128: attention_extend_paged's
+    MFMA kernel on tiles converted from nibbles — the result's bits are attention_extend_paged's over pools holding K', V' (representable in
+    q.dtype: every row kv_append_paged_mxfp4 writes is); everything else the wave-per-chunk kernel.  Either way a sequence's bits are
     attention_extend_mxfp4kv's at B = 1 on its gathered slots."""
     num_pages, Hkv, Dh, B, max_pages = _paged_mxfp4_shapes(k_q, k_s, v_q, v_s, block_table, len0)
     assert Tn >= 1 and 0 <= max_len0 and max_len0 + Tn <= max_pages * KV_PAGE, \
