@@ -600,6 +600,22 @@ int setok_attention_extend_gqa(void* stream, int dtype, const void* q, int64_t l
 int setok_sample_rows(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u, float temperature, int top_k,
                       float top_p, int64_t* out, float* probs, int64_t ld_probs);
 
+/* setok_sample_rows_each - the same launch (one workgroup per row, the same kernel text) with the three parameters PER ROW: temperature and top_p
+ * are (rows) fp32 device arrays, top_k a (rows) int32 device array, and row r is selected under temperature[r], top_k[r], top_p[r].  It is what a
+ * batch needs whose rows belong to different requests (ContinuousBatcher.submit(sampler=)): greedy rows sit next to sampled ones.  Every thread of
+ * a row's workgroup reads the same three words, so each branch below is workgroup-uniform.  Pure addition: the ABI version stays 9.
+ *   - Sampled row: temperature[r] finite and > 0, top_k[r] >= 0, top_p[r] in (0, 1].  out[r] and the `probs` row are, bit for bit, what
+ *     setok_sample_rows writes for that row under those three scalars and the same u[r] (rules 1-7 above, bad rows included).
+ *   - Greedy row: temperature[r] == 0; top_k[r], top_p[r] and u[r] are ignored.  out[r] is what setok_argmax_rows writes for the row: the lowest
+ *     index of the maximum of the logits as they are, a NaN counting as the maximum.  The `probs` row, when given, is one-hot at that index.  This
+ *     is NOT top_k = 1, which keeps tied maxima together and draws among them (16-bit logits tie).
+ *   - Invalid row: anything else - a NaN, negative or infinite temperature, top_k < 0, top_p outside (0, 1] or NaN.  out[r] = -1 and zeros in the
+ *     `probs` row.  The row is classified before any of the three values is used: no address and no loop bound is formed from one.
+ * Refused on the host before any launch (-1, setok_last_error): a null logits / u / out / temperature / top_k / top_p, V < 1 or V > 2^20, ld < V,
+ * ld_probs < V with probs, a dtype the library does not serve.  rows == 0 launches nothing. */
+int setok_sample_rows_each(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u, const float* temperature,
+                           const int* top_k, const float* top_p, int64_t* out, float* probs, int64_t ld_probs);
+
 /* ---- Speculative decoding (csrc/speculate.hip): draft-and-verify on top of the extend above.  A round feeds K + 1 rows per sequence - the pending
  * token and K drafted ones - through one `extend`, selects a token from every row's logits (setok_argmax_rows or setok_sample_rows) and then keeps
  * the longest prefix of the drafts that the model itself would have produced, plus one more token: what the plain loop emits, in fewer passes

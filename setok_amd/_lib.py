@@ -110,6 +110,7 @@ SIGNATURES = {
     "setok_attention_extend_workspace": [_i, _i, _i, _i, _i, _i, _i],
     "setok_attention_extend_gqa": [_vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64],
     "setok_sample_rows": [_vp, _i, _vp, _i64, _i, _i, _vp, _f, _i, _f, _vp, _vp, _i64],
+    "setok_sample_rows_each": [_vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64],
     "setok_spec_accept": [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "setok_ngram_propose": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp],
     "setok_beam_topk": [_vp, _i, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64],

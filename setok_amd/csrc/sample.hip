@@ -1,5 +1,6 @@
 // sample.hip — sampled token selection for the decode loop: temperature, top-k and top-p in ONE launch per step (include/setok_hip.h, "Sampling").
-//   setok_sample_rows    out[r] = the token row r of the logits draws with the uniform u[r]
+//   setok_sample_rows        out[r] = the token row r of the logits draws with the uniform u[r]
+//   setok_sample_rows_each   the same launch with (temperature, top_k, top_p) per row; a row with temperature 0 takes the argmax instead
 //
 // The draw is a pure function of (logits row, u, temperature, top_k, top_p): the uniform is an input, every sum is an INTEGER sum of the
 // fixed-point weights w_i = rint(exp(s_i - max s) * 2^32), so no result depends on the order in which lanes or waves arrive (LDS integer atomics
@@ -172,15 +173,97 @@ __device__ inline unsigned sample_select(const Row& row, int V, float m, unsigne
     return prefix;
 }
 
-template <typename T, bool IN_LDS>
+// Where a row's three parameters come from.  Both sources give every thread of a workgroup the same values, so the kernel's branches on them are
+// workgroup-uniform.  setok_sample_rows: the launch's scalars, validated on the host - every row is drawn from.
+struct SampleScalars {
+    float temperature;
+    int top_k;
+    float top_p;
+    static constexpr bool PER_ROW = false;
+    __device__ inline float t(int) const { return temperature; }
+    __device__ inline int k(int) const { return top_k; }
+    __device__ inline float p(int) const { return top_p; }
+};
+// setok_sample_rows_each: (rows) arrays, nothing validated on the host - the kernel classifies the row before it uses a value.
+struct SampleArrays {
+    const float* temperature;
+    const int* top_k;
+    const float* top_p;
+    static constexpr bool PER_ROW = true;
+    __device__ inline float t(int r) const { return temperature[r]; }
+    __device__ inline int k(int r) const { return top_k[r]; }
+    __device__ inline float p(int r) const { return top_p[r]; }
+};
+
+// f(i, float(g[i])) for every i < V, each element once: 16-byte pieces between the row's first 16-byte boundary and its last whole piece.
+template <typename T, class F>
+__device__ inline void sample_read_row(const T* g, int V, F&& f) {
+    constexpr int VEC = Elem<T>::VEC;
+    const int tid = threadIdx.x;
+    int head = (int)(((16u - (unsigned)((uintptr_t)g & 15u)) & 15u) / sizeof(T));          // elements before the first 16-byte boundary
+    if (head > V) head = V;
+    const int nvec = (V - head) / VEC, tail0 = head + nvec * VEC;
+    if (tid < head) f(tid, (float)g[tid]);
+    for (int v = tid; v < nvec; v += SAMPLE_THREADS) {
+        float x[VEC];
+        ld_vec<T>(g + head + v * VEC, x);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) f(head + v * VEC + e, x[e]);
+    }
+    if (tail0 + tid < V) f(tail0 + tid, (float)g[tail0 + tid]);                            // fewer than VEC elements
+}
+
+// A greedy row (temperature 0): setok_argmax_rows' rule - the lowest index of the maximum of the logits as they are, a NaN counting as the maximum,
+// -0 == +0 - as one integer maximum of (order key of the value, V's complement of the index): exact in any association.  probs: one-hot.
+template <typename T>
+__device__ inline void sample_greedy_row(const T* g, int V, SampleShared& sh, int64_t* out_r, float* probs_r) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr u64 LOW = (u64)SAMPLE_MAX_V - 1;                         // i <= 2^20 - 1: 20 bits under a 33-bit key
+    u64 best = 0;                                                      // below every element's word (a key is never 0 ... and V >= 1)
+    sample_read_row(g, V, [&](int i, float x) {
+        const u64 key = x != x ? 0x100000000ull : (u64)sample_key(x);
+        const u64 word = (key << 20) | (LOW - (u64)i);
+        best = word > best ? word : best;
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)best, o, 64), hi = __shfl_xor((unsigned)(best >> 32), o, 64);
+        const u64 t = ((u64)hi << 32) | lo;
+        best = t > best ? t : best;
+    }
+    if (lane == 0) sh.wtot[wave] = best;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < SAMPLE_WAVES; ++w) best = sh.wtot[w] > best ? sh.wtot[w] : best;
+    const int at = (int)(LOW - (best & LOW));
+    if (tid == 0) *out_r = at;
+    if (probs_r)
+        for (int i = tid; i < V; i += SAMPLE_THREADS) probs_r[i] = i == at ? 1.f : 0.f;
+}
+
+template <typename T, bool IN_LDS, class Params>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __restrict__ logits, int64_t ld, int V, const float* __restrict__ u,
-                                                                       float temperature, int top_k, float top_p, int64_t* __restrict__ out,
-                                                                       float* __restrict__ probs, int64_t ld_probs) {
+                                                                       Params params, int64_t* __restrict__ out, float* __restrict__ probs,
+                                                                       int64_t ld_probs) {
     extern __shared__ __attribute__((aligned(16))) float srow[];
     __shared__ SampleShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x;
     const T* g = logits + (int64_t)r * ld;
-    constexpr int VEC = Elem<T>::VEC;
+    const float temperature = params.t(r), top_p = params.p(r);
+    const int top_k = params.k(r);
+    if constexpr (Params::PER_ROW) {                                   // workgroup-uniform: every thread read the same three words
+        if (temperature == 0.0f) {
+            sample_greedy_row(g, V, sh, out + r, probs ? probs + (int64_t)r * ld_probs : nullptr);
+            return;
+        }
+        // the host checks of setok_sample_rows, per row: nothing below sees a value outside them (the comparisons are false for a NaN)
+        if (!(temperature > 0.0f && temperature < INFINITY && top_k >= 0 && top_p > 0.0f && top_p <= 1.0f)) {
+            if (tid == 0) out[r] = -1;
+            if (probs)
+                for (int i = tid; i < V; i += SAMPLE_THREADS) probs[(int64_t)r * ld_probs + i] = 0.f;
+            return;
+        }
+    }
 
     // ---- pass 1: the only read of the row from memory; maximum and the bad-row flags --------------------------------------------------------
     float mx = -INFINITY;
@@ -191,19 +274,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
         else { if (s == INFINITY) flag |= 2; mx = fmaxf(mx, s); }
         if constexpr (IN_LDS) srow[i] = s;
     };
-    {
-        int head = (int)(((16u - (unsigned)((uintptr_t)g & 15u)) & 15u) / sizeof(T));      // elements before the first 16-byte boundary
-        if (head > V) head = V;
-        const int nvec = (V - head) / VEC, tail0 = head + nvec * VEC;
-        if (tid < head) see(tid, (float)g[tid]);
-        for (int v = tid; v < nvec; v += SAMPLE_THREADS) {
-            float x[VEC];
-            ld_vec<T>(g + head + v * VEC, x);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) see(head + v * VEC + e, x[e]);
-        }
-        if (tail0 + tid < V) see(tail0 + tid, (float)g[tail0 + tid]);                      // fewer than VEC elements
-    }
+    sample_read_row(g, V, see);
     mx = wave_max(mx);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) flag |= __shfl_xor(flag, o, 64);
@@ -292,20 +363,28 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const T* __
     }
 }
 
-template <typename T>
-static int sample_launch(hipStream_t s, const T* logits, int64_t ld, int rows, int V, const float* u, float temperature, int top_k, float top_p,
-                         int64_t* out, float* probs, int64_t ld_probs) {
+template <typename T, class Params>
+static int sample_launch(const char* who, hipStream_t s, const T* logits, int64_t ld, int rows, int V, const float* u, Params params, int64_t* out,
+                         float* probs, int64_t ld_probs) {
     if (V <= SAMPLE_LDS_MAX_V) {
         static SetokDeviceOnce once;
-        if (!once.run([] { return hipFuncSetAttribute((const void*)sample_rows_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (!once.run([] { return hipFuncSetAttribute((const void*)sample_rows_kernel<T, true, Params>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                       SAMPLE_LDS_MAX_V * (int)sizeof(float)) == hipSuccess; }))
-            return setok_fail(SETOK_ELAUNCH, "setok_sample_rows: cannot raise the dynamic LDS limit");
+            return setok_fail(SETOK_ELAUNCH, "%s: cannot raise the dynamic LDS limit", who);
         const size_t lds = ((size_t)V * sizeof(float) + 15) & ~(size_t)15;
-        sample_rows_kernel<T, true><<<rows, SAMPLE_THREADS, lds, s>>>(logits, ld, V, u, temperature, top_k, top_p, out, probs, ld_probs);
+        sample_rows_kernel<T, true, Params><<<rows, SAMPLE_THREADS, lds, s>>>(logits, ld, V, u, params, out, probs, ld_probs);
     } else {
-        sample_rows_kernel<T, false><<<rows, SAMPLE_THREADS, 0, s>>>(logits, ld, V, u, temperature, top_k, top_p, out, probs, ld_probs);
+        sample_rows_kernel<T, false, Params><<<rows, SAMPLE_THREADS, 0, s>>>(logits, ld, V, u, params, out, probs, ld_probs);
     }
     return SETOK_OK;
+}
+
+template <class Params>
+static int sample_dispatch(const char* who, void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u, Params params,
+                           int64_t* out, float* probs, int64_t ld_probs) {
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SETOK_BF16) return sample_launch<bf16>(who, s, (const bf16*)logits, ld, rows, V, u, params, out, probs, ld_probs);
+    return sample_launch<float>(who, s, (const float*)logits, ld, rows, V, u, params, out, probs, ld_probs);
 }
 
 extern "C" int setok_sample_rows(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u, float temperature,
@@ -318,11 +397,24 @@ extern "C" int setok_sample_rows(void* stream, int dtype, const void* logits, in
     SETOK_CHECK_ARG(top_p > 0.0f && top_p <= 1.0f, "setok_sample_rows: bad top_p %g (a probability in (0, 1]; 1 = no filter)", (double)top_p);
     SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_sample_rows: bad dtype %d", dtype);
     if (rows == 0) return SETOK_OK;
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (dtype == SETOK_BF16) rc = sample_launch<bf16>(s, (const bf16*)logits, ld, rows, V, u, temperature, top_k, top_p, out, probs, ld_probs);
-    else rc = sample_launch<float>(s, (const float*)logits, ld, rows, V, u, temperature, top_k, top_p, out, probs, ld_probs);
+    const int rc = sample_dispatch("setok_sample_rows", stream, dtype, logits, ld, rows, V, u, SampleScalars{temperature, top_k, top_p}, out, probs,
+                                   ld_probs);
     if (rc != SETOK_OK) return rc;
     SETOK_CHECK_LAUNCH("setok_sample_rows");
+    return SETOK_OK;
+}
+
+extern "C" int setok_sample_rows_each(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, const float* u,
+                                      const float* temperature, const int* top_k, const float* top_p, int64_t* out, float* probs,
+                                      int64_t ld_probs) {
+    SETOK_CHECK_ARG(logits && u && out && temperature && top_k && top_p, "setok_sample_rows_each: null operand");
+    SETOK_CHECK_ARG(rows >= 0 && V >= 1 && V <= SAMPLE_MAX_V && ld >= V && (!probs || ld_probs >= V),
+                    "setok_sample_rows_each: bad shape rows=%d V=%d (1 .. 2^20) ld=%lld ld_probs=%lld", rows, V, (long long)ld, (long long)ld_probs);
+    SETOK_CHECK_ARG(dtype == SETOK_BF16 || dtype == SETOK_F32, "setok_sample_rows_each: bad dtype %d", dtype);
+    if (rows == 0) return SETOK_OK;
+    const int rc = sample_dispatch("setok_sample_rows_each", stream, dtype, logits, ld, rows, V, u, SampleArrays{temperature, top_k, top_p}, out,
+                                   probs, ld_probs);
+    if (rc != SETOK_OK) return rc;
+    SETOK_CHECK_LAUNCH("setok_sample_rows_each");
     return SETOK_OK;
 }

@@ -1047,6 +1047,7 @@ class _Running:
     ticket: int
     max_new: int
     tokens: List[int]
+    sampled: bool = False
 
 
 @dataclass(eq=False)
@@ -1063,7 +1064,7 @@ class PrefixHandle:
 
 
 class ContinuousBatcher:
-    """Greedy decoding of many requests of different lengths on `rows` rows of one PagedKVCache: a request joins the running batch as soon as a row is
+    """Greedy - or, per request, sampled - decoding of many requests of different lengths on `rows` rows of one PagedKVCache: a request joins the running batch as soon as a row is
     idle and the pool can reserve the pages for ALL of its prompt + max_new_tokens slots, and leaves - its pages back in the pool - the step it emits
     an eos id or its last token.  Because a request's pages are reserved up front, a running request never runs out of pages: nothing is preempted.
 
@@ -1094,14 +1095,30 @@ class ContinuousBatcher:
     tokens are those of `lm.generate(..., kv_cache="mxfp4")` for that request alone, a prefixed request's those of the same call with
     `prefill_chunk=Ps`: the paged kernels run the dense MXFP4 kernels' arithmetic on the same partition of the keys.
 
-    Greedy only; refused by name (NotImplementedError): sampler=, beams=, draft=, processors=, prefill_chunk= and a quantised kv_cache= string
-    (quantised pages come in through `cache=`)."""
+    Sampling is per request: `submit(..., sampler=Sampler(temperature, top_k, top_p, u= | generator=))` - or a fourth element of a `run` tuple -
+    makes that request a sampled one; the others stay greedy and sit next to it in the batch.  The request's j-th emitted token is drawn with
+    u[j, 0] of ITS OWN stream, `u` (>= max_new_tokens, 1) float32; with `generator=` (or neither) the whole stream is ONE
+    `torch.rand((max_new_tokens, 1), generator=...)` draw at admission - not the per-step draws `generate`'s plain loop makes from a generator, so
+    only `u=` reproduces a `generate` call.  The first token is drawn from the admission's last state with u[0, 0], behind a prefix too.  The
+    batcher keeps (rows,) device arrays of the three parameters - an idle or greedy row holds temperature 0 - and the rows' uniforms on the device
+    by decode step; a step with at least one sampled running row selects for ALL rows with one `setok_sample_rows_each` launch, a step with none
+    calls `argmax_rows` exactly as before (the same launches in the same order), and neither adds a host read.  A sampled request's tokens are
+    those of `lm.generate(inputs_embeds=x[None], max_new_tokens=n, sampler=Sampler(temperature, top_k, top_p, u=u))` for that request alone.
+    A row that cannot be drawn from (-1: a NaN or +inf in its logits, or no finite entry) does not raise as `generate` does: the request ends in
+    that step - its row released, its pages back in the pool -, is reported in the step's result with the tokens drawn before it, and
+    `errors[ticket]` holds the message; the other requests are unaffected, and `run` drains everything and then raises RuntimeError naming the
+    failed tickets.  Not built (follow-ups): per-request `processors=`, n parallel samples over shared prompt pages, log-probabilities in the result.
+
+    Refused by name (NotImplementedError): sampler= at the constructor (a sampler belongs to a request: `submit(sampler=)`), beams=, draft=,
+    processors=, prefill_chunk= and a quantised kv_cache= string (quantised pages come in through `cache=`)."""
 
     def __init__(self, lm, rows: int, num_pages: Optional[int] = None, max_pages_per_seq: Optional[int] = None, eos_token_id=None, pad_token_id=None, *,
                  sampler=None, beams=None, draft=None, processors=None, prefill_chunk=None, kv_cache: str = "native", cache: Optional[PagedKVCache] = None):
         who = "ContinuousBatcher"
-        for name, given, why in (("sampler=", sampler is not None, "the batcher selects by argmax"),
-                                 ("beams=", beams is not None, "a beam's pages would have to be shared between rows"),
+        if sampler is not None:
+            raise NotImplementedError(f"{who}: sampler= is not an argument of the batcher: requests that share a batch each bring their own "
+                                      "temperature, nucleus and random stream; pass it per request, submit(..., sampler=Sampler(...))")
+        for name, given, why in (("beams=", beams is not None, "a beam's pages would have to be shared between rows"),
                                  ("draft=", draft is not None, "a verify pass over pages is not wired to LlamaModel.extend_paged yet"),
                                  ("processors=", processors is not None, "the rows' histories are not kept"),
                                  ("prefill_chunk=", prefill_chunk is not None, "a window over pages is not wired to LlamaModel.extend_paged yet")):
@@ -1137,9 +1154,18 @@ class ContinuousBatcher:
         self.cache = cache if cache is not None else PagedKVCache.for_model(lm.model, rows, num_pages, max_pages_per_seq, self.device)
         self.eos_ids = None if eos_token_id is None else [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
         self.pad_token_id = pad_token_id                                           # (kept for HF's signature: a finished request leaves, nothing is padded)
-        self.queue: List[Tuple[int, torch.Tensor, int, Optional[PrefixHandle]]] = []      # (ticket, prompt, max_new, prefix) in submit order
+        self.queue: List[Tuple[int, torch.Tensor, int, Optional[PrefixHandle], Optional[Sampler]]] = []      # (ticket, prompt, max_new, prefix, sampler) in submit order
         self.running: List[Optional[_Running]] = [None] * rows
         self.cur = torch.zeros(rows, dtype=torch.int64, device=self.device)        # every row's latest token: the next decode step's input
+        # per-request sampling: the rows' parameters (temperature 0 = an idle or greedy row: setok_sample_rows_each takes its argmax) and their
+        # uniforms by decode step - row t - _u_t0 of `_u` is what decode step t draws with; an admission writes its request's column ahead
+        self.temperature = torch.zeros(rows, dtype=torch.float32, device=self.device)
+        self.top_k = torch.zeros(rows, dtype=torch.int32, device=self.device)
+        self.top_p = torch.ones(rows, dtype=torch.float32, device=self.device)
+        self._u = torch.zeros((0, rows), dtype=torch.float32, device=self.device)
+        self._u_t0 = 0
+        self._t = 0                                                                # decode steps taken
+        self.errors: dict = {}                                                     # ticket -> why a sampled request ended early (an undrawable row)
         self._tickets = 0
         self._released: set = set()                                                # pages that went back to the pool at least once
         self.stats = dict(steps=0, row_steps_active=0, row_steps_total=0, pages_high_water=0, admitted=0, admitted_midflight=0, page_waits=0,
@@ -1198,7 +1224,7 @@ class ContinuousBatcher:
         if n > self.cache.pages_free:
             raise RuntimeError(f"{who}: the prefix needs {n} free pages, the pool has {self.cache.pages_free} of {self.cache.num_pages}")
         room = self.cache.num_pages - self._pinned() - n                           # what an empty batcher could still hand out with this prefix held too
-        for ticket, queued, max_new, pre in self.queue:
+        for ticket, queued, max_new, pre, _ in self.queue:
             own = self._own_pages(queued.shape[0], max_new, pre)
             if own > room:
                 raise RuntimeError(f"{who}: holding {n} more pages would leave the pool {room} pages for requests, and the queued request {ticket} "
@@ -1238,15 +1264,25 @@ class ContinuousBatcher:
         handle.dropped = True
         self._prefixes.remove(handle)
 
-    def submit(self, inputs_embeds=None, max_new_tokens: int = 1, input_ids=None, prefix: Optional[PrefixHandle] = None) -> int:
+    def submit(self, inputs_embeds=None, max_new_tokens: int = 1, input_ids=None, prefix: Optional[PrefixHandle] = None,
+               sampler: Optional[Sampler] = None) -> int:
         """Queue one request: its spliced prompt embeddings (T, D), or its token ids (T,) (as `input_ids=`, or an integer tensor in the first place).
         With `prefix=` (a handle of `register_prefix`) the prompt argument is the remainder behind the prefix, S >= 1 rows, and the request's prompt
-        is prefix ++ remainder.  Returns the ticket.  ValueError - the queue and the cache untouched - if the prompt's + max_new_tokens slots cannot
+        is prefix ++ remainder.  With `sampler=` (a `Sampler`) the request's tokens are drawn instead of taken by argmax: token j with u[j, 0] of
+        the sampler's `u` (>= max_new_tokens, 1), or - with a generator, or neither - of one `torch.rand((max_new_tokens, 1), generator=...)` draw
+        made at admission.  Returns the ticket.  ValueError - the queue and the cache untouched - if the prompt's + max_new_tokens slots cannot
         fit in max_pages_per_seq pages, or could never fit in the pool - the pool less the pages the registered prefixes hold, which no request can
-        have as its own until a `drop_prefix` -, and for a dropped or foreign handle."""
+        have as its own until a `drop_prefix` -, for a dropped or foreign handle, and for a sampler whose `u` is not (>= max_new_tokens, 1);
+        TypeError for a `sampler=` that is not a `Sampler`."""
         who = "ContinuousBatcher.submit"
         prompt = self._prompt_of(who, inputs_embeds, input_ids)
         _count(max_new_tokens, "max_new_tokens", who)
+        if sampler is not None:
+            if not isinstance(sampler, Sampler):
+                raise TypeError(f"{who}: sampler= must be a Sampler, got {type(sampler).__name__}")
+            if sampler.u is not None and (sampler.u.shape[0] < max_new_tokens or sampler.u.shape[1] != 1):
+                raise ValueError(f"{who}: the sampler's u has shape {tuple(sampler.u.shape)}; a request's stream is (at least max_new_tokens = "
+                                 f"{max_new_tokens}, 1): row j draws its j-th token")
         T = prompt.shape[0]
         if T < 1:
             raise ValueError(f"{who}: an empty prompt")
@@ -1266,12 +1302,32 @@ class ContinuousBatcher:
                                  f"request's own behind the prefix's {len(prefix.pages)} shared ones; a sequence has at most max_pages_per_seq = "
                                  f"{self.cache.max_pages_per_seq} and the pool num_pages = {self.cache.num_pages}{held}")
         ticket, self._tickets = self._tickets, self._tickets + 1
-        self.queue.append((ticket, prompt, max_new_tokens, prefix))
+        self.queue.append((ticket, prompt, max_new_tokens, prefix, sampler))
         return ticket
 
     def _tokens_of(self, h: torch.Tensor) -> torch.Tensor:
         """States (M, D) -> lm_head -> the rows' argmax, (M,) int64 on the device."""
         return ops.argmax_rows(ops.linear(h, self.w_lm))
+
+    def _stream_of(self, row: int, sampler: Sampler, max_new: int) -> torch.Tensor:
+        """A sampled admission: the request's parameters into the row's entries of the device arrays, its uniforms u[1:] into the row's column of
+        `_u` at the decode steps that will draw with them (a running row decodes in every step from its admission's on).  Returns u[0], (1,)."""
+        dev = self.device
+        if sampler.u is None:                                                      # the whole stream at once: one draw per request
+            u = torch.rand((max_new, 1), generator=sampler.generator, dtype=torch.float32,
+                           device=dev if sampler.generator is None else sampler.generator.device).to(dev)
+        else:
+            u = sampler.u[:max_new].to(dev)
+        self.temperature[row], self.top_k[row], self.top_p[row] = sampler.temperature, sampler.top_k, sampler.top_p
+        ahead, lo = max_new - 1, self._t - self._u_t0
+        if lo + ahead > self._u.shape[0]:                                          # regrow from the current step on: earlier rows are spent
+            keep = max(self._u.shape[0] - lo, 0)
+            grown = torch.zeros((max(2 * keep, ahead, 16), self.rows), dtype=torch.float32, device=dev)
+            grown[:keep] = self._u[self._u.shape[0] - keep:]
+            self._u, self._u_t0, lo = grown, self._t, 0
+        if ahead:
+            self._u[lo:lo + ahead, row] = u[1:, 0]
+        return u[0]
 
     def _embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
         """Token ids (M,) -> embed_tokens' rows (M, D)."""
@@ -1284,7 +1340,7 @@ class ContinuousBatcher:
             idle = [r for r in range(self.rows) if self.running[r] is None]
             if not idle:
                 break
-            ticket, prompt, max_new, prefix = self.queue[0]
+            ticket, prompt, max_new, prefix, sampler = self.queue[0]
             row, T = idle[0], prompt.shape[0]
             shared = [] if prefix is None else prefix.pages
             if not cache.assign(row, (0 if prefix is None else prefix.P) + T + max_new, shared=shared):
@@ -1306,15 +1362,21 @@ class ContinuousBatcher:
                 h = self.lm.model.extend_paged(torch.cat([prefix.tail, x.to(prefix.tail.dtype)])[None], cache, [row])
                 self.prefix_stats["hits"] += 1
                 self.prefix_stats["slots_shared"] += prefix.Ps
-            self.cur[row:row + 1] = self._tokens_of(h[:, -1].contiguous())
-            self.running[row] = _Running(ticket, max_new, [])
+            if sampler is None:
+                self.cur[row:row + 1] = self._tokens_of(h[:, -1].contiguous())
+            else:                                                                  # the first token: drawn from the admission's last state with u[0]
+                u0 = self._stream_of(row, sampler, max_new)
+                self.cur[row:row + 1] = ops.sample_rows(ops.linear(h[:, -1].contiguous(), self.w_lm), u0, sampler.temperature, sampler.top_k,
+                                                        sampler.top_p)
+            self.running[row] = _Running(ticket, max_new, [], sampler is not None)
             fresh.append(row)
         st["pages_high_water"] = max(st["pages_high_water"], cache.num_pages - cache.pages_free)
         return fresh
 
     def step(self) -> List[Tuple[int, torch.Tensor]]:
         """One round: admissions with their prefills, one decode step over all rows, one host read, releases.  Returns [(ticket, tokens (n,) int64)]
-        of the requests that finished in it."""
+        of the requests that finished in it - a sampled request that could not be drawn from among them, with the tokens drawn before and its
+        message in `errors`."""
         fresh = self._admit()
         if all(r is None for r in self.running):
             return []
@@ -1323,8 +1385,14 @@ class ContinuousBatcher:
         flags = [r is not None and not (i in fresh and r.max_new == 1) for i, r in enumerate(self.running)]
         if any(flags):
             active = torch.tensor(flags, dtype=torch.bool, device=self.device)
-            h = self.lm.model.decode_step_paged(self._embed_ids(self.cur), self.cache, active, active_host=flags)
-            self.cur = self._tokens_of(h)
+            sampled = any(f and r.sampled for f, r in zip(flags, self.running))
+            if not sampled:
+                h = self.lm.model.decode_step_paged(self._embed_ids(self.cur), self.cache, active, active_host=flags)
+                self.cur = self._tokens_of(h)
+            else:                                                                  # one launch selects for all rows; a -1 (read below) embeds as token 0
+                h = self.lm.model.decode_step_paged(self._embed_ids(self.cur.clamp_min(0)), self.cache, active, active_host=flags)
+                self.cur = ops.sample_rows_each(ops.linear(h, self.w_lm), self._u[self._t - self._u_t0], self.temperature, self.top_k, self.top_p)
+            self._t += 1
             self.stats["steps"] += 1
             self.stats["row_steps_active"] += sum(flags)
             self.stats["row_steps_total"] += self.rows
@@ -1336,20 +1404,31 @@ class ContinuousBatcher:
                 continue
             new = ([firsts[row]] if row in fresh else []) + ([toks[row]] if flags[row] else [])
             for t in new:
-                run.tokens.append(int(t))
-                if len(run.tokens) == run.max_new or (self.eos_ids is not None and int(t) in self.eos_ids):
+                if t < 0:                                                          # a sampled row that could not be drawn from: the request ends here
+                    self.errors[run.ticket] = (f"ContinuousBatcher.step: the logits of request {run.ticket} at step {len(run.tokens)} contain a NaN "
+                                               "or +inf, or no finite entry: no token can be drawn")
+                else:
+                    run.tokens.append(int(t))
+                if t < 0 or len(run.tokens) == run.max_new or (self.eos_ids is not None and int(t) in self.eos_ids):
                     self._released.update(p for p in self.cache.pages_of(row) if self.cache.page_refs[p] == 1)      # those that go back to the pool
                     self.cache.release(row)
                     self.running[row] = None
+                    if run.sampled:
+                        self.temperature[row] = 0.0                                # an idle row is a greedy row
                     done.append((run.ticket, torch.tensor(run.tokens, dtype=torch.int64, device=self.device)))
                     break
         return done
 
     def run(self, requests) -> List[torch.Tensor]:
-        """Submit every (prompt, max_new_tokens) pair - or (remainder, max_new_tokens, prefix handle) triple -, step until the queue and the rows
-        are empty; the token tensors in submit order."""
-        tickets = [self.submit(r[0], r[1], prefix=r[2] if len(r) > 2 else None) for r in requests]
+        """Submit every (prompt, max_new_tokens) pair - or (remainder, max_new_tokens, prefix handle or None[, sampler or None]) tuple -, step until
+        the queue and the rows are empty; the token tensors in submit order.  RuntimeError, after everything has drained, if a sampled request of
+        this call could not be drawn from: it names the tickets, `errors` holds each message, and the other requests' tokens were computed."""
+        tickets = [self.submit(r[0], r[1], prefix=r[2] if len(r) > 2 else None, sampler=r[3] if len(r) > 3 else None) for r in requests]
         out = {}
         while self.queue or any(r is not None for r in self.running):
             out.update(self.step())
+        failed = [t for t in tickets if t in self.errors]
+        if failed:
+            raise RuntimeError(f"ContinuousBatcher.run: the requests with tickets {failed} could not be drawn from and ended early (every other "
+                               f"request drained): {self.errors[failed[0]]}")
         return [out[t] for t in tickets]

@@ -1105,6 +1105,31 @@ def sample_rows(logits: Tensor, u: Tensor, temperature: float = 1.0, top_k: int 
     return out
 
 
+def sample_rows_each(logits: Tensor, u: Tensor, temperature: Tensor, top_k: Tensor, top_p: Tensor, out: Optional[Tensor] = None,
+                     probs: Optional[Tensor] = None) -> Tensor:
+    """`sample_rows` with the three parameters per row, still one launch: `temperature` and `top_p` fp32 (rows,), `top_k` int32 (rows,), on the
+    logits' device.  Row r is drawn under its own three values, bit for bit as `sample_rows` would draw it; temperature[r] == 0 makes it a greedy
+    row - `argmax_rows`' token, one-hot `probs`, u[r] ignored -; any other value outside `sample_rows`' domain gives -1 and zero `probs` for that
+    row alone (include/setok_hip.h, "Sampling")."""
+    rows, V = logits.shape
+    assert logits.stride(1) == 1 and logits.is_cuda
+    assert u.dtype == torch.float32 and u.numel() == rows
+    for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32)):
+        assert isinstance(t, Tensor) and t.dtype == dt and t.shape == (rows,) and t.is_contiguous() and t.device == logits.device, \
+            f"sample_rows_each: {name} must be a contiguous {dt} ({rows},) tensor on {logits.device}"
+    assert u.device == logits.device and (rows <= 1 or u.dim() == 0 or u.is_contiguous())
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and out.numel() == rows
+    ldp = 0
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.shape == (rows, V) and probs.stride(1) == 1 and probs.is_cuda
+        ldp = probs.stride(0) if rows > 1 else max(probs.stride(0), V)
+    _lib.call("setok_sample_rows_each", _stream(), _code(logits.dtype), logits.data_ptr(), logits.stride(0) if rows > 1 else max(logits.stride(0), V),
+              rows, V, _p(u), _p(temperature), _p(top_k), _p(top_p), _p(out), None if probs is None else probs.data_ptr(), ldp)
+    return out
+
+
 # ---- speculative decoding (csrc/speculate.hip) ---------------------------------------------------------------------------------------------------
 SPEC_MAX_K = 63                                   # drafted tokens per round: K + 1 <= 64 rows per sequence
 NGRAM_MAX_N = 8
